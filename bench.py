@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpixel/s of one JSPSR training step on 512x512 DEM tiles (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE config 3 / 4): JSPSR image+mask guided (jspsr_r8_img_msk.yml architecture,
@@ -10,9 +10,13 @@ synthetic inputs.  One step = zero_grad -> model(*inputs)
 0.1*Sobel-L1 -> backward -> gradient all-reduce (N > 1) -> AdamW step, i.e. the body of the
 reference's train_one_epoch (train/train_utils.py:210-219).  Weak scaling: 8 tiles per GPU.
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (K1, the HBM-bound propagation kernels,
-timed live with events on the launch stream; algorithmic bytes per SURVEY.md section 8d) and, at
-N = 1, "cpu_baseline" (the oracle's CPU restatement timed on the host cores on a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W untimed and K timed eager steps, writes
+the last timed step's outputs (--dump-outputs DIR) and prints the line; `ms_per_step` is the mean
+of the K timed steps.  --full adds the side legs to the same line: "host" (enqueue time of one
+step), "roofline" (K1, the HBM-bound propagation kernels, timed live with events on the launch
+stream; algorithmic bytes per SURVEY.md section 8d; and the conv kernels' MFMA rate), at N = 1
+"fp32", "inference" and "graph" (eager vs hipGraph replay, reported beside the headline), and
+"cpu_baseline" (the oracle's CPU restatement timed on the host cores on a bounded sample).
 """
 from __future__ import annotations
 
@@ -385,6 +389,25 @@ def launch_ranks(n):
     return rc
 
 
+def dump_outputs(out_dir, pred, losses, reducer, opt, sample=1 << 20):
+    """What the timed step hands its caller, as of the last timed step: the prediction (whole), the four loss terms, and
+    the updated parameters and their gradients (the flat buffers of FlatAdamW / GradReducer, 43.87 M values each) at a
+    fixed seeded sample of positions.  ~25 MB of .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = opt.flat_p.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, sample), replace=False))
+    idx_t = torch.from_numpy(idx).to(opt.flat_p.device)
+    arrays = {
+        "pred": pred.detach().float().cpu().numpy(),
+        "losses": np.array([float(losses[k]) for k in ("L1", "L2", "Grad", "Total")], dtype=np.float64),
+        "param_sample_index": idx.astype(np.float64),
+        "param_sample": opt.flat_p.index_select(0, idx_t).float().cpu().numpy(),
+        "grad_sample": reducer.flat.index_select(0, idx_t).float().cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def time_steps(step, n, warmup):
     for _ in range(warmup):
         step()
@@ -542,7 +565,7 @@ def graph_leg_child(args):
             return round((time.perf_counter() - t0) / n * 1e3, 3), round(host * 1e3, 3)
 
         # at the headline's tile count the replay is timed by the headline's own rules (W untimed steps, then EXACTLY K):
-        # the parent may take it as the headline where it is the faster way to run the step on this box
+        # the parent sets it beside the headline as `other_mode`
         n = args.steps if tiles == args.batch else max(5, min(args.steps, 10))
         warm = args.warmup if tiles == args.batch else 2
         e_ms, e_host = timed(eager, max(5, min(args.steps, 10)))
@@ -593,11 +616,17 @@ def main():
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16",
                     help="activation storage / MFMA operand type (BASELINE config 3 names bf16); "
                          "accumulation, BN statistics, K1 and master weights are fp32 either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 legs (N = 1 only)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the whole-scene strip forward (N = 1 only)")
-    ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph-replay leg (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0): prediction, loss terms, and a fixed "
+                         "sample of the updated parameters and their gradients")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (host enqueue time, roofline + conv MFMA rate, fp32, inference, hipGraph, "
+                         "CPU baseline); a plain run times the headline step only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the fp32 legs (N = 1 only)")
+    ap.add_argument("--no-inference", action="store_true", help="with --full: skip the whole-scene strip forward (N = 1 only)")
+    ap.add_argument("--no-graph", action="store_true", help="with --full: skip the hipGraph-replay leg (N = 1 only)")
     ap.add_argument("--graph-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.graph_child:
@@ -643,6 +672,7 @@ def main():
     opt = FlatAdamW(reducer, lr=1e-3, weight_decay=1e-6)  # configs/*.yml:71-76, one fused HIP launch
     criterion = MultiLoss(1.0, 1.0, 0.1)
     inputs, gt = synthetic_batch(args.batch, TILE, TILE, device, seed=1000 + rank)
+    last = {}
 
     def step():
         reducer.zero_grad()
@@ -651,6 +681,7 @@ def main():
         loss.backward()
         reducer.finish()
         opt.step()
+        last["pred"] = pred
         return loss
 
     for _ in range(args.warmup):
@@ -680,65 +711,64 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = loss.item()
-    # host side of one step: C-ABI calls issued and the time the host needs to enqueue them (no synchronisation inside)
-    torch.cuda.synchronize()
-    c0, h0 = _lib.calls, time.perf_counter()
-    step()
-    host_ms, abi_calls = (time.perf_counter() - h0) * 1e3, _lib.calls - c0
-    torch.cuda.synchronize()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["pred"], criterion.out, reducer, opt)
 
-    # the roofline leg runs right behind the training steps -- the state the kernels run in inside the model.  Behind
-    # the fp32 legs (seconds of fp32 MFMA work at the power limit) the same HBM-bound launches read 12-15 % slower on this
-    # pool's boxes (89.5 vs 78.1 us for the backward on one box, profiles/r04_*), which is the chip's power state, not the kernel.
-    roof = None
-    if rank == 0 and not args.no_roofline:
-        try:
-            roof = time_k1(model, inputs)
-            roof["convs"] = time_convs(args.batch, model.compute_dtype)
-        except Exception as e:       # (every side leg below likewise: none of them may take the headline line with it)
-            roof = {"error": f"{type(e).__name__}: {e}"[:300]}
-    fp32 = None
-    if world == 1 and args.dtype == "bf16" and not args.no_fp32:
-        try:
-            fp32 = fp32_legs(args, device, model, step)
-        except Exception as e:
-            fp32 = {"error": f"{type(e).__name__}: {e}"[:300]}
-            model.compute_dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    infer = None
-    if rank == 0 and world == 1 and not args.no_inference:
-        try:
-            infer = inference_leg(model, device)
-        except Exception as e:       # a side leg must not take the headline line with it
-            infer = {"error": f"{type(e).__name__}: {e}"[:300]}
-    graph = None
-    if rank == 0 and world == 1 and not args.no_graph:
-        torch.cuda.empty_cache()
-        graph = graph_leg(args)
-    cpu = None
-    if rank == 0 and not args.no_cpu_baseline:      # on rank 0 at every N: north_star wants the CPU figure "in the same run"
-        try:
-            cpu = cpu_baseline()
-        except Exception as e:
-            cpu = {"error": f"{type(e).__name__}: {e}"[:300]}
+    # --full only from here on: side legs behind the timed steps, reported beside the headline, never instead of it
+    host = roof = fp32 = infer = graph = cpu = None
+    if args.full:
+        # host side of one step: C-ABI calls issued and the time the host needs to enqueue them (no synchronisation inside)
+        torch.cuda.synchronize()
+        c0, h0 = _lib.calls, time.perf_counter()
+        step()
+        host_ms, abi_calls = (time.perf_counter() - h0) * 1e3, _lib.calls - c0
+        torch.cuda.synchronize()
+        host = {"abi_calls_per_step": abi_calls, "enqueue_ms_per_step": round(host_ms, 2),
+                "note": "C-ABI entry points called per step (each launches 1-3 kernels) and the host time to enqueue "
+                        "them with nothing to wait for; while it stays under ms_per_step the GPU, not the host, sets the step"}
+
+        # the roofline leg runs right behind the training steps -- the state the kernels run in inside the model.  Behind
+        # the fp32 legs (seconds of fp32 MFMA work at the power limit) the same HBM-bound launches read 12-15 % slower on this
+        # pool's boxes (89.5 vs 78.1 us for the backward on one box, profiles/r04_*), which is the chip's power state, not the kernel.
+        if rank == 0 and not args.no_roofline:
+            try:
+                roof = time_k1(model, inputs)
+                roof["convs"] = time_convs(args.batch, model.compute_dtype)
+            except Exception as e:       # (every side leg below likewise: none of them may take the headline line with it)
+                roof = {"error": f"{type(e).__name__}: {e}"[:300]}
+        if world == 1 and args.dtype == "bf16" and not args.no_fp32:
+            try:
+                fp32 = fp32_legs(args, device, model, step)
+            except Exception as e:
+                fp32 = {"error": f"{type(e).__name__}: {e}"[:300]}
+                model.compute_dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+        if rank == 0 and world == 1 and not args.no_inference:
+            try:
+                infer = inference_leg(model, device)
+            except Exception as e:       # a side leg must not take the headline line with it
+                infer = {"error": f"{type(e).__name__}: {e}"[:300]}
+        if rank == 0 and world == 1 and not args.no_graph:
+            torch.cuda.empty_cache()
+            graph = graph_leg(args)
+        if rank == 0 and not args.no_cpu_baseline:      # on rank 0 at every N: north_star wants the CPU figure "in the same run"
+            try:
+                cpu = cpu_baseline()
+            except Exception as e:
+                cpu = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     if rank == 0:
         px_per_step = args.batch * TILE * TILE * world
         ms = dt / args.steps * 1e3
         # N = 1: the same step, bit for bit, can run eagerly (Python enqueues ~1 400 launches per step) or as ONE hipGraph replay
         # (jspsr_amd.graph.GraphedStep).  Which is faster depends on the box's HOST: on this pool the eager step reads 60-64 ms
-        # on most boxes and 69-71 ms on those with a slow host, the replay 62-64 ms everywhere.  The headline is the faster of
-        # the two on THIS box, both timed by the same rules (W untimed steps, then exactly K; the replay in the graph leg's child
-        # process); `step_mode` says which, the other is kept beside it.
+        # on most boxes and 69-71 ms on those with a slow host, the replay 62-64 ms everywhere.  The headline is the eager step
+        # timed above, the reference's loop body as its train loop runs it; with --full the replay (timed by the same rules in
+        # the graph leg's child process) is kept beside it in `other_mode`.
         step_mode, alt = "eager", None
         gk = f"tiles_{args.batch}"
         if world == 1 and graph and gk in graph and graph[gk].get("graph_steps_timed") == args.steps:
             g_ms = graph[gk]["graph_ms_per_step"]
-            if g_ms < ms:
-                alt = {"mode": "eager", "ms_per_step": round(ms, 3), "value": round(px_per_step / ms / 1e3, 4)}
-                step_mode, ms, final_loss = "hipgraph replay (jspsr_amd.graph.GraphedStep), timed in the graph leg's child process", g_ms, graph[gk]["final_loss"]
-                dt = ms * args.steps / 1e3
-            else:
-                alt = {"mode": "hipgraph replay", "ms_per_step": g_ms, "value": round(px_per_step / g_ms / 1e3, 4)}
+            alt = {"mode": "hipgraph replay", "ms_per_step": g_ms, "value": round(px_per_step / g_ms / 1e3, 4)}
         line = {
             "metric": "Mpixels/sec fwd+bwd, JSPSR x8 on 512^2 DEM tiles",
             "value": round(px_per_step / (dt / args.steps) / 1e6, 4),
@@ -763,9 +793,7 @@ def main():
                 "parallelism": f"dp{world}", "final_loss": round(final_loss, 6),
                 "step_mode": step_mode, "other_mode": alt,
             },
-            "host": {"abi_calls_per_step": abi_calls, "enqueue_ms_per_step": round(host_ms, 2),
-                     "note": "C-ABI entry points called per step (each launches 1-3 kernels) and the host time to enqueue "
-                             "them with nothing to wait for; while it stays under ms_per_step the GPU, not the host, sets the step"},
+            "host": host,
             "roofline": roof,
             "cpu_baseline": cpu,
             "fp32": fp32,
