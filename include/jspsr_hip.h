@@ -184,6 +184,26 @@ int jspsr_head_backward(int dtype, const float* grad_planes, const float* w25, i
                         int gx_coff, void* grad_nhwc32, float* grad_b25, void* workspace, int B, int H, int W,
                         jspsr_stream_t stream);
 
+/* ---- K1p: the plain output head (spn=False): nn.Conv2d(C, 1, 3, padding=1) writing the fp32 prediction -----------------
+ * Replaces JSPSR's postprocessor = Basic2d(c0_channels, 1, 3, bn=False, relu=False) (models/JSPSR.py:195-204,378) and EDSR's
+ * self.head (models/EDSR.py:108-111,132-136), and their autograd.  fp32 arithmetic (bf16 inputs widened exactly), fixed
+ * summation order.
+ *   x      NHWC (B,H,W,·) of `dtype` (JSPSR_F32 / JSPSR_BF16), channel pitch x_cstride, first channel x_coff (both multiples of
+ *          4 fp32 / 8 bf16), 16-byte aligned; C a multiple of 8, at most 256 (JSPSR_EINVAL otherwise, before any launch)
+ *   w      [C][3][3] fp32 (the nn.Conv2d weight as it is), bias [1] fp32;  y  (B,1,H,W) fp32
+ * Zero padding at the image borders only; any H, W.
+ * Backward, one pass over dy (B,1,H,W) fp32 and x: dx (NHWC, `dtype`, pitch / offset as x; NULL = not wanted), dw [C][3][3] and
+ * db [1] fp32, overwritten.  The weight / bias gradient goes through per-workgroup partial rows in `workspace`
+ * (jspsr_conv_head1_workspace_bytes(B, H, W, C) bytes, 16-byte aligned; 0 for an unsupported C) folded in a fixed order by
+ * a second launch: the same bits from run to run.  Launch-count names "head1_forward", "head1_backward",
+ * "head1_backward_fold". */
+int jspsr_conv_head1_forward(int dtype, const void* x, int x_cstride, int x_coff, int C, const float* w, const float* bias,
+                             float* y, int B, int H, int W, jspsr_stream_t stream);
+size_t jspsr_conv_head1_workspace_bytes(int B, int H, int W, int C);
+int jspsr_conv_head1_backward(int dtype, const float* dy, const void* x, int x_cstride, int x_coff, int C, const float* w,
+                              void* dx, int dx_cstride, int dx_coff, float* dw, float* db, void* workspace, int B, int H,
+                              int W, jspsr_stream_t stream);
+
 /* ---- K2: convolutions on the matrix cores (implicit GEMM, NHWC) ---------------------------
  * Replace the reference's nn.Conv2d / nn.ConvTranspose2d calls and their autograd
  * (models/components/basics.py:6-20,39-47,69-77; every conv of models/JSPSR.py:66-180 and

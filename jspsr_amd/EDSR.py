@@ -1,7 +1,7 @@
-"""``EDSR`` -- drop-in for the reference's ``models.EDSR.EDSR`` in the configuration that shares the hot
-path (models/EDSR.py:66-137 with ``scale=1, spn=True``): BN-free residual trunk feeding the same
-affinity/offset generator and propagation step as JSPSR.  Same constructor arguments, ``forward(x)``
-with ``x = cat(dem, guides)`` (B,C,H,W) and ``state_dict`` keys.
+"""``EDSR`` -- drop-in for the reference's ``models.EDSR.EDSR`` with ``scale=1`` (models/EDSR.py:66-137): BN-free
+residual trunk feeding either the same affinity/offset generator and propagation step as JSPSR (``spn=True``) or the
+plain 3x3 one-channel head (``spn=False``, the reference's default for EDSR, utils/config.py:95-99).  Same constructor
+arguments, ``forward(x)`` with ``x = cat(dem, guides)`` (B,C,H,W) and ``state_dict`` keys.
 """
 from __future__ import annotations
 
@@ -34,13 +34,15 @@ class ResBlock(nn.Module):
 
 
 class EDSR(HotPathModule):
-    receptive_radius = None      # sharded inference (tiling.py): not certified for this network (check_reach=False only)
+    receptive_radius = None      # sharded inference (tiling.py): spn=True is not certified (check_reach=False only)
 
     def __init__(self, in_channels=3, out_channels=3, n_resblocks=16, n_features=64, scale=2, res_scale=0.1,
                  spn=False):
         super().__init__()
-        if scale != 1 or not spn:
-            raise NotImplementedError("only scale=1, spn=True (the configuration on the JSPSR hot path) is built")
+        if scale != 1:
+            raise NotImplementedError("only scale=1 (no Upscaler) is built")
+        if not spn and out_channels != 1:
+            raise NotImplementedError("spn=False is built for out_channels=1 (the one-channel DEM head)")
         self.url = r"./models/pretrained/EDSR-b32f128x2.bin"
         self.in_channels, self.out_channels = in_channels, out_channels
         self.res_scale, self.spn = res_scale, spn
@@ -49,8 +51,14 @@ class EDSR(HotPathModule):
         blocks = [ResBlock(n_features, res_scale) for _ in range(n_resblocks)]
         blocks.append(nn.Conv2d(n_features, n_features, 3, padding=1))
         self.encoder = nn.Sequential(*blocks)
-        self.generator = Generator(n_features, 3, bc=n_features // 2)
-        self.post_layer = PostProcessor(3, True)
+        if spn:
+            self.generator = Generator(n_features, 3, bc=n_features // 2)
+            self.post_layer = PostProcessor(3, True)
+        else:   # EDSR.py:108-111
+            self.head = nn.Conv2d(n_features, out_channels, 3, padding=1)
+            # no BatchNorm, no gate, no learned offsets: entry 1 + 2 per block + tail 1 + head 1 (tiling.py)
+            self.receptive_radius = 2 * n_resblocks + 3
+            self.learned_offsets = False
         for m in self.modules():  # EDSR.py:109-117
             if isinstance(m, nn.Conv2d):
                 n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
@@ -70,4 +78,6 @@ class EDSR(HotPathModule):
                 h = blk(h)
             tail = self.encoder[-1]
             h = E.conv2d(h, tail.weight, tail.bias, 1, 1) + self.res_scale * xs
+            if not self.spn:   # EDSR.py:135, on the fp32-output head kernel
+                return E.conv_head1(h, self.head.weight, self.head.bias)
             return self.post_layer.from_feature(dem.float(), self.generator.features(E.from_nchw(dem), h), self.generator)

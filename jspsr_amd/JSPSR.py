@@ -26,6 +26,9 @@ class Model(HotPathModule):
     # pixels of input a prediction depends on beyond its own position, learned offsets aside (tiling.py certifies strips
     # with it): stem 2 + encoder 4+8+16+32 + decoder 16+8+4 + conv0 1 + generator 5 + 3x3 sampler 1
     receptive_radius = 97
+    # spn=False (the no-propagation ablation, JSPSR.py:195-204,378): the 3x3 conv head replaces generator + sampler, so the
+    # radius is 97 - 5 - 1 + 1 = 92 and there are no learned offsets (tiling.py certifies on the radius alone)
+    plain_receptive_radius = 92
 
     def __init__(self, in_channels: dict, out_channels: int = 1, num_feature: int = 32,
                  layers: tuple = (2, 2, 2, 2), res_scale: tuple = (1, 1, 1, 1), spn: bool = True,
@@ -38,8 +41,8 @@ class Model(HotPathModule):
         self.spn_scale = spn_scale
         self.compute_dtype = torch.float32  # or torch.bfloat16: bf16 storage, fp32 accumulate/statistics
         assert len(in_channels) > 1, "At least 2 input data are required"
-        if not spn:
-            raise NotImplementedError("spn=False (plain conv head) is outside the hot path")
+        if not spn and out_channels != 1:
+            raise NotImplementedError("spn=False is built for out_channels=1 (the one-channel DEM head)")
         nf = num_feature
         self.flag_dem_img = "image" in in_channels
         self.flag_dem_msk = "mask" in in_channels
@@ -74,8 +77,14 @@ class Model(HotPathModule):
         self.layer2d = UpUnit(nf * 8 + nf * 8 * nb, nf * 4)
         self.layer1d = UpUnit(nf * 4 + nf * 4 * nb, nf * 2)
         self.conv0 = ConvUnit(nf * 2 + nf * 2 * nb, nf * 2, 3, bn=True, relu=True, gate=True)
-        self.generator = Generator(in_channels=nf * 2, kernel_size=3, bc=nf)
-        self.postprocessor = PostProcessor(kernel_size=3, residual=True, scale=self.spn_scale)
+        if spn:
+            self.generator = Generator(in_channels=nf * 2, kernel_size=3, bc=nf)
+            self.postprocessor = PostProcessor(kernel_size=3, residual=True, scale=self.spn_scale)
+        else:   # JSPSR.py:195-204: Basic2d(c0_channels, out_channels, 3, bn=False, relu=False)
+            self.generator = None
+            self.postprocessor = ConvUnit(nf * 2, out_channels, 3, bn=False, relu=False)
+            self.receptive_radius = self.plain_receptive_radius
+            self.learned_offsets = False
         self._initialize_weights()
 
     # -- init: truncated normal +-2 sigma, sigma = sqrt(2.6 / (k*k*C_in)) (JSPSR.py:494-517) -------
@@ -231,6 +240,9 @@ class Model(HotPathModule):
             # first block (grad_extra above) instead of by autograd
             x = buf.join([up(x, dest=(buf, 0))] + joined[s], 0, defer=nb if defer_skip else 0)
         c0 = self.conv0(x)
+        if not self.spn:    # :378, on the fp32-output head kernel
+            head = self.postprocessor.conv[0]
+            return E.conv_head1(c0, head.weight, head.bias)
         dem = dem.detach()  # :372
         # the two 1x1 heads write the planes the propagation kernel reads (sigmoid, zero centre offset, mean subtraction,
         # gather, residual: one kernel -- the one of the public PostProcessor boundary; engine.heads_propagate)

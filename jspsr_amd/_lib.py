@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lock = threading.Lock()
 _lib = None
@@ -44,6 +44,9 @@ SIGNATURES = {
     "jspsr_head_forward": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "jspsr_head_backward_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_head_backward": (c_i, [c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "jspsr_conv_head1_forward": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "jspsr_conv_head1_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "jspsr_conv_head1_backward": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "jspsr_pack_weight": (c_i, [c_i, c_p, c_p] + [c_i] * 6 + [c_p]),
     "jspsr_pack_chunk": (c_i, []),
     "jspsr_pack_weights_multi": (c_i, [c_p, c_i, c_ll, c_p]),

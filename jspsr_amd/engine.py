@@ -187,6 +187,12 @@ def heads_propagate(dem, feature, conv_weight, conv_offset, w, b, scale=1.0):
     return ops.propagate_head(dem, head, w, b, scale)
 
 
+def conv_head1(x, weight, bias):
+    """K1p: the plain 3x3 one-channel output head of the spn=False models (JSPSR.py:195-204,378; EDSR.py:108-111,135):
+    NHWC feature in the compute dtype -> the (B,1,H,W) fp32 prediction, never rounded to the compute dtype."""
+    return ops.conv_head1(x, weight, bias)
+
+
 def cat(tensors):
     return torch.cat(tuple(tensors), 3)
 

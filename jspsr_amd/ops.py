@@ -401,6 +401,48 @@ def head_planes(x, w_weight, b_weight, w_offset, b_offset):
     return _HeadPlanes.apply(x, w25, b25)
 
 
+# ---- K1p: the plain output head of the spn=False models (JSPSR postprocessor, EDSR head) ------------------------------
+class _ConvHead1(torch.autograd.Function):
+    """nn.Conv2d(C, 1, 3, padding=1) on an NHWC feature (dense or a channel slice) -> (B,1,H,W) fp32: jspsr_conv_head1_forward;
+    backward = jspsr_conv_head1_backward (dx in the compute dtype, dW / db fp32 through a fixed-order fold)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = K.nhwc(x)
+        B, H, W, C = x.shape
+        if tuple(weight.shape) != (1, C, 3, 3) or bias is None or bias.numel() != 1:
+            raise ValueError(f"conv_head1: weight {tuple(weight.shape)} / bias must be (1,{C},3,3) / (1,)")
+        w = weight.detach().contiguous().float()
+        b = bias.detach().contiguous().float()
+        y = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        _lib.check(lib.jspsr_conv_head1_forward(K._dt(x), x.data_ptr(), K.pitch(x), 0, C, w.data_ptr(), b.data_ptr(),
+                                                y.data_ptr(), B, H, W, _stream()), "jspsr_conv_head1_forward")
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dy = dy.contiguous().float()
+        lib = _lib.load()
+        dx = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((1, C, 3, 3), dtype=torch.float32, device=x.device)
+        db = torch.empty(1, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.jspsr_conv_head1_workspace_bytes(B, H, W, C), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.jspsr_conv_head1_backward(K._dt(x), dy.data_ptr(), x.data_ptr(), K.pitch(x), 0, C, w.data_ptr(),
+                                                 dx.data_ptr() if dx is not None else None, C, 0, dw.data_ptr(),
+                                                 db.data_ptr(), ws.data_ptr(), B, H, W, _stream()),
+                   "jspsr_conv_head1_backward")
+        return dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
+
+
+def conv_head1(x, weight, bias):
+    """(B,H,W,C) NHWC feature (fp32 | bf16) -> (B,1,H,W) fp32 = nn.Conv2d(C, 1, 3, padding=1) with fp32 arithmetic."""
+    return _ConvHead1.apply(x, weight, bias)
+
+
 class _PropagateLogits(torch.autograd.Function):
     """Sigmoid (spn.py:43) + zero centre offset (spn.py:69-73) + PostProcessor.forward (spn.py:99-118) on the planar
     head: jspsr_prop_logits_forward_f32 / _backward_f32 -- the kernels of the public PostProcessor boundary."""

@@ -129,7 +129,8 @@ def _run(model, tiles, windows, combine, check_reach=True):
             out = model(*tiles)
     finally:
         E._gate_sync, E._offset_probe = prev, prev_probe
-    if check_reach and not probe:
+    plain = getattr(model, "learned_offsets", True) is False     # a plain conv head: exactness is the radius alone
+    if check_reach and not probe and not plain:
         raise RuntimeError(f"{type(model).__name__} reported no learned offsets during the sharded forward: the halo check "
                            "would pass vacuously (every propagation step must append to engine._offset_probe)")
     chained = bool(getattr(model, "offsets_chain", False))   # steps applied to their own output: the reaches add up
