@@ -389,6 +389,34 @@ int jspsr_loss_backward(const float* pred, const float* gt, const float* grad_to
                         float wg, float* grad_pred, const void* workspace, int B, int H, int W,
                         jspsr_stream_t stream);
 
+/* The rest of the reference's loss menu (get_loss, losses/loss_schemes.py:6-33; get_criterion,
+ * utils/common_config.py:209-233) on fp32 (planes, H, W) tensors (ABI v17).  `terms` is a bit set: 1 BerHu
+ * (BerhuLoss, losses/loss_functions.py:191-208), 2 BCE-with-logits (nn.BCEWithLogitsLoss), 4 surface normal of a
+ * one-channel map (SurfaceNormalLoss :211-229), 8 SSIM (SSIMLoss :232-239 = 1 - piq.ssim(clamp(pred,0,1), gt,
+ * data_range=1, downsample=False): 11-tap Gaussian (sigma 1.5) window, valid map (H-10) x (W-10)).  Term slots:
+ * 0 L1, 1 L2, 2 Grad (taken from losses[0..2] of jspsr_loss_forward, passed as base_losses), 3 BerHu, 4 BCE, 5 Norm,
+ * 6 SSIM.  BerHu's threshold 0.6 max|pred - gt| stays in device memory.  No host synchronisation.
+ * Forward: out[k] = the term of key k (key_slot[k], host array of n_keys <= 16), out[n_keys] = Total = sum_k
+ * key_weight[k] * out[k] (host doubles; in double, rounded once).  workspace: jspsr_loss_menu_workspace_bytes(), shared
+ * with the backward, which ADDS d(sum_s slot_weight[s] term_s)/d(pred) * grad_total[0] over the slots 3..6 of `terms`
+ * (slot_weight: host doubles [7]; grad_total may be NULL = 1) to grad_pred.  JSPSR_EINVAL on bad arguments, SSIM with
+ * H < 11 or W < 11 among them; the workspace query returns 0 there. */
+size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W);
+int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int planes, int H, int W, int n_keys,
+                            const int* key_slot, const double* key_weight, const float* base_losses, float* out,
+                            void* workspace, jspsr_stream_t stream);
+int jspsr_loss_menu_backward(const float* pred, const float* gt, int terms, int planes, int H, int W,
+                             const double* slot_weight, const float* grad_total, float* grad_pred,
+                             const void* workspace, jspsr_stream_t stream);
+/* Mean SSIM of prepared [0,1] tiles (MeterSSIM.update, evaluation/metrics.py:275-335), pred clamped to [0,1]:
+ * same = 0 is piq.ssim(downsample=False) on the valid map with the Gaussian window (window11 ignored, may be NULL);
+ * same = 1 is the local ssim (metrics.py:20-63): H x W map over the zero-padded planes with the 11-tap window11 (host
+ * floats; NULL = the Gaussian).  out[0] (device) = the mean over every map element of every plane.  workspace:
+ * jspsr_ssim_workspace_bytes() (0 = bad arguments). */
+size_t jspsr_ssim_workspace_bytes(int planes, int H, int W, int same);
+int jspsr_ssim_forward(const float* pred, const float* gt, int planes, int H, int W, int same, const float* window11,
+                       float* out, void* workspace, jspsr_stream_t stream);
+
 /* Evaluation scores of one tile on the device (evaluation/metrics.py: MeterBase._prepare :147-199, MeterPSNR :229-235,
  * MeterRMSE :372-384, MeterMedian :453, MeterNMAD :508-510, MeterLE95 :565-568; ToDEM.descale_data,
  * data/data_utils.py:441-457).  pred, gt: fp32 [H][W] in the network's [0,1] range (the reference evaluates one tile

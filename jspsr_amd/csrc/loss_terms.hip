@@ -1,0 +1,499 @@
+// The rest of the reference's loss menu (losses/loss_schemes.py:6-33, utils/common_config.py:209-233) on fp32
+// (planes, H, W) tensors, beside the fused L1 + L2 + Sobel pair of train_step.hip:
+//   * pointwise terms, one pass: BerHu (loss_functions.py:191-208), BCE-with-logits (nn.BCEWithLogitsLoss) and the
+//     surface-normal loss of a one-channel map (:211-229).  BerHu's threshold 0.6 max|pred - gt| comes from a max pass
+//     before the sum pass and stays in the workspace (no host round trip; a captured graph replays it).
+//   * SSIM (SSIMLoss :232-239 = 1 - piq.ssim(clamp(pred,0,1), gt, data_range=1, downsample=False)): five 11x11 window
+//     moments per map element, separable (an 11-tap horizontal then an 11-tap vertical pass out of LDS), valid mode for
+//     the loss; zero-padded "same" mode with a caller's window for the local meter (evaluation/metrics.py:20-63).  The
+//     forward writes the three per-element coefficients of dS/d(moment) so that the backward is the adjoint filter of
+//     those three maps plus an epilogue.
+// Every reduction writes per-workgroup partials folded in a fixed order in double: the same bits on every run.
+// Gradients accumulate (+=) into a buffer the caller has already written.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+using namespace jspsr;
+
+constexpr int PT = 256;          // pointwise workgroup
+constexpr int ST = 32;           // SSIM tile edge (map elements forward, pixels backward)
+constexpr int SH = ST + 10;      // staged edge: tile + 10-px halo of the 11-tap window
+constexpr int SN = 256;          // SSIM workgroup: 8 row groups x 32 columns, 4 rows each
+constexpr float C1 = 1e-4f;      // (0.01 * data_range)^2
+constexpr float C2 = 9e-4f;      // (0.03 * data_range)^2
+
+enum { T_BERHU = 1, T_BCE = 2, T_NORM = 4, T_SSIM = 8, T_ALL = 15 };
+enum { S_L1, S_L2, S_GRAD, S_BERHU, S_BCE, S_NORM, S_SSIM, NSLOT };
+constexpr int MAXKEY = 16;
+
+struct Win11 {
+  float w[11];
+};
+
+struct KeyMap {             // the configured keys in config order: slot and weight of each
+  int n;
+  int slot[MAXKEY];
+  double w[MAXKEY];
+};
+
+int pw_blocks(long long n) {
+  long long b = (n + PT - 1) / PT;
+  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+
+// the max pass: few partials, since every workgroup of the sum pass folds all of them
+int max_blocks(long long n) {
+  long long b = (n + PT - 1) / PT;
+  return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
+}
+
+size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// piq's window: 11 taps, sigma 1.5, centred, normalised (the 2-D window is the outer product)
+Win11 gaussian_window() {
+  double g[11], s = 0.0;
+  for (int i = 0; i < 11; ++i) { const double c = i - 5.0; g[i] = exp(-(c * c) / (2.0 * 1.5 * 1.5)); s += g[i]; }
+  Win11 k;
+  for (int i = 0; i < 11; ++i) k.w[i] = (float)(g[i] / s);
+  return k;
+}
+
+struct Layout {             // one workspace for the whole menu forward + backward
+  int nb = 0, nbm = 0, nbs = 0, tiles_x = 0, tiles_y = 0, Hm = 0, Wm = 0;
+  size_t th = 0, pmax = 0, psum = 0, ssum = 0, coef = 0, bytes = 0;
+  long long cplane = 0;     // elements of one coefficient map set: planes * Hm * Wm
+};
+
+Layout layout(int terms, int planes, int H, int W) {
+  Layout L;
+  const long long n = (long long)planes * H * W;
+  L.nb = pw_blocks(n);
+  L.nbm = max_blocks(n);
+  size_t off = 16;          // th[4] = {thf, th^2 as float, 2 th as float, -}
+  if (terms & (T_BERHU | T_BCE | T_NORM)) {
+    L.pmax = off; off += al16((size_t)L.nbm * 4);
+    L.psum = off; off += al16((size_t)L.nb * 3 * 4);
+  }
+  if (terms & T_SSIM) {
+    L.Hm = H - 10; L.Wm = W - 10;
+    L.tiles_x = (L.Wm + ST - 1) / ST; L.tiles_y = (L.Hm + ST - 1) / ST;
+    L.nbs = L.tiles_x * L.tiles_y * planes;
+    L.ssum = off; off += al16((size_t)L.nbs * 4);
+    L.cplane = (long long)planes * L.Hm * L.Wm;
+    L.coef = off; off += al16((size_t)L.cplane * 3 * 4);
+  }
+  L.bytes = off;
+  return L;
+}
+
+__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// Block reduction of one float (sum or max) over SN/PT = 256 threads into lane 0 of wave 0 (fixed order).
+template <bool MAX>
+__device__ __forceinline__ float block_reduce(float v, float* red) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const float o = __shfl_xor(v, d, 64);
+    v = MAX ? fmaxf(v, o) : v + o;
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = MAX ? fmaxf(t, red[w]) : t + red[w];
+  return t;
+}
+
+// ---- pointwise terms --------------------------------------------------------------------------------------------
+// Per-element BerHu as torch evaluates the reference's expression with th a Python float: the comparison and both
+// constants in fp32, no contraction of diff^2 + th^2.
+__device__ __forceinline__ float berhu_elem(float ad, float thf, float t2f, float tw) {
+#pragma clang fp contract(off)
+  return ad <= thf ? ad : (ad * ad + t2f) / tw;
+}
+
+__device__ __forceinline__ float bce_elem(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
+
+__device__ __forceinline__ float unit(float v) { return v / fmaxf(fabsf(v), 1e-12f); }   // F.normalize, C = 1
+
+__global__ __launch_bounds__(PT) void menu_max_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     long long n, float* __restrict__ pmax) {
+  __shared__ float red[PT / 64];
+  float m = 0.f;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT)
+    m = fmaxf(m, fabsf(pred[i] - gt[i]));
+  m = block_reduce<true>(m, red);
+  if (threadIdx.x == 0) pmax[blockIdx.x] = m;
+}
+
+// partial sums {BerHu, BCE, 1 - p^.g^} per workgroup; block 0 stores BerHu's threshold for the backward
+__global__ __launch_bounds__(PT) void menu_sum_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     long long n, int terms, const float* __restrict__ pmax, int nb,
+                                                     float* __restrict__ th, float* __restrict__ psum) {
+  __shared__ float red[3][PT / 64];
+  float thf = 0.f, t2f = 0.f, tw = 0.f;
+  if (terms & T_BERHU) {
+    float m = 0.f;
+    for (int r = threadIdx.x; r < nb; r += PT) m = fmaxf(m, pmax[r]);
+    m = block_reduce<true>(m, red[0]);
+    __syncthreads();
+    const double t = 0.6 * (double)m;       // delta * torch.max(diff).item()
+    thf = (float)t; t2f = (float)(t * t); tw = (float)(2.0 * t);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { th[0] = thf; th[1] = t2f; th[2] = tw; th[3] = 0.f; }
+  }
+  float sb = 0.f, sc = 0.f, sn = 0.f;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    const float x = pred[i], y = gt[i];
+    if (terms & T_BERHU) sb += berhu_elem(fabsf(x - y), thf, t2f, tw);
+    if (terms & T_BCE) sc += bce_elem(x, y);
+    if (terms & T_NORM) sn += 1.f - unit(x) * unit(y);
+  }
+  float v[3] = {sb, sc, sn};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
+    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    float t = 0.f;
+    for (int w = 0; w < PT / 64; ++w) t += red[threadIdx.x][w];
+    psum[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+  }
+}
+
+// grad += up * (wb/n BerHu' + wc/n BCE' + wn/n Norm').  BerHu's threshold is a constant (the reference detaches it by
+// .item()); at th = 0 every element takes the |d| branch, whose gradient there is 0 (the reference: NaN, see header).
+__global__ __launch_bounds__(PT) void menu_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     long long n, int terms, const float* __restrict__ th,
+                                                     const float* __restrict__ gscale, float cb, float cc, float cn,
+                                                     float* __restrict__ grad) {
+  const float up = gscale ? gscale[0] : 1.f;
+  const float thf = (terms & T_BERHU) ? th[0] : 0.f, tw = (terms & T_BERHU) ? th[2] : 1.f;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    const float x = pred[i], y = gt[i];
+    float g = 0.f;
+    if (terms & T_BERHU) {
+      const float d = x - y, ad = fabsf(d);
+      g += cb * (ad <= thf ? sgnf(d) : 2.f * ad / tw * sgnf(d));
+    }
+    if (terms & T_BCE) g += cc * (1.f / (1.f + expf(-x)) - y);
+    if (terms & T_NORM) g += fabsf(x) <= 1e-12f ? -cn * unit(y) : 0.f;
+    grad[i] += up * g;
+  }
+}
+
+// ---- SSIM -------------------------------------------------------------------------------------------------------
+// Forward over one ST x ST tile of the map of one plane.  SAME = false: valid map (H-10) x (W-10), map element q reads
+// pixels q .. q+10; SAME = true: H x W map over the zero-padded plane, q reads q-5 .. q+5.  x = clamp(pred, 0, 1).
+// coef (valid mode, may be NULL): alpha, beta, gamma of every map element, three planar maps cplane apart.
+template <bool SAME>
+__global__ __launch_bounds__(SN) void ssim_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     int H, int W, int Hm, int Wm, int tiles_x, Win11 k,
+                                                     float* __restrict__ coef, long long cplane,
+                                                     float* __restrict__ part) {
+  __shared__ float xs[SH * SH], ys[SH * SH];
+  __shared__ float hs[5][SH * ST];
+  __shared__ float red[SN / 64];
+  const int plane = blockIdx.y, tile = blockIdx.x;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int q0y = ty * ST, q0x = tx * ST;
+  const int i0y = q0y - (SAME ? 5 : 0), i0x = q0x - (SAME ? 5 : 0);
+  const float* P = pred + (long long)plane * H * W;
+  const float* G = gt + (long long)plane * H * W;
+  for (int o = threadIdx.x; o < SH * SH; o += SN) {
+    const int r = o / SH, c = o - r * SH;
+    const int iy = i0y + r, ix = i0x + c;
+    float xv = 0.f, yv = 0.f;
+    if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+      const long long j = (long long)iy * W + ix;
+      xv = fminf(fmaxf(P[j], 0.f), 1.f);
+      yv = G[j];
+    }
+    xs[o] = xv;
+    ys[o] = yv;
+  }
+  __syncthreads();
+  // horizontal: SH rows x ST columns of the five moments
+  for (int o = threadIdx.x; o < SH * ST; o += SN) {
+    const int r = o / ST, c = o - r * ST;
+    const float* xr = xs + r * SH + c;
+    const float* yr = ys + r * SH + c;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 11; ++t) {
+      const float xv = xr[t], yv = yr[t], w = k.w[t];
+      a0 += w * xv;
+      a1 += w * yv;
+      a2 += w * (xv * xv);
+      a3 += w * (yv * yv);
+      a4 += w * (xv * yv);
+    }
+    hs[0][o] = a0; hs[1][o] = a1; hs[2][o] = a2; hs[3][o] = a3; hs[4][o] = a4;
+  }
+  __syncthreads();
+  // vertical: 4 consecutive rows of one column per thread share 14 staged rows
+  const int c = threadIdx.x & (ST - 1), r0 = (threadIdx.x >> 5) * 4;
+  float mo[5][4];
+#pragma unroll
+  for (int m = 0; m < 5; ++m) {
+    float v[14];
+#pragma unroll
+    for (int t = 0; t < 14; ++t) v[t] = hs[m][(r0 + t) * ST + c];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float a = 0.f;
+#pragma unroll
+      for (int t = 0; t < 11; ++t) a += k.w[t] * v[j + t];
+      mo[m][j] = a;
+    }
+  }
+  float s_acc = 0.f;
+  const int qx = q0x + c;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int qy = q0y + r0 + j;
+    if (qy < Hm && qx < Wm) {
+      const float mx = mo[0][j], my = mo[1][j];
+      const float sxx = mo[2][j] - mx * mx, syy = mo[3][j] - my * my, sxy = mo[4][j] - mx * my;
+      const float A = 2.f * mx * my + C1, B = mx * mx + my * my + C1, Cc = 2.f * sxy + C2, D = sxx + syy + C2;
+      const float S = (A * Cc) / (B * D);
+      s_acc += S;
+      if (!SAME && coef) {
+        const long long qi = (long long)plane * Hm * Wm + (long long)qy * Wm + qx;
+        coef[qi] = S * (2.f * my / A - 2.f * mx / B - 2.f * my / Cc + 2.f * mx / D);
+        coef[cplane + qi] = -S / D;
+        coef[2 * cplane + qi] = 2.f * S / Cc;
+      }
+    }
+  }
+  s_acc = block_reduce<false>(s_acc, red);
+  if (threadIdx.x == 0) part[(size_t)plane * gridDim.x + tile] = s_acc;
+}
+
+// Backward (valid mode) over one ST x ST pixel tile of one plane: the adjoint ("full") window filter of alpha, beta,
+// gamma (zero outside the map), then grad[p] += -(w up / M) [Ka + 2 x Kb + y Kg] where 0 <= pred <= 1 (clamp's mask).
+__global__ __launch_bounds__(SN) void ssim_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     const float* __restrict__ coef, long long cplane, int H, int W,
+                                                     int Hm, int Wm, int tiles_x, Win11 k,
+                                                     const float* __restrict__ gscale, float cw,
+                                                     float* __restrict__ grad) {
+  __shared__ float cs[3][SH * SH];
+  __shared__ float hs[3][SH * ST];
+  const int plane = blockIdx.y, tile = blockIdx.x;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int p0y = ty * ST, p0x = tx * ST;
+  const int q0y = p0y - 10, q0x = p0x - 10;          // map elements whose window covers a pixel of the tile
+  for (int o = threadIdx.x; o < SH * SH; o += SN) {
+    const int r = o / SH, c = o - r * SH;
+    const int qy = q0y + r, qx = q0x + c;
+    float a = 0.f, b = 0.f, g = 0.f;
+    if (qy >= 0 && qy < Hm && qx >= 0 && qx < Wm) {
+      const long long qi = (long long)plane * Hm * Wm + (long long)qy * Wm + qx;
+      a = coef[qi];
+      b = coef[cplane + qi];
+      g = coef[2 * cplane + qi];
+    }
+    cs[0][o] = a; cs[1][o] = b; cs[2][o] = g;
+  }
+  __syncthreads();
+  for (int o = threadIdx.x; o < SH * ST; o += SN) {
+    const int r = o / ST, c = o - r * ST;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 11; ++t) {          // pixel column c reads map columns c + 10 - t
+      const int j = r * SH + c + 10 - t;
+      const float w = k.w[t];
+      a0 += w * cs[0][j];
+      a1 += w * cs[1][j];
+      a2 += w * cs[2][j];
+    }
+    hs[0][o] = a0; hs[1][o] = a1; hs[2][o] = a2;
+  }
+  __syncthreads();
+  const int c = threadIdx.x & (ST - 1), r0 = (threadIdx.x >> 5) * 4;
+  float kf[3][4];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    float v[14];
+#pragma unroll
+    for (int t = 0; t < 14; ++t) v[t] = hs[m][(r0 + t) * ST + c];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float a = 0.f;
+#pragma unroll
+      for (int t = 0; t < 11; ++t) a += k.w[t] * v[j + 10 - t];
+      kf[m][j] = a;
+    }
+  }
+  const float s = -(gscale ? gscale[0] : 1.f) * cw;
+  const int px = p0x + c;
+  const long long base = (long long)plane * H * W;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int py = p0y + r0 + j;
+    if (py < H && px < W) {
+      const long long i = base + (long long)py * W + px;
+      const float x = pred[i], y = gt[i];
+      if (x >= 0.f && x <= 1.f) grad[i] += s * (kf[0][j] + 2.f * x * kf[1][j] + y * kf[2][j]);
+    }
+  }
+}
+
+// Fixed-order double fold of `rows` partials of column q (stride `cols`) by one wave; the sum lands in every lane.
+__device__ double wave_fold(const float* __restrict__ p, int rows, int cols, int q) {
+  const int lane = threadIdx.x & 63;
+  double s = 0.0;
+  if (p)
+    for (int r = lane; r < rows; r += 64) s += (double)p[(size_t)r * cols + q];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+// out[k] = term of key k (config order), out[n] = Total = sum_k w_k out[k] (in double over the fp32 values, rounded
+// once).  Slots 0..2 come from jspsr_loss_forward's losses[0..2] when the caller passes them.
+__global__ void menu_combine_kernel(const float* __restrict__ psum, int nb, const float* __restrict__ ssum, int nbs,
+                                    long long n, long long m, const float* __restrict__ base, KeyMap km,
+                                    float* __restrict__ out) {
+  __shared__ double acc[4];
+  const int q = threadIdx.x >> 6;
+  const double s = q < 3 ? wave_fold(psum, nb, 3, q) : wave_fold(ssum, nbs, 1, 0);
+  if ((threadIdx.x & 63) == 0) acc[q] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    float f[NSLOT];
+    for (int i = 0; i < 3; ++i) f[i] = base ? base[i] : 0.f;
+    f[S_BERHU] = (float)(acc[0] / (double)n);
+    f[S_BCE] = (float)(acc[1] / (double)n);
+    f[S_NORM] = (float)(acc[2] / (double)n);
+    f[S_SSIM] = m > 0 ? (float)(1.0 - acc[3] / (double)m) : 0.f;
+    double tot = 0.0;
+    for (int i = 0; i < km.n; ++i) {
+      const float v = f[km.slot[i]];
+      out[i] = v;
+      tot += km.w[i] * (double)v;
+    }
+    out[km.n] = (float)tot;
+  }
+}
+
+// out[0] = mean SSIM over every map element of every plane
+__global__ void ssim_finalize_kernel(const float* __restrict__ ssum, int nbs, long long m, float* __restrict__ out) {
+  const double s = wave_fold(ssum, nbs, 1, 0);
+  if (threadIdx.x == 0) out[0] = (float)(s / (double)m);
+}
+
+bool dims_ok(int planes, int H, int W) {
+  return planes > 0 && H > 0 && W > 0 && planes <= 65535 && (long long)planes * H * W < (1ll << 40);
+}
+
+}  // namespace
+
+extern "C" size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W) {
+  if (terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W)) return 0;
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return 0;
+  return layout(terms, planes, H, W).bytes;
+}
+
+extern "C" int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int planes, int H, int W,
+                                       int n_keys, const int* key_slot, const double* key_weight,
+                                       const float* base_losses, float* out, void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
+      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
+    return fail(JSPSR_EINVAL, "loss_menu_forward: bad arguments");
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_forward: SSIM needs H, W >= 11");
+  KeyMap km{};
+  km.n = n_keys;
+  for (int i = 0; i < n_keys; ++i) {
+    const int s = key_slot[i];
+    const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < NSLOT && (terms & (1 << (s - S_BERHU))));
+    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_forward: key %d has slot %d outside the configured terms", i, s);
+    km.slot[i] = s;
+    km.w[i] = key_weight[i];
+  }
+  const Layout L = layout(terms, planes, H, W);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  const bool pw = terms & (T_BERHU | T_BCE | T_NORM);
+  if (terms & T_BERHU) {
+    hipLaunchKernelGGL(menu_max_kernel, dim3(L.nbm), dim3(PT), 0, st, pred, gt, n, reinterpret_cast<float*>(ws + L.pmax));
+    if (int e = check_launch("loss_menu_max")) return e;
+  }
+  if (pw) {
+    hipLaunchKernelGGL(menu_sum_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, n, terms,
+                       reinterpret_cast<const float*>(ws + L.pmax), L.nbm, reinterpret_cast<float*>(ws),
+                       reinterpret_cast<float*>(ws + L.psum));
+    if (int e = check_launch("loss_menu_sum")) return e;
+  }
+  if (terms & T_SSIM) {
+    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
+                       L.Hm, L.Wm, L.tiles_x, gaussian_window(), reinterpret_cast<float*>(ws + L.coef), L.cplane,
+                       reinterpret_cast<float*>(ws + L.ssum));
+    if (int e = check_launch("ssim_forward")) return e;
+  }
+  hipLaunchKernelGGL(menu_combine_kernel, dim3(1), dim3(256), 0, st, pw ? reinterpret_cast<const float*>(ws + L.psum) : nullptr,
+                     L.nb, (terms & T_SSIM) ? reinterpret_cast<const float*>(ws + L.ssum) : nullptr, L.nbs, n, L.cplane,
+                     base_losses, km, out);
+  return check_launch("loss_menu_combine");
+}
+
+extern "C" int jspsr_loss_menu_backward(const float* pred, const float* gt, int terms, int planes, int H, int W,
+                                        const double* slot_weight, const float* grad_total, float* grad_pred,
+                                        const void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W))
+    return fail(JSPSR_EINVAL, "loss_menu_backward: bad arguments");
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_backward: SSIM needs H, W >= 11");
+  const Layout L = layout(terms, planes, H, W);
+  const char* ws = static_cast<const char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  if (terms & (T_BERHU | T_BCE | T_NORM)) {
+    const double dn = (double)n;
+    hipLaunchKernelGGL(menu_bwd_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, n, terms,
+                       reinterpret_cast<const float*>(ws), grad_total, (float)(slot_weight[S_BERHU] / dn),
+                       (float)(slot_weight[S_BCE] / dn), (float)(slot_weight[S_NORM] / (1e-12 * dn)), grad_pred);
+    if (int e = check_launch("loss_menu_backward")) return e;
+  }
+  if (terms & T_SSIM) {
+    const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
+    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
+                       reinterpret_cast<const float*>(ws + L.coef), L.cplane, H, W, L.Hm, L.Wm, tx, gaussian_window(),
+                       grad_total, (float)(slot_weight[S_SSIM] / (double)L.cplane), grad_pred);
+    if (int e = check_launch("ssim_backward")) return e;
+  }
+  return JSPSR_OK;
+}
+
+extern "C" size_t jspsr_ssim_workspace_bytes(int planes, int H, int W, int same) {
+  if (!dims_ok(planes, H, W) || (!same && (H < 11 || W < 11))) return 0;
+  const int Hm = same ? H : H - 10, Wm = same ? W : W - 10;
+  return al16((size_t)((Wm + ST - 1) / ST) * ((Hm + ST - 1) / ST) * planes * 4);
+}
+
+extern "C" int jspsr_ssim_forward(const float* pred, const float* gt, int planes, int H, int W, int same,
+                                  const float* window11, float* out, void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !out || !workspace || !dims_ok(planes, H, W)) return fail(JSPSR_EINVAL, "ssim_forward: bad arguments");
+  if (!same && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "ssim_forward: valid mode needs H, W >= 11");
+  Win11 k = gaussian_window();
+  if (window11)
+    for (int i = 0; i < 11; ++i) k.w[i] = window11[i];
+  const int Hm = same ? H : H - 10, Wm = same ? W : W - 10;
+  const int tx = (Wm + ST - 1) / ST, ty = (Hm + ST - 1) / ST;
+  float* part = static_cast<float*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (same)
+    hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
+                       nullptr, 0ll, part);
+  else
+    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
+                       nullptr, 0ll, part);
+  if (int e = check_launch("ssim_forward")) return e;
+  hipLaunchKernelGGL(ssim_finalize_kernel, dim3(1), dim3(64), 0, st, part, tx * ty * planes, (long long)planes * Hm * Wm, out);
+  return check_launch("ssim_finalize");
+}

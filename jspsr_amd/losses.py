@@ -1,7 +1,14 @@
 """Training loss of the reference configs (configs/*.yml:67-70): L1 + L2 + 0.1 * Sobel-L1
 (losses/loss_schemes.py:55-72, losses/loss_functions.py:171-185) as one fused HIP forward and one
-fused HIP backward over the (B,1,H,W) prediction (jspsr_loss_forward / jspsr_loss_backward)."""
+fused HIP backward over the (B,1,H,W) prediction (jspsr_loss_forward / jspsr_loss_backward).
+
+The rest of the reference's loss menu -- every name `get_loss` accepts (loss_schemes.py:6-33) -- and the criterion
+`get_criterion` builds from a config's `loss:` dict (utils/common_config.py:209-233) run on the device too
+(jspsr_loss_menu_forward / _backward, csrc/loss_terms.hip): one fused forward and one fused backward for the whole dict.
+"""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -66,3 +73,180 @@ class MultiLoss(torch.nn.Module):
 
     def __str__(self):
         return f"{self.__class__.__name__}:: ['L1', 'L2', 'Grad'], {list(self.weights)}, fused HIP (jspsr_loss_forward/backward)"
+
+
+# ---- the loss menu -------------------------------------------------------------------------------------------------
+# get_loss's names and aliases (case-insensitive) -> term slot of jspsr_loss_menu_*: 0..2 are the three terms of
+# jspsr_loss_forward, 3..6 the terms of csrc/loss_terms.hip (bit 1 << (slot - 3) of its `terms` set)
+_SLOT = {"l1": 0, "l2": 1, "mse": 1, "edge": 2, "grad": 2, "berhu": 3, "vanilla": 4, "bce": 4, "norm": 5, "ssim": 6}
+_NSLOT = 7
+
+
+def _slot(name):
+    s = _SLOT.get(str(name).lower())
+    if s is None:
+        raise NotImplementedError(f"Undefined loss: {name}")
+    return s
+
+
+class _Spec:
+    """Host-side plan of one criterion: keys in config order, their slots and weights, the per-slot weight sums."""
+
+    def __init__(self, weights):
+        self.keys = list(weights)
+        self.slots = [_slot(k) for k in self.keys]
+        self.weights = [float(weights[k]) for k in self.keys]
+        self.slot_w = [0.0] * _NSLOT
+        for s, w in zip(self.slots, self.weights):
+            self.slot_w[s] += w
+        self.terms = sum(1 << (s - 3) for s in set(self.slots) if s >= 3)
+        self.base = any(s < 3 for s in self.slots)
+        self.base_w = tuple(self.slot_w[:3])
+        n = len(self.keys)
+        self.c_slots = (ctypes.c_int * n)(*self.slots)
+        self.c_weights = (ctypes.c_double * n)(*self.weights)
+        self.c_slot_w = (ctypes.c_double * _NSLOT)(*self.slot_w)
+
+    def check(self, pred, gt):
+        """Shape rules, raised before any launch."""
+        if not pred.is_cuda:
+            raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
+        if pred.shape != gt.shape or pred.dim() != 4:
+            raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
+        if 5 in self.slots and pred.shape[1] != 1:
+            raise ValueError(f"loss Norm: supported for one channel (the DEM head) only, got C = {pred.shape[1]}")
+        if 6 in self.slots and (pred.shape[2] < 11 or pred.shape[3] < 11):
+            raise ValueError(f"loss SSIM: needs H, W >= 11 (11x11 window, valid map), got {tuple(pred.shape[2:])}")
+
+
+class _MenuLoss(torch.autograd.Function):
+    """out = (term of every key in config order..., Total).  Only Total carries gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, spec):
+        pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
+        B, C, H, W = pred_c.shape
+        P = B * C
+        lib = _lib.load()
+        base, bws = None, None
+        if spec.base:
+            bws = torch.empty(lib.jspsr_loss_workspace_bytes(P, H, W), dtype=torch.uint8, device=pred.device)
+            base = torch.empty(4, dtype=torch.float32, device=pred.device)
+            _lib.check(lib.jspsr_loss_forward(pred_c.data_ptr(), gt_c.data_ptr(), *spec.base_w, base.data_ptr(),
+                                              bws.data_ptr(), P, H, W, _stream()), "jspsr_loss_forward")
+        ws = torch.empty(lib.jspsr_loss_menu_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
+        out = torch.empty(len(spec.keys) + 1, dtype=torch.float32, device=pred.device)
+        _lib.check(lib.jspsr_loss_menu_forward(pred_c.data_ptr(), gt_c.data_ptr(), spec.terms, P, H, W, len(spec.keys),
+                                               spec.c_slots, spec.c_weights, base.data_ptr() if base is not None else None,
+                                               out.data_ptr(), ws.data_ptr(), _stream()), "jspsr_loss_menu_forward")
+        ctx.save_for_backward(pred_c, gt_c, ws, bws)
+        ctx.spec = spec
+        ctx.mark_non_differentiable(gt)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, ws, bws = ctx.saved_tensors
+        spec = ctx.spec
+        B, C, H, W = pred.shape
+        P = B * C
+        n = len(spec.keys)
+        g = gout[n:n + 1].float().contiguous()
+        lib = _lib.load()
+        if spec.base:   # writes the gradient of the L1 / L2 / Grad part; the menu adds its own terms
+            gp = torch.empty_like(pred)
+            _lib.check(lib.jspsr_loss_backward(pred.data_ptr(), gt.data_ptr(), g.data_ptr(), *spec.base_w, gp.data_ptr(),
+                                               bws.data_ptr(), P, H, W, _stream()), "jspsr_loss_backward")
+        else:
+            gp = torch.zeros_like(pred)
+        _lib.check(lib.jspsr_loss_menu_backward(pred.data_ptr(), gt.data_ptr(), spec.terms, P, H, W, spec.c_slot_w,
+                                                g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
+                   "jspsr_loss_menu_backward")
+        return gp, None, None
+
+
+def _evaluate(spec, pred, gt):
+    """-> (components in config order, Total): one fused forward, one fused backward."""
+    spec.check(pred, gt)
+    n = len(spec.keys)
+    if spec.terms == 0:      # L1 / L2 / Grad (any aliases) only: exactly the fused pair MultiLoss runs
+        v = _FusedLoss.apply(pred, gt, *spec.base_w)
+        return [v[s].detach() for s in spec.slots], v[3]
+    v = _MenuLoss.apply(pred, gt, spec)
+    return [v[i].detach() for i in range(n)], v[n]
+
+
+class LossTerm(torch.nn.Module):
+    """One term of the menu on its own, like the module the reference's get_loss returns: (pred, gt) -> 0-d tensor."""
+
+    def __init__(self, name):
+        super().__init__()
+        self.name = str(name)
+        self.spec = _Spec({self.name: 1.0})
+
+    def forward(self, pred, gt):
+        return _evaluate(self.spec, pred, gt)[1]
+
+    def __str__(self):
+        return f"{self.__class__.__name__}({self.name}), fused HIP"
+
+
+def get_loss(name):
+    """The reference's get_loss (losses/loss_schemes.py:6-33) on the device: l1, l2 / mse, vanilla / bce, edge / grad,
+    berhu, norm, ssim, case-insensitively.
+
+    Semantics and where they depart from the reference:
+      * berhu: th = 0.6 * max|pred - gt| (double from the fp32 max, as `.item()` gives it), compared in fp32, th^2 and
+        2 th rounded to fp32; the gradient treats th as a constant.  It stays on the device (the reference's `.item()`
+        is a host sync).  At pred == gt everywhere (th = 0) the loss is 0 and the gradient is 0; the reference's
+        gradient there is NaN (its unselected torch.where branch divides by 0).
+      * norm: F.normalize over the channel of a ONE-channel map (the DEM head); ValueError for C != 1.  Its gradient is
+        0 where |pred| > 1e-12 (the reference's autograd leaves residues of about 2e-16 there) and -g^/(1e-12 N) below.
+      * bce: max(x, 0) - x y + log1p(exp(-|x|)), gradient (sigmoid(x) - y) / N.
+      * ssim: 1 - piq.ssim(clamp(pred, 0, 1), gt, data_range=1, reduction="mean", downsample=False) -- restated from
+        piq's public source, UNPINNED against piq itself (not installed here): valid 11x11 Gaussian window (sigma 1.5),
+        c1 = 0.01^2, c2 = 0.03^2, the mean of the map over every element of every plane.  piq's input-range assertion
+        (a host sync) is not reproduced.  ValueError for H or W < 11.
+    Unknown names raise NotImplementedError("Undefined loss: <name>")."""
+    _slot(name)
+    return LossTerm(name)
+
+
+class Criterion(torch.nn.Module):
+    """get_criterion's criterion on the device: the components (detached device scalars, keys in the config's spelling
+    and order) and "Total" (what carries gradient, train/train_utils.py:214-226).  One fused forward and one fused
+    backward for the whole dict; no host synchronisation, so GraphedStep can capture it."""
+
+    def __init__(self, weights, single=False):
+        super().__init__()
+        if not weights:
+            raise ValueError("get_criterion: empty loss config")
+        self.single = single
+        self.spec = _Spec(weights)
+        self.out = {}
+
+    def forward(self, pred, gt):
+        comps, total = _evaluate(self.spec, pred, gt)
+        self.out = dict(zip(self.spec.keys, comps))
+        self.out.pop("Total", None)
+        self.out["Total"] = total
+        return self.out
+
+    def reset(self):
+        self.out = {}
+
+    def __str__(self):
+        if self.single:
+            return f"SingleLoss:: {self.spec.keys[0]}:: fused HIP (jspsr_loss_menu_forward/backward)"
+        return f"MultiLoss:: {self.spec.keys}, {self.spec.weights}, fused HIP (jspsr_loss_menu_forward/backward)"
+
+
+def get_criterion(config):
+    """utils/common_config.py:209-233: one key -> that term alone with weight 1 (whatever the configured weight),
+    returning {name: v, "Total": v}; several keys -> the weighted sum, {keys in config order..., "Total"}.
+    The default {"L1": 1, "L2": 1, "Grad": 0.1} runs exactly MultiLoss(1, 1, 0.1)'s fused pair."""
+    config = dict(config)
+    if len(config) == 1:
+        (name, _), = config.items()
+        return Criterion({name: 1.0}, single=True)
+    return Criterion(config)

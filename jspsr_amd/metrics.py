@@ -7,10 +7,12 @@ size, clamp of the prediction to [0,1]); PSNR :229-235 (piq.psnr(data_range=1, r
 RMSE :361-384; median :444-455; NMAD :499-512 (1.4826 * median|dh - median dh|); LE95 :556-570
 (k-th smallest |dh| with k = 1 + round(0.95 (n-1))), and data/data_utils.py:441-457
 ``ToDEM.descale_data`` / :289-312 ``ToTensor.scale_data``.  The reference feeds batches of one tile.
+SSIM (MeterSSIM :275-335, opt-in): packages "piq" and "local" (``ssim``).
 """
 from __future__ import annotations
 
-from math import log
+import ctypes
+from math import exp, log
 
 import torch
 
@@ -96,31 +98,83 @@ def tile_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
     return out
 
 
+def local_window():
+    """The window of the reference's local ssim (evaluation/metrics.py:20-27) exactly as written there:
+    exp(-(x - 5) * 2 / (2 * 1.5 * 2)), normalised in fp32.  Asymmetric and exponential, not a Gaussian; kept as is."""
+    g = torch.tensor([exp(-(x - 5) * 2 / float(2 * 1.5 * 2)) for x in range(11)], dtype=torch.float32)
+    return g / g.sum()
+
+
+_LOCAL_WINDOW = None
+
+
+def ssim(pred, gt, package="piq"):
+    """Mean SSIM of prepared [0,1] tiles (B,C,H,W) on the GPU (jspsr_ssim_forward) -> 0-d device tensor.  pred is clamped
+    to [0,1] (a no-op after ``prepare``).
+      "piq":   piq.ssim(gt, pred, data_range=1, reduction="mean", downsample=False) (metrics.py:307-309): 11x11 Gaussian
+               window (sigma 1.5), valid map, c1 = 0.01^2, c2 = 0.03^2 -- restated from piq's public source, unpinned
+               against piq (not installed here); its input-range assertion (a host sync) is not reproduced.
+      "local": ssim(gt, pred) of metrics.py:20-63 (:319): the window of ``local_window``, zero padding 5, H x W map."""
+    global _LOCAL_WINDOW
+    if package not in ("piq", "local"):
+        raise NotImplementedError(f"ssim: package {package!r} (supported: 'piq', 'local')")
+    if not pred.is_cuda or pred.shape != gt.shape or pred.dim() != 4:
+        raise ValueError(f"ssim: expected equal (B,C,H,W) GPU tensors, got {tuple(pred.shape)} {tuple(gt.shape)}")
+    same = package == "local"
+    B, C, H, W = pred.shape
+    if not same and (H < 11 or W < 11):
+        raise ValueError(f"ssim (piq): needs H, W >= 11, got {(H, W)}")
+    win = None
+    if same:
+        if _LOCAL_WINDOW is None:
+            _LOCAL_WINDOW = (ctypes.c_float * 11)(*local_window().tolist())
+        win = _LOCAL_WINDOW
+    p, g = pred.float().contiguous(), gt.float().contiguous()
+    lib = _lib.load()
+    ws = torch.empty(lib.jspsr_ssim_workspace_bytes(B * C, H, W, int(same)), dtype=torch.uint8, device=pred.device)
+    out = torch.empty(1, dtype=torch.float32, device=pred.device)
+    _lib.check(lib.jspsr_ssim_forward(p.data_ptr(), g.data_ptr(), B * C, H, W, int(same), win, out.data_ptr(), ws.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream), "jspsr_ssim_forward")
+    return out[0]
+
+
 class Meter:
     """Running per-sample averages of all five scores (what PerformanceMeter.get_score reports,
     evaluation/evaluate_utils.py:26-47).  Accumulates on the device; one host sync in ``scores()``.
     GPU tiles of batch size 1 (how the reference evaluates) go through the fused HIP path (`tile_scores`); CPU tensors
-    and larger batches through the same formulas as torch operators."""
+    and larger batches through the same formulas as torch operators.
+    ssim = "piq" | "local" adds "SSIM" (get_meter's MeterSSIM, evaluate_utils.py:75): ``ssim`` after the same
+    ``prepare`` (border crop, clamp), on the GPU only.  With ssim = None (the default) the five scores are unchanged."""
 
     NAMES = ("PSNR", "RMSE", "Median", "NMAD", "LE95")
 
-    def __init__(self, value_min, value_max, border=0.05, elev_log=True):
+    def __init__(self, value_min, value_max, border=0.05, elev_log=True, ssim=None):
+        if ssim not in (None, "piq", "local"):
+            raise NotImplementedError(f"Meter: ssim package {ssim!r} (supported: None, 'piq', 'local')")
         self.vmin, self.vmax, self.border, self.elev_log = value_min, value_max, border, elev_log
+        self.ssim = ssim
+        self.names = self.NAMES + (("SSIM",) if ssim else ())
         self.sums, self.n = None, 0
+
+    def _with_ssim(self, vals, pred, gt):
+        if not self.ssim:
+            return vals
+        p, g = prepare(pred.float(), gt.float(), self.border)
+        return torch.cat((vals, ssim(p, g, self.ssim).view(1)))
 
     @torch.no_grad()
     def update(self, pred, gt):
         if pred.is_cuda and pred.dim() == 4 and pred.shape[0] == 1 and pred.shape[1] == 1:
-            vals = tile_scores(pred, gt, self.vmin, self.vmax, self.border, self.elev_log)
+            vals = self._with_ssim(tile_scores(pred, gt, self.vmin, self.vmax, self.border, self.elev_log), pred, gt)
             self.sums = vals if self.sums is None else self.sums + vals
             self.n += 1
             return
         p, g = prepare(pred.float(), gt.float(), self.border)
         dh = descale_data(p, self.vmin, self.vmax, self.elev_log) - descale_data(g, self.vmin, self.vmax, self.elev_log)
-        vals = torch.stack((psnr(p, g), rmse(dh), median(dh), nmad(dh), le95(dh)))
+        vals = self._with_ssim(torch.stack((psnr(p, g), rmse(dh), median(dh), nmad(dh), le95(dh))), pred, gt)
         self.sums = vals if self.sums is None else self.sums + vals
         self.n += 1
 
     def scores(self):
         v = (self.sums / max(self.n, 1)).tolist()
-        return dict(zip(self.NAMES, v))
+        return dict(zip(self.names, v))
