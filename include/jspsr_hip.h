@@ -149,6 +149,32 @@ int jspsr_mirror_pad_f32(const float* x, float* out, int C, int H, int W, int n,
 int jspsr_elev_scale_f32(const float* in, float* out, long long n, int descale, int elev_log, double elev_min, double elev_max,
                          double base_elev, jspsr_stream_t stream);
 
+/* ---- K9: the training batch on device, from a device-resident scene store ------------------------
+ * jspsr_batch_make: every raster of a batch in one launch -- RandomCrop / TileCrop's window, RandomFlipRotate90's D4 map
+ *   (data/data_utils.py:9-168) and ToTensor's per-kind arithmetic (data_utils.py:217-312) -- written as the fp32 NCHW
+ *   tensors collate_fn stacks (data/dfc30.py:346-364), or as channel slices of one concatenated tensor (EDSR's input,
+ *   utils/utils.py:248-315).  Kinds, indexed 0..5: lr_dem, hr_dem (fp32, 1 channel), image, mask (uint8, 1..16 channels),
+ *   canopy (uint8, 1 channel), coord (2 channels, computed: row / (H - 1), col / (W - 1) over the whole scene).
+ *   src[6], src_bytes[6], out[6], channels[6], coff[6], cpitch[6] are HOST arrays: kind i's scene store (HWC, all scenes
+ *   back to back, 4-byte aligned; NULL for coord) and its size in bytes, its output (NULL: kind absent; 4-byte aligned) of
+ *   (B, cpitch, k, k) whose channels coff .. coff + channels - 1 this kind writes.
+ *   scenes  device int64 [n_scenes][3] = {pixel offset into every store, H, W}.
+ *   samples device int32 [B][8] = {scene, y0, x0, code, base elevation (fp32 bit pattern), 0, 0, 0}: the crop is rows
+ *     y0 .. y0 + k - 1, columns x0 .. x0 + k - 1; code = rot90 angle * 4 + flip_lr * 2 + flip_ud.  A row that leaves its
+ *     scene or the store writes NaN.
+ *   flags JSPSR_BATCH_*; elev_min / elev_max the DEM range (the Python numbers of tensor_kwargs); mask_div =
+ *   len(mask_channel) + 1.  Image, mask, canopy and coord values are the reference's bits; DEM values within 1 ulp of
+ *   numpy's fp32 log.  No host synchronisation. */
+#define JSPSR_BATCH_LOG 1          /* tensor_kwargs log: log min-max scaling of the DEMs */
+#define JSPSR_BATCH_SCALE_MASK 2   /* tensor_kwargs scale_mask: mask channel i times (i + 1) / mask_div */
+#define JSPSR_BATCH_IMAGE_11 4     /* image_range "[-1, 1]" (image and lr_dem) */
+#define JSPSR_BATCH_LABEL_11 8     /* label_range "[-1, 1]" (hr_dem) */
+#define JSPSR_BATCH_IMAGE_255 16   /* image_range "[0, 255]" (image: a second division by 255) */
+#define JSPSR_BATCH_FLAGS 31
+int jspsr_batch_make(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
+                     const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples, int B,
+                     int k, int flags, double elev_min, double elev_max, int mask_div, jspsr_stream_t stream);
+
 /* ---- K1 in the models (round 4): logits + offsets as PLANES of one tensor ---------------------------------------
  * The same operator as jspsr_prop_forward_f32 / jspsr_prop_backward_f32 -- same kernels, same 108 / 208 algorithmic bytes
  * per pixel -- with what the reference does between the generator's heads and deform_conv2d folded in: the Sigmoid of

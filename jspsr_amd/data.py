@@ -1,0 +1,370 @@
+"""Training and validation batches made on the device (K9, csrc/batch.hip).
+
+The reference's loader decodes a scene's files, then runs `RandomCrop` -> `RandomFlipRotate90` -> `ToTensor` on the CPU for
+every sample and stacks the samples in `DFC30.collate_fn` (data/dfc30.py:193-246,346-364; data/data_utils.py:9-312).
+Here decoding stays on the host; everything after it runs on the GPU:
+
+    scenes = DeviceScenes(lr_dem=[...], hr_dem=[...], image=[...], mask=[...], relative=True,
+                          elev_min=-80, elev_max=933, elev_log=True, scale_mask=True)
+    for batch in RandomCropBatches(scenes, 50, 128, generator=g):
+        inputs, gt, base, meta = batch_pair(batch, "JSPSR", input_data)
+        loss = criterion(model(*inputs), gt)
+
+`DeviceScenes` uploads the decoded HWC rasters once (the configs' `preload: True`).  `RandomCropBatches` makes the crop and
+D4 draws on the host from numpy's random stream, in the reference's order.  Each batch is then ONE launch of
+`jspsr_batch_make`, which writes every raster of the batch.  Nothing syncs with the host per step.
+"""
+from __future__ import annotations
+
+import math
+from typing import Iterable, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .tiles import get_tile
+
+KINDS = ("lr_dem", "hr_dem", "image", "mask", "canopy", "coord")   # the C ABI's kind indices 0..5
+CONCAT_ORDER = ("lr_dem", "image", "mask", "canopy", "coord")      # EDSR's input, utils/utils.py:248-315
+_DTYPE = {"lr_dem": np.float32, "hr_dem": np.float32, "image": np.uint8, "mask": np.uint8, "canopy": np.uint8}
+LOG, SCALE_MASK, IMAGE_11, LABEL_11, IMAGE_255 = 1, 2, 4, 8, 16   # JSPSR_BATCH_* (include/jspsr_hip.h)
+ROW = 8                                                            # int32 words per sample-table row
+
+
+def d4_code(angle: int, flip_lr: bool, flip_ud: bool) -> int:
+    """The kernel's code of np.rot90(., angle), then fliplr, then flipud (data_utils.py:12-30)."""
+    return int(angle) * 4 + 2 * bool(flip_lr) + bool(flip_ud)
+
+
+def _as_hwc(a, kind: str, i: int) -> np.ndarray:
+    a = a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim != 3 or a.dtype != _DTYPE[kind]:
+        raise ValueError(f"{kind}[{i}]: expected an HWC {np.dtype(_DTYPE[kind]).name} array, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+class DeviceScenes:
+    """Decoded scenes, uploaded once, in the layout `DFC30.__getitem__` holds them: lr_dem / hr_dem fp32 (H,W,1), image
+    uint8 (H,W,3), mask uint8 (H,W,C) (the `mask_channel` selection already applied), canopy uint8 (H,W,1); lists of numpy
+    arrays or CPU tensors, one entry per scene.  Scenes may differ in size; every kind of a scene has the same H and W.
+
+    Each scene's base elevation is `np.min(lr_dem)` when `relative` (dfc30.py:200), else 0.  The reference asserts its
+    ranges per crop (data_utils.py:253-279, 297-299).  Here they are checked once per WHOLE scene at preload: the log domain
+    `min - base - elev_min >= 1` and every scaled value in [0, 1].  The scaling is monotone, so a scene that passes cannot
+    give a crop that fails.  This is stricter than the reference: a scene whose only bad pixels no crop ever covers is
+    refused here.  `elev_min` / `elev_max` are the config's Python numbers (tensor_kwargs min / max).
+    """
+
+    def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
+                 relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
+                 mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
+                 normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda"):
+        if coord not in (None, "local"):
+            if str(coord).lower() == "global":
+                raise NotImplementedError("coord='global' needs the scenes' georeferencing; only 'local' is built")
+            raise ValueError(f"coord must be None, 'local' or 'global', got {coord!r}")
+        if normalize:
+            raise NotImplementedError("Normalize is not built (the reference advises against it, data_utils.py:315)")
+        for name, r in (("image_range", image_range), ("label_range", label_range)):
+            if r not in (None, "[0, 1]", "[-1, 1]", "[0, 255]"):
+                raise ValueError(f"{name} {r!r}")
+        if not elev_max > elev_min:
+            raise ValueError(f"elev_max {elev_max} <= elev_min {elev_min}")
+        self.device = torch.device(device)
+        self.relative, self.elev_min, self.elev_max, self.elev_log = relative, elev_min, elev_max, elev_log
+        self.scale_mask, self.image_range, self.label_range = scale_mask, image_range, label_range
+        self.mask_channel = list(mask_channel) if mask_channel else [*range(15)]      # ToTensor's default (data_utils.py:215)
+        raw = {"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}
+        n = len(lr_dem)
+        if n == 0:
+            raise ValueError("no scenes")
+        host = {}
+        for kind, lst in raw.items():
+            if lst is None:
+                continue
+            if len(lst) != n:
+                raise ValueError(f"{kind}: {len(lst)} scenes, lr_dem has {n}")
+            host[kind] = [_as_hwc(a, kind, i) for i, a in enumerate(lst)]
+        self.kinds = [k for k in KINDS if k in host] + (["coord"] if coord else [])
+        self.channels = {k: host[k][0].shape[2] for k in host}
+        if coord:
+            self.channels["coord"] = 2
+        for kind in ("lr_dem", "hr_dem", "canopy"):
+            if kind in host and self.channels[kind] != 1:
+                raise ValueError(f"{kind} has {self.channels[kind]} channels, not 1")
+        for kind, arrs in host.items():
+            for i, a in enumerate(arrs):
+                if a.shape[2] != self.channels[kind] or a.shape[:2] != host["lr_dem"][i].shape[:2]:
+                    raise ValueError(f"{kind}[{i}] {a.shape} does not match lr_dem {host['lr_dem'][i].shape} / "
+                                     f"{self.channels[kind]} channels")
+            if self.channels[kind] > 16:
+                raise ValueError(f"{kind}: {self.channels[kind]} channels, the kernel takes at most 16")
+        self.shapes = [a.shape[:2] for a in host["lr_dem"]]
+        if coord and any(h < 2 or w < 2 for h, w in self.shapes):
+            raise ValueError("local coordinates need scenes of at least 2 x 2 pixels")
+        self.ids = [str(i) for i in range(n)] if ids is None else [str(i) for i in ids]
+        self.base = [np.min(a) if relative else 0 for a in host["lr_dem"]]
+        for i in range(n):
+            self._check_scene(i, {k: v[i] for k, v in host.items()})
+        offs = np.zeros(n + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([h * w for h, w in self.shapes])
+        self.scene_table = torch.tensor([[int(offs[i]), h, w] for i, (h, w) in enumerate(self.shapes)], dtype=torch.int64,
+                                        device=self.device)
+        # one flat buffer per kind; the store is never modified
+        self.store = {k: torch.from_numpy(np.concatenate([a.reshape(-1) for a in v])).to(self.device) for k, v in host.items()}
+        self.flags = ((LOG if elev_log else 0) | (SCALE_MASK if scale_mask else 0) | (IMAGE_11 if image_range == "[-1, 1]" else 0)
+                      | (LABEL_11 if label_range == "[-1, 1]" else 0) | (IMAGE_255 if image_range == "[0, 255]" else 0))
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def scale_dem(self, a: np.ndarray, base) -> np.ndarray:
+        """ToTensor.scale_data in numpy, as the reference runs it (data_utils.py:289-312)."""
+        data = a.astype(np.float32)
+        if base != 0:
+            data = data - base
+        if self.elev_log:
+            assert np.min(data) - self.elev_min >= 1, \
+                f"elev_min must smaller than (data - 1) for [0, 1] range: {np.min(data)} {self.elev_min}"
+            return np.log(data - self.elev_min) / np.log(self.elev_max - self.elev_min) + 1e-8
+        return (data - self.elev_min) / (self.elev_max - self.elev_min)
+
+    def _check_scene(self, i: int, s: dict):
+        """The reference's per-crop range asserts, once over the whole scene (see the class docstring)."""
+        for kind in ("lr_dem", "hr_dem"):
+            v = self.scale_dem(s[kind], self.base[i])
+            if not (v.min() >= 0 and v.max() <= 1):
+                raise AssertionError(f"scene {self.ids[i]} {kind}: scaled to [{v.min()}, {v.max()}], not within [0, 1]")
+        if "mask" in s:
+            m = s["mask"].astype(np.float32)
+            if self.scale_mask:
+                m = m * (np.arange(m.shape[2], dtype=np.float32) + 1) / np.float32(len(self.mask_channel) + 1)
+            if not (m.min() >= 0 and m.max() <= 1):
+                raise AssertionError(f"scene {self.ids[i]} mask: values within [{m.min()}, {m.max()}], not [0, 1]")
+        if "canopy" in s and s["canopy"].max() > 68:
+            raise AssertionError(f"scene {self.ids[i]} canopy: {s['canopy'].max()} > 68")
+
+    def make(self, table: torch.Tensor, k: int, outs: dict):
+        """One launch: table (B, 8) int32 sample rows on the device; outs kind -> (tensor (B, cpitch, k, k), coff)."""
+        lib = _lib.load()
+        P = ctypes_arrays(self, outs)
+        B = table.shape[0]
+        _lib.check(lib.jspsr_batch_make(P[0], P[1], P[2], P[3], P[4], P[5], self.scene_table.data_ptr(), len(self), table.data_ptr(),
+                                        B, k, self.flags, float(self.elev_min), float(self.elev_max),
+                                        len(self.mask_channel) + 1, torch.cuda.current_stream(self.device).cuda_stream),
+                   "jspsr_batch_make")
+
+
+def ctypes_arrays(scenes: DeviceScenes, outs: dict):
+    """The six-entry host arrays of jspsr_batch_make (include/jspsr_hip.h)."""
+    import ctypes
+    src = (ctypes.c_void_p * 6)()
+    nbytes = (ctypes.c_longlong * 6)()
+    out = (ctypes.c_void_p * 6)()
+    ch, coff, pitch = (ctypes.c_int * 6)(), (ctypes.c_int * 6)(), (ctypes.c_int * 6)()
+    for i, kind in enumerate(KINDS):
+        if kind not in outs:
+            continue
+        t, c0 = outs[kind]
+        if kind in scenes.store:
+            st = scenes.store[kind]
+            src[i], nbytes[i] = st.data_ptr(), st.numel() * st.element_size()
+        out[i] = t.data_ptr()
+        ch[i], coff[i], pitch[i] = scenes.channels[kind], c0, t.shape[1]
+    return src, nbytes, out, ch, coff, pitch
+
+
+class ShuffleOrder:
+    """The index order of `DataLoader(dataset, shuffle=True, generator=g, num_workers=0)`: each epoch the loader's iterator
+    first draws its base seed from `g` (or torch's global generator), then RandomSampler draws the permutation."""
+
+    def __init__(self, n: int, generator: torch.Generator | None = None):
+        self.n, self.generator = n, generator
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        torch.empty((), dtype=torch.int64).random_(generator=self.generator)
+        return iter(torch.utils.data.RandomSampler(range(self.n), generator=self.generator))
+
+
+class _Batches:
+    """Shared part of the two batch iterables: output allocation, the launch and the yielded dict."""
+
+    def __init__(self, scenes: DeviceScenes, batch_size: int, patch_size: int, concat: bool):
+        if batch_size <= 0 or patch_size <= 0:
+            raise ValueError("batch_size and patch_size must be positive")
+        self.scenes, self.batch_size, self.k, self.concat = scenes, batch_size, patch_size, concat
+
+    def _upload(self, rows: np.ndarray) -> torch.Tensor:
+        """One stream-ordered copy of a whole table from a pinned buffer that is never written again (a new one per call:
+        the caching host allocator keeps a freed block until the copies from it are done)."""
+        host = torch.empty(rows.shape, dtype=torch.int32, pin_memory=True)
+        host.numpy()[...] = rows
+        return host.to(self.scenes.device, non_blocking=True)
+
+    def _launch(self, table: torch.Tensor, side: int, meta: list) -> dict:
+        S, B = self.scenes, table.shape[0]
+        kw = dict(dtype=torch.float32, device=S.device)
+        batch, outs = {}, {}
+        if self.concat:
+            C = sum(S.channels[k] for k in CONCAT_ORDER if k in S.channels)
+            images = torch.empty((B, C, side, side), **kw)
+            c0 = 0
+            for kind in CONCAT_ORDER:
+                if kind in S.channels:
+                    outs[kind] = (images, c0)
+                    batch[kind] = images[:, c0:c0 + S.channels[kind]]
+                    c0 += S.channels[kind]
+            outs["hr_dem"] = (torch.empty((B, 1, side, side), **kw), 0)
+            batch["hr_dem"] = outs["hr_dem"][0]
+            batch["images"] = images
+        else:
+            for kind in S.kinds:
+                outs[kind] = (torch.empty((B, S.channels[kind], side, side), **kw), 0)
+                batch[kind] = outs[kind][0]
+        S.make(table, side, outs)
+        batch["base"] = table[:, 4].view(torch.float32)      # (B,) fp32 view of the rows' base elevations, on the device
+        batch["meta"] = meta
+        return batch
+
+    def _meta(self, s: int, bbox, aug) -> dict:
+        S = self.scenes
+        return {"id": S.ids[s], "base": S.base[s], "bbox": bbox,
+                "augmentation": {"rot90": aug[0], "flip_lr": aug[1], "flip_ud": aug[2]}}
+
+    def _side(self, s: int) -> int:
+        h, w = self.scenes.shapes[s]
+        if self.k > h or self.k > w or self.k == h == w:          # no crop (data_utils.py:53-54, 108-109)
+            if h != w:
+                raise ValueError(f"scene {self.scenes.ids[s]} ({h} x {w}) is not cropped and not square: it cannot be stacked")
+            return h
+        return self.k
+
+    def _run(self, table: torch.Tensor, sides: list, metas: list):
+        B = self.batch_size
+        for lo in range(0, len(sides), B):
+            hi = min(lo + B, len(sides))
+            side = set(sides[lo:hi])
+            if len(side) != 1:
+                raise ValueError(f"samples of sides {sorted(side)} in one batch cannot be stacked")
+            yield self._launch(table[lo:hi], side.pop(), metas[lo:hi])
+
+
+class RandomCropBatches(_Batches):
+    """The training batches: `DataLoader(DFC30(transform=RandomCrop -> RandomFlipRotate90 -> ToTensor), batch_size,
+    shuffle=True, drop_last=True, collate_fn=DFC30.collate_fn)` with the samples made on the device.
+
+    sampler: any iterable of scene indices (a DistributedSampler works); default `ShuffleOrder(len(scenes), generator)`.
+    rng: the numpy RandomState the draws come from; default numpy's global one, as the reference draws.  Per sample, in the
+    reference's order: randint(0, h-k-1) for the row, randint(0, w-k-1) for the column (h, w of the scene; no draw when the
+    crop is skipped), then with `augment` random_sample() < 0.5 and, if so, choice([1,2,3]), choice([True, False]) for
+    flip_lr and for flip_ud.  All draws of an epoch are made when its iteration starts (the reference makes them as each
+    batch is fetched: the stream is the same unless the caller draws from the same RandomState in between).
+    Each yielded dict holds the present rasters as (B, C, k, k) fp32 device tensors, `base` (B,) on the device and `meta`
+    as collate_fn gives it.  concat=True writes [lr_dem | image | mask | canopy | coord] into one tensor `images` (EDSR's
+    input) and gives the kinds as its channel slices.
+    """
+
+    def __init__(self, scenes: DeviceScenes, batch_size: int, patch_size: int, augment: bool = True, rng=None,
+                 sampler: Iterable[int] | None = None, drop_last: bool = True, generator: torch.Generator | None = None,
+                 concat: bool = False):
+        super().__init__(scenes, batch_size, patch_size, concat)
+        self.augment, self.rng, self.drop_last = augment, rng, drop_last
+        self.sampler = ShuffleOrder(len(scenes), generator) if sampler is None else sampler
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
+
+    def draw(self, indices: Sequence[int]):
+        """Host draws for these samples: (rows (n, 8) int32, sides, metas)."""
+        r = self.rng if self.rng is not None else np.random.mtrand._rand
+        rows = np.zeros((len(indices), ROW), dtype=np.int32)
+        sides, metas = [], []
+        k = self.k
+        for j, s in enumerate(indices):
+            s = int(s)
+            h, w = self.scenes.shapes[s]
+            side = self._side(s)
+            if side == k and not (k == h == w):
+                y0, x0 = int(r.randint(0, h - k - 1)), int(r.randint(0, w - k - 1))
+                bbox = (y0, x0, y0 + k, x0 + k)
+            else:
+                y0 = x0 = 0
+                bbox = (0, 0, h, w)
+            aug = (0, False, False)
+            if self.augment and r.random_sample() < 0.5:
+                aug = (int(r.choice([1, 2, 3])), bool(r.choice([True, False])), bool(r.choice([True, False])))
+            rows[j, :4] = (s, y0, x0, d4_code(*aug))
+            rows[j, 4] = np.float32(self.scenes.base[s]).view(np.int32)
+            sides.append(side)
+            metas.append(self._meta(s, bbox, aug))
+        return rows, sides, metas
+
+    def __iter__(self):
+        idx = [int(i) for i in self.sampler]
+        if self.drop_last:
+            idx = idx[:len(idx) // self.batch_size * self.batch_size]
+        if not idx:
+            return
+        rows, sides, metas = self.draw(idx)
+        yield from self._run(self._upload(rows), sides, metas)
+
+
+class TileCropBatches(_Batches):
+    """The validation batches (crop_mode: tile): sample i is tile i % n of scene i // n, row-major over the cover
+    `tiles.get_tile(W, k, n)` (TileCrop, data_utils.py:87-168), no augmentation, in order, the last batch kept.  meta's
+    bbox is TileCrop's (x0, y0, x0 + k, y0 + k)."""
+
+    def __init__(self, scenes: DeviceScenes, batch_size: int, patch_size: int, patches_per_image: int, concat: bool = False):
+        super().__init__(scenes, batch_size, patch_size, concat)
+        self.n = patches_per_image
+        rows, self.sides, self.metas = [], [], []
+        for s in range(len(scenes)):
+            h, w = scenes.shapes[s]
+            side = self._side(s)
+            cover = [(0, 0)] * self.n
+            if side == self.k and not (self.k == h == w):
+                stride, n = get_tile(w, self.k, self.n)
+                if n != self.n:
+                    raise ValueError(f"scene {scenes.ids[s]}: a {n}-tile cover, not {self.n}")
+                n_x = math.isqrt(n)
+                cover = [(stride * (t // n_x), stride * (t % n_x)) for t in range(n)]
+            for y0, x0 in cover:
+                bbox = (x0, y0, x0 + self.k, y0 + self.k) if side == self.k and not (self.k == h == w) else (0, 0, h, w)
+                rows.append([s, y0, x0, 0, np.float32(scenes.base[s]).view(np.int32), 0, 0, 0])
+                self.sides.append(side)
+                self.metas.append(self._meta(s, bbox, (0, False, False)))
+        self.rows = np.array(rows, dtype=np.int32).reshape(-1, ROW)
+        self._table = None
+
+    def __len__(self):
+        return math.ceil(len(self.sides) / self.batch_size)
+
+    def __iter__(self):
+        if self._table is None:
+            self._table = self._upload(self.rows)
+        yield from self._run(self._table, self.sides, self.metas)
+
+
+def batch_pair(batch: dict, model_name: str, input_data: dict):
+    """(inputs, hr_dem, base_elev, meta) as get_batch_pair returns them (utils/utils.py:152-315), from a device batch.
+    JSPSR / LRRU: inputs = [lr_dem, image, mask, canopy, coord], the kinds input_data names.  Any other model (EDSR): inputs
+    = [images], the concatenated tensor the kernel wrote (a batch made with concat=True)."""
+    name = (model_name or "").lower()
+    if name in {"jspsr", "lrru"}:
+        inputs = [batch["lr_dem"]] + [batch[k] for k in ("image", "mask", "canopy", "coord") if k in input_data]
+    elif name == "completionformer":
+        raise NotImplementedError("the completionformer split input is not built")
+    else:
+        if "images" not in batch:
+            raise ValueError(f"{model_name} takes one concatenated input: make the batches with concat=True")
+        want = [k for k in CONCAT_ORDER[1:] if k in input_data]
+        have = [k for k in CONCAT_ORDER[1:] if k in batch]
+        if want != have:
+            raise ValueError(f"input_data asks for {want}, the batch holds {have}")
+        inputs = [batch["images"]]
+    return inputs, batch["hr_dem"], batch["base"], batch["meta"]
