@@ -455,6 +455,27 @@ size_t jspsr_metrics_workspace_bytes(int H, int W);
 int jspsr_metrics_forward(const float* pred, const float* gt, int H, int W, float border, float value_min,
                           float value_max, int elev_log, float* scores, void* workspace, jspsr_stream_t stream);
 
+/* K10 (ABI v19): the evaluation scores of a whole batch of tiles in one call -- what PerformanceMeter.update does one
+ * tile at a time with one meter object and one host round trip per score (evaluation/evaluate_utils.py:26-47, get_meter
+ * :50-118; evaluation/metrics.py: MeterBase._prepare :147-199, psnr :97-113, Sobel :116-139, MeterPSNR :229-250,
+ * MeterRMSE :372-384, MeterMedian :453, MeterNMAD :508-510, MeterLE95 :565-568, MeterSlope :648-673).
+ * pred, gt: fp32 [B][H][W] in the network's range.  Crop, clamp and de-scaling as jspsr_metrics_forward (the same
+ * expressions: the elevation differences dh have the same bits).  scores (device, [B][8]), per tile:
+ *   0 PSNR "piq"   -10 log10(mse + 1e-8) on the [0,1] tensors      1 PSNR "local"  20 log10(1 / sqrt(mse)), 100 at mse == 0
+ *   2 RMSE   3 median   4 NMAD   5 LE95 of dh (the three order statistics exact, as jspsr_metrics_forward)
+ *   6 slope "local":  sqrt(mean((|S P| - |S G|)^2)) over the (h-2)(w-2) valid outputs of the unnormalised 3x3 Sobel pair
+ *   7 slope "kornia": sqrt(mean((grad P - grad G)^2)) over 2 h w values of spatial_gradient (replicate pad, Sobel / 8);
+ *                     restated from kornia's public source, not pinned against kornia itself
+ * A cropped tile of at most 20 272 pixels (142 x 142; 128 x 128 at border 0) is scored by ONE launch, one workgroup per
+ * tile with both de-scaled rasters in LDS; larger tiles stream through 27 launches whatever B is.  Sums fold in double in
+ * an order fixed by (h, w): row b does not depend on B or on the other tiles.  No host synchronisation.
+ * JSPSR_EINVAL: B <= 0, border outside [0, 0.5), value_max - value_min <= 1, nothing or fewer than 3 rows / columns
+ * left after the crop.  workspace: jspsr_scores_batch_workspace_bytes(B, H, W) bytes (0 = bad arguments), 16-byte
+ * aligned (JSPSR_EALIGN). */
+size_t jspsr_scores_batch_workspace_bytes(int B, int H, int W);
+int jspsr_scores_batch_forward(const float* pred, const float* gt, int B, int H, int W, float border, float value_min,
+                               float value_max, int elev_log, float* scores, void* workspace, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -8,6 +8,9 @@ RMSE :361-384; median :444-455; NMAD :499-512 (1.4826 * median|dh - median dh|);
 (k-th smallest |dh| with k = 1 + round(0.95 (n-1))), and data/data_utils.py:441-457
 ``ToDEM.descale_data`` / :289-312 ``ToTensor.scale_data``.  The reference feeds batches of one tile.
 SSIM (MeterSSIM :275-335, opt-in): packages "piq" and "local" (``ssim``).
+``batch_scores`` gives the scores of a whole batch of tiles in one launch, with the local PSNR (:97-113) and the slope
+score (MeterSlope :595-688, "local" and "kornia") beside the five above; ``jspsr_amd.evaluate`` builds the validation
+pass on it.
 """
 from __future__ import annotations
 
@@ -95,6 +98,33 @@ def tile_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
     _lib.check(lib.jspsr_metrics_forward(p.data_ptr(), g.data_ptr(), H, W, float(border), float(value_min), float(value_max),
                                          int(bool(elev_log)), out.data_ptr(), ws.data_ptr(),
                                          torch.cuda.current_stream().cuda_stream), "jspsr_metrics_forward")
+    return out
+
+
+SCORE_COLUMNS = ("PSNR_piq", "PSNR_local", "RMSE", "Median", "NMAD", "LE95", "Slope_local", "Slope_kornia")
+
+
+def batch_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
+    """All scores of a whole batch (B,1,H,W) of GPU tiles in one C-ABI call (K10, jspsr_scores_batch_forward) -> (B, 8)
+    fp32 device tensor, columns ``SCORE_COLUMNS``: PSNR as piq.psnr and as the reference's local psnr (metrics.py:97-113),
+    RMSE / median / NMAD / LE95 exactly as ``tile_scores`` gives them (the same elevation differences, exact selections),
+    and the slope score (MeterSlope, metrics.py:595-688) in its "local" form -- RMS difference of the magnitudes of the
+    unnormalised valid 3x3 Sobel pair (metrics.py:116-139) -- and its "kornia" form -- RMS of
+    spatial_gradient(P) - spatial_gradient(G) (replicate pad, Sobel / 8).  The kornia form is restated from kornia's public
+    source and is NOT pinned against kornia itself (not installed here); the richdem form is not built.
+    One launch per call for tiles of up to 142 x 142 after the crop (one workgroup per tile, both de-scaled rasters in LDS),
+    27 launches whatever B is for larger ones.  Row b does not depend on B or on the other tiles.  No host
+    synchronisation."""
+    if not pred.is_cuda or pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 1:
+        raise ValueError(f"batch_scores: equal (B,1,H,W) GPU tensors, got {tuple(pred.shape)} {tuple(gt.shape)}")
+    B, _, H, W = pred.shape
+    p, g = pred.float().contiguous(), gt.float().contiguous()
+    lib = _lib.load()
+    ws = torch.empty(max(lib.jspsr_scores_batch_workspace_bytes(B, H, W), 16), dtype=torch.uint8, device=pred.device)
+    out = torch.empty((B, len(SCORE_COLUMNS)), dtype=torch.float32, device=pred.device)
+    _lib.check(lib.jspsr_scores_batch_forward(p.data_ptr(), g.data_ptr(), B, H, W, float(border), float(value_min), float(value_max),
+                                              int(bool(elev_log)), out.data_ptr(), ws.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "jspsr_scores_batch_forward")
     return out
 
 
