@@ -487,6 +487,42 @@ int jspsr_adamw_step(float* param, const float* grad, float* exp_avg, float* exp
 int jspsr_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                          const float* hyper, jspsr_stream_t stream);
 
+/* K11 (ABI v20): the rest of the reference's optimizer menu over the same flat buffers (utils/common_config.py:241-291 builds
+ * torch.optim.SGD / Adam / AdamW / RMSprop; their per-tensor step loops are what this replaces), torch's semantics at its
+ * defaults, with the gradient range of the training monitor (train/train_utils.py:127-143, get_gradient_range) fused in.
+ *   kind            state1              state2                   a         b
+ *   JSPSR_OPT_SGD      momentum_buffer | NULL  NULL                     momentum  -       dampening 0, no Nesterov, coupled decay;
+ *                                                                                      step == 1: the buffer becomes the gradient
+ *   JSPSR_OPT_ADAM     exp_avg             exp_avg_sq               beta1     beta2   coupled L2 (g += wd * p before the moments)
+ *   JSPSR_OPT_ADAMW    exp_avg             exp_avg_sq               beta1     beta2   jspsr_adamw_step's arithmetic, bit for bit
+ *   JSPSR_OPT_RMSPROP  square_avg          momentum_buffer | NULL   momentum  alpha   eps outside the root, not centered, coupled
+ * A NULL momentum buffer selects the update without momentum.  Pointers as for jspsr_adamw_step.  `step` >= 1 feeds Adam's
+ * bias corrections (computed here in double) and SGD's first step.
+ * hyper != NULL: the scalars come from DEVICE memory instead (launches captured in a hipGraph), hyper[7] = { lr, a, b, eps,
+ * weight_decay, c1, c2 } with c1 = 1 - beta1^step, c2 = sqrt(1 - beta2^step) for Adam / AdamW (jspsr_adamw_step_dev's row)
+ * and c1 = 1 on SGD's first step, else 0; lr .. step are then ignored.  Same arithmetic, same bits as the argument form.
+ * grad_range != NULL (4 floats: min, max, count of non-finite elements, spare): the kernel also reduces the gradient it
+ * has just read -- a wave reduction, per-workgroup partials in `workspace` (jspsr_optim_workspace_bytes(), 4-byte aligned),
+ * one small last reduction -- and FOLDS the result into grad_range: min / max over the finite values, the count added.
+ * Several ranges of one step combine in the same 4 floats; the caller resets them once per step (the reference starts
+ * from 999 / -999).  The parameters do not depend on whether grad_range is given. */
+#define JSPSR_OPT_SGD 0
+#define JSPSR_OPT_ADAM 1
+#define JSPSR_OPT_ADAMW 2
+#define JSPSR_OPT_RMSPROP 3
+size_t jspsr_optim_workspace_bytes(void);
+int jspsr_optim_step(int kind, float* param, const float* grad, float* state1, float* state2, long long n, float lr, float a,
+                     float b, float eps, float weight_decay, int step, const float* hyper, float* grad_range, void* workspace,
+                     jspsr_stream_t stream);
+/* min / max of up to 8 device tensors (JSPSR_F32 or JSPSR_BF16, contiguous, numel[k] elements) in one call: what
+ * get_tensor_range (train/train_utils.py:84-96: torch.min + torch.max per tensor, read back with .item()) gives for
+ * `monitor_value: input / pred`.  tensors / numel / dtypes are HOST arrays of `count` entries; table[k][4] on the device
+ * receives { min, max, count of non-finite elements, 0 } of tensor k, min / max over its finite values.  workspace:
+ * jspsr_tensor_ranges_workspace_bytes(), 4-byte aligned. */
+size_t jspsr_tensor_ranges_workspace_bytes(void);
+int jspsr_tensor_ranges(int count, const void* const* tensors, const long long* numel, const int* dtypes, float* table,
+                        void* workspace, jspsr_stream_t stream);
+
 /* The MLP between gate_pool and gate_scale (resnet_cbam.py:41-53: two bias-free 1x1 convs C -> Ch -> C shared by the
  * average- and the max-pooled vector, ReLU between, Sigmoid of the sum): s[b,c] = sigmoid(W2 relu(W1 avg[b]) + W2 relu(W1
  * mx[b])).  w1 (Ch, C), w2 (C, Ch) fp32 row-major; hid (B, 2, Ch) receives the two hidden vectors for the backward pass.

@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _lock = threading.Lock()
 _lib = None
@@ -84,7 +84,11 @@ SIGNATURES = {
     "jspsr_scores_batch_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p]),
     "jspsr_adamw_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p]),
     "jspsr_adamw_step_dev": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_p, c_p]),
-    "jspsr_tiles_crop_f32": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),
+    "jspsr_optim_workspace_bytes": (ctypes.c_size_t, []),
+    "jspsr_optim_step": (c_i, [c_i, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p]),
+    "jspsr_tensor_ranges_workspace_bytes": (ctypes.c_size_t, []),
+    "jspsr_tensor_ranges": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_tiles_crop_f32":(c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),
     "jspsr_tiles_merge_f32": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "jspsr_mirror_pad_f32": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "jspsr_elev_scale_f32": (c_i, [c_p, c_p, c_ll, c_i, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_p]),

@@ -7,9 +7,8 @@ runs the model and one meter object per score on ONE tile per step (valid_batch_
 `.item()`; here a batch of any size is scored by one launch (`metrics.batch_scores`, K10), the rows stay in a device
 table, and a pass ends in one device-to-host copy.
 
-Left out: plotting, GeoTIFF output, summarise_evaluation, the skimage and richdem packages, the bicubic resize of a
-smaller input, and EarlyStopper (its comparisons read the `val_loss` argument instead of the monitored value; a port
-would have to choose which to copy).
+Left out: plotting, GeoTIFF output, summarise_evaluation, the skimage and richdem packages and the bicubic resize of a
+smaller input.  (EarlyStopper is in jspsr_amd/train.py.)
 """
 from __future__ import annotations
 
