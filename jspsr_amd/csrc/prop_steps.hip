@@ -13,8 +13,11 @@
 //     workspace, and a second, pixel-ordered pass (prop_step_gdem_gather_kernel) lets every pixel GATHER the 3..6 windows
 //     that cover it, in fixed order, and adds the sum into grad_dem.  Rounds 2-3 used ds_add_f32 (~170 cycles per wave
 //     instruction on gfx950: 320 of the kernel's 450 us) and flushed every window with device-scope float atomics.
-//     Only taps BEYOND tile + halo (|offset| > 8 px) still add to grad_dem with global float atomics, so grad_dem is
-//     bit-reproducible whenever no such tap exists (everything else always is).
+//     Only taps BEYOND tile + halo (possible from |offset| >= 7 px on) still add to grad_dem with global float atomics, so grad_dem is
+//     bit-reproducible whenever no such tap exists (everything else always is).  Range of the per-tile scale 2^fexp:
+//     fexp = 45 - ilogb(tile max) puts the tile's largest term at [2^45, 2^46), so one unit is <= (tile max) * 2^-45 and
+//     grad_out * 2^k gives exactly grad_dem * 2^k; fexp is clamped at 126 (the largest power of two ldexpf can hand back
+//     is 2^127), i.e. the scale follows the tile maximum down to 2^-81; below that one unit stays 2^-126.
 //   * gradients of the fixed affinities / offsets SUMMED over the iterations -> ACC: add into grad_weight / grad_offset.
 // Same tile (8 x 64, one pixel per lane), same LDS staging and border rule as prop.hip.
 #include "prop_tile.h"
@@ -48,8 +51,10 @@ __device__ __forceinline__ constexpr int soch(int k, int c) {
 // profiles/r04_k1s_backward.txt) while the integer atomics run at the LDS's normal rate -- and integer addition is
 // associative, so the window's content does not depend on the order the waves arrive in (bit-reproducible without
 // per-wave windows).  `fscale` = 2^e, chosen per tile so that the largest |contribution| sits at 2^45: 24 significant bits
-// of every fp32 product survive exactly, and 2^17 such terms cannot overflow.
-__device__ __forceinline__ unsigned long long to_fixed(float c) { return (unsigned long long)(long long)c; }
+// of every fp32 product survive exactly, and 2^17 such terms cannot overflow.  Terms are ROUNDED to the nearest unit: a
+// cast truncates toward zero, which pulls every sum toward zero -- with one term of a tile 2^30 times the others, the
+// small gradients came out 0.7 units short on average (mean |error| 1.4 units; 0.6 units and no bias with rounding).
+__device__ __forceinline__ unsigned long long to_fixed(float c) { return (unsigned long long)__float2ll_rn(c); }
 
 template <int LH, int LW>
 __device__ __forceinline__ void scatter_corners(unsigned long long* __restrict__ ldsacc, float* __restrict__ gimg, int H, int W,
@@ -76,7 +81,7 @@ __device__ __forceinline__ void scatter_corners(unsigned long long* __restrict__
     atomicAdd(p + LW + 1, to_fixed(vs * ly * lx));
 #endif
   } else if (near) {
-    // a tap beyond tile + halo (|offset| > 8 px): global float atomics -- the one place where grad_dem's last bits depend
+    // a tap beyond tile + halo (|offset| >= 7 px): global float atomics -- the one place where grad_dem's last bits depend
     // on the execution order
     const bool y0ok = (unsigned)y0 < (unsigned)H, y1ok = (unsigned)(y0 + 1) < (unsigned)H;
     const bool x0ok = (unsigned)x0 < (unsigned)W, x1ok = (unsigned)(x0 + 1) < (unsigned)W;
@@ -210,7 +215,8 @@ __global__ __launch_bounds__(NT) void prop_step_bwd_kernel(const float* __restri
     float t_ = tmax[0];
 #pragma unroll
     for (int w = 1; w < NT / 64; ++w) t_ = fmaxf(t_, tmax[w]);
-    fexp = t_ > 0.f ? min(100, 45 - ilogbf(t_)) : 0;       // the largest term lands in [2^45, 2^46)
+    // the largest term lands in [2^45, 2^46); 2^126 is the last scale ldexpf can give, reached at a tile maximum of 2^-81
+    fexp = t_ > 0.f ? min(126, 45 - ilogbf(t_)) : 0;
     fscale = ldexpf(1.f, fexp);
   }
   float sums[NRED];
