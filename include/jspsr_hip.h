@@ -353,13 +353,17 @@ size_t jspsr_reduce_workspace_bytes(int dtype, int C, int nseg);
  * The shortcut of a projecting BasicBlock is itself conv1x1 -> BatchNorm (basics.py:118-119): instead of normalising
  * it in a pass of its own, that BatchNorm is called with y == NULL and affine_out [2][C] (statistics, running stats
  * and its per-channel scale | shift only), and the block's second BatchNorm takes the RAW conv1x1 output as `res`
- * together with res_affine = that [2][C]:  y = [relu]( bn(x) * res_scale + (res * res_affine[0] + res_affine[1]) ). */
+ * together with res_affine = that [2][C]:  y = [relu]( bn(x) * res_scale + (res * res_affine[0] + res_affine[1]) ).
+ * mask_out (may be NULL; needs res, relu and y): the ReLU's bit mask for the backward, jspsr_bn_mask_bytes(dtype, npix, C)
+ * bytes -- one bit per element, set where y AS STORED (after rounding to the storage type) is > 0.  jspsr_bn_backward
+ * (relu = 1) takes it in place of y: one byte per 16 bytes of y to read.  The layout is private to the two entries. */
+size_t jspsr_bn_mask_bytes(int dtype, long long npix, int C);
 int jspsr_bn_forward(int dtype, const void* x, int x_cs, int x_coff, const void* res, int r_cs, int r_coff,
                      void* y, int y_cs, int y_coff, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float momentum, float eps, int training,
                      int relu, float res_scale, float* save_mean, float* save_invstd, long long npix, int C,
                      const float* ext_partial, int ext_rows, const float* res_affine, float* affine_out,
-                     void* workspace, jspsr_stream_t stream);
+                     void* mask_out, void* workspace, jspsr_stream_t stream);
 
 /* BatchNorm in eval mode as a per-channel affine: scale = gamma / sqrt(var + eps) * res_scale,
  * shift = (beta - mean * gamma / sqrt(var + eps)) * res_scale. */
@@ -372,14 +376,18 @@ int jspsr_bn_fold(const float* gamma, const float* beta, const float* running_me
  * dgamma, dbeta [C]: overwritten, or added to when accumulate != 0 (gradients landing directly in a
  * caller-owned accumulation buffer).
  * ext_partial / ext_rows (NULL / 0: this call makes its own reduce pass): the per-tile sums of dz and dz * xhat, rows of
- * [2][C], that the producing data gradient's epilogue wrote (jspsr_conv2d_dgrad: red_out) -- relu mode 2 only. */
+ * [2][C], that the producing data gradient's epilogue wrote (jspsr_conv2d_dgrad: red_out) -- relu mode 2 only.
+ * mask (may be NULL; relu = 1 only): the bit mask jspsr_bn_forward wrote (mask_out); it replaces the reads of y, which
+ * may then be NULL.  Same bits as with y.
+ * relu = 1 with dres != NULL makes 7 tensor passes (6 with mask) instead of 8: the reduce pass writes dres = the masked dy
+ * while it sums, and the apply pass reads dres back as its dy.  Sums, order and results are those of the 8-pass form. */
 int jspsr_bn_reduce_params(const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, int C,
                            float* par, jspsr_stream_t stream);
 int jspsr_bn_backward(int dtype, const void* dy, int dy_cs, int dy_coff, const void* y, int y_cs, int y_coff,
                       const void* x, int x_cs, int x_coff, const float* gamma, const float* beta, const float* save_mean,
                       const float* save_invstd, int training, int relu, float res_scale, void* dx, void* dres,
                       float* dgamma, float* dbeta, int accumulate, long long npix, int C, void* workspace,
-                      const float* ext_partial, int ext_rows, jspsr_stream_t stream);
+                      const float* ext_partial, int ext_rows, const void* mask, jspsr_stream_t stream);
 
 /* Backward of the conv epilogue `y = [relu](conv + bias)` of the BN-free Basic2d (basics.py:36-53):
  * dz = dy * [y > 0] (y read with channel pitch y_cs; dz written with pitch dz_cs if dz != NULL),

@@ -51,7 +51,7 @@ __device__ __forceinline__ unsigned bf16_bits(float x) {  // round-to-nearest-ev
 }
 
 template <typename T>
-__device__ __forceinline__ void store_vec(T* p, const float (&f)[V<T>::N]) {
+__device__ __forceinline__ uint4 pack_vec(const float (&f)[V<T>::N]) {
   uint4 raw;
   if constexpr (sizeof(T) == 4) {
     raw.x = __float_as_uint(f[0]); raw.y = __float_as_uint(f[1]); raw.z = __float_as_uint(f[2]); raw.w = __float_as_uint(f[3]);
@@ -61,7 +61,22 @@ __device__ __forceinline__ void store_vec(T* p, const float (&f)[V<T>::N]) {
     raw.z = bf16_bits(f[4]) | (bf16_bits(f[5]) << 16);
     raw.w = bf16_bits(f[6]) | (bf16_bits(f[7]) << 16);
   }
-  *reinterpret_cast<uint4*>(p) = raw;
+  return raw;
+}
+template <typename T>
+__device__ __forceinline__ void store_vec(T* p, const float (&f)[V<T>::N]) { *reinterpret_cast<uint4*>(p) = pack_vec<T>(f); }
+
+// The ReLU bit mask of a lane vector: bit k set where channel k of the STORED 16 bytes (after rounding to T) is > 0 -- the
+// predicate the backward applies to the saved output.  One byte per lane vector, [pixel][C / N]: the bytes of a wave's
+// 64 lanes are contiguous, like its 16-byte pieces.
+template <typename T>
+__device__ __forceinline__ unsigned char relu_bits(const uint4& raw) {
+  float f[V<T>::N];
+  unpack<T>(raw, f);
+  unsigned m = 0;
+#pragma unroll
+  for (int k = 0; k < V<T>::N; ++k) m |= (f[k] > 0.f ? 1u : 0u) << k;
+  return (unsigned char)m;
 }
 
 struct Slice {  // a channel slice of an NHWC tensor
@@ -248,6 +263,18 @@ __device__ __forceinline__ void wave_sum_rows2(const float* __restrict__ partial
   s1 = b;
 }
 
+// The 16 bytes `raw` with every channel whose bit of m (relu_bits) is clear set to +0: the masked gradient, exactly
+template <typename T>
+__device__ __forceinline__ uint4 keep_bits(const uint4& raw, unsigned m) {
+  unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if constexpr (sizeof(T) == 4) w[j] &= 0u - ((m >> j) & 1u);
+    else w[j] &= ((0u - ((m >> (2 * j)) & 1u)) & 0xffffu) | ((0u - ((m >> (2 * j + 1)) & 1u)) & 0xffff0000u);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // ---------------------------------------------------------------- BatchNorm forward
 template <typename T>
 __global__ __launch_bounds__(TX * TY) void bn_stats_kernel(const T* __restrict__ x, int cs, int coff, RedGeom g,
@@ -332,13 +359,15 @@ __global__ void bn_fold_kernel(const float* __restrict__ gamma, const float* __r
 }
 
 // y = [relu]( (x*scale + shift) * res_scale + res )
-template <typename T, bool RES>
+template <typename T, bool RES, bool MASK>
 __global__ __launch_bounds__(TX * TY) void bn_apply_kernel(const T* __restrict__ x, int x_cs, int x_coff,
                                                           const T* __restrict__ res, int r_cs, int r_coff,
                                                           T* __restrict__ y, int y_cs, int y_coff,
                                                           const float* __restrict__ scale, const float* __restrict__ shift,
-                                                          const float* __restrict__ raff, float res_scale, int relu, RedGeom g) {
+                                                          const float* __restrict__ raff, float res_scale, int relu,
+                                                          unsigned char* __restrict__ mask, RedGeom g) {
   constexpr int N = V<T>::N;
+  const int groups = g.C / N;
   float sc[N], sh[N], rsc[N], rsh[N];
   const int c0 = lane_map<N>(g).c;
   if (c0 < g.C) { load_param<N>(scale + c0, sc); load_param<N>(shift + c0, sh); }
@@ -363,24 +392,34 @@ __global__ __launch_bounds__(TX * TY) void bn_apply_kernel(const T* __restrict__
           if (relu) v = fmaxf(v, 0.f);
           f[k] = v;
         }
-        store_vec<T>(y + (size_t)pix * y_cs + y_coff + c, f);
+        const uint4 o = pack_vec<T>(f);
+        *reinterpret_cast<uint4*>(y + (size_t)pix * y_cs + y_coff + c) = o;
+        if constexpr (MASK) mask[(size_t)pix * groups + c / N] = relu_bits<T>(o);
       });
 }
 
 // ---------------------------------------------------------------- BatchNorm backward
 // dz = dy * (y > 0 if relu);  partial sums of dz and dz * xhat
 // RELU (compile time, so that the pixel loop has no branch between its loads): 0 none; 1 mask from the saved output y;
-// 2 (no residual) mask recomputed from x, [gamma*xhat + beta > 0], which saves reading y.
-template <typename T, int RELU>
+// 2 (no residual) mask recomputed from x, [gamma*xhat + beta > 0], which saves reading y; 3 mask from the forward's bit
+// mask (relu_bits: one byte per lane vector in place of 16 bytes of y).
+// DRES (modes 1 and 3): the masked gradient dz -- dy or zero, so exact -- goes out as the residual branch's gradient
+// here, once; the apply pass then reads it in place of dy and needs neither y nor the mask.  It is formed from dy's raw
+// bytes (keep_bits) and stored before the arithmetic: packing the unpacked floats again measured 6-10 % slower over the
+// call (8 x 512^2 x 64 bf16: 358 vs 324 us), two or three pixels in flight instead of four 1-2 % slower.
+template <typename T, int RELU, bool DRES>
 __global__ __launch_bounds__(TX * TY) void bn_bwd_reduce_kernel(const T* __restrict__ dy, int dy_cs, int dy_coff,
                                                                const T* __restrict__ y, int y_cs, int y_coff,
                                                                const T* __restrict__ x, int x_cs, int x_coff,
                                                                const float* __restrict__ mean,
                                                                const float* __restrict__ invstd,
                                                                const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, RedGeom g,
+                                                               const float* __restrict__ beta,
+                                                               const unsigned char* __restrict__ mask,
+                                                               T* __restrict__ dres, RedGeom g,
                                                                float* __restrict__ partial) {
-  constexpr int N = V<T>::N, NTEN = RELU == 1 ? 3 : 2;
+  constexpr int N = V<T>::N, NTEN = (RELU == 1 || RELU == 3) ? 3 : 2;
+  const int groups = g.C / N;
   float mu[N], is[N], ga[N], be[N];       // per-channel parameters live in registers
   const int c0 = lane_map<N>(g).c;
   if (c0 < g.C) {
@@ -393,16 +432,22 @@ __global__ __launch_bounds__(TX * TY) void bn_bwd_reduce_kernel(const T* __restr
         raw[0] = load_raw<T>(dy + (size_t)pix * dy_cs + dy_coff + c);
         raw[1] = load_raw<T>(x + (size_t)pix * x_cs + x_coff + c);
         if constexpr (RELU == 1) raw[2] = load_raw<T>(y + (size_t)pix * y_cs + y_coff + c);
+        if constexpr (RELU == 3) raw[2].x = mask[(size_t)pix * groups + c / N];
       },
-      [&](long long, int, const uint4 (&raw)[NTEN], float (&acc)[2][N]) {
+      [&](long long pix, int c, const uint4 (&raw)[NTEN], float (&acc)[2][N]) {
         float d[N], xv[N], yv[N];
+        unsigned m = 0;      // modes 1 and 3: bit i set where the ReLU was open
+        if constexpr (RELU == 3) m = raw[2].x;
+        if constexpr (RELU == 1 && DRES) m = relu_bits<T>(raw[2]);
+        if constexpr (DRES) *reinterpret_cast<uint4*>(dres + (size_t)pix * g.C + c) = keep_bits<T>(raw[0], m);
         unpack<T>(raw[0], d);
         unpack<T>(raw[1], xv);
-        if constexpr (RELU == 1) unpack<T>(raw[2], yv);
+        if constexpr (RELU == 1 && !DRES) unpack<T>(raw[2], yv);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
           const float xhat = (xv[i] - mu[i]) * is[i];
-          const bool off = RELU == 1 ? !(yv[i] > 0.f) : (RELU == 2 ? !(ga[i] * xhat + be[i] > 0.f) : false);
+          const bool off = (RELU == 3 || (RELU == 1 && DRES)) ? !((m >> i) & 1u)
+                           : (RELU == 1 ? !(yv[i] > 0.f) : (RELU == 2 ? !(ga[i] * xhat + be[i] > 0.f) : false));
           const float dz = off ? 0.f : d[i];
           acc[0][i] += dz;
           acc[1][i] += dz * xhat;
@@ -436,9 +481,10 @@ __global__ __launch_bounds__(TX * TY) void bn_bwd_apply_kernel(const T* __restri
                                                               const float* __restrict__ mean, const float* __restrict__ invstd,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               const float* __restrict__ coef,
+                                                              const unsigned char* __restrict__ mask,
                                                               T* __restrict__ dx, T* __restrict__ dres, RedGeom g) {
-  constexpr int N = V<T>::N, NTEN = RELU == 1 ? 3 : 2;
-  const int C = g.C;
+  constexpr int N = V<T>::N, NTEN = (RELU == 1 || RELU == 3) ? 3 : 2;
+  const int C = g.C, groups = C / N;
   float mu[N], is[N], k0[N], ka[N], kb[N], ga[N], be[N];
   const int c0 = lane_map<N>(g).c;
   if (c0 < C) {
@@ -452,6 +498,7 @@ __global__ __launch_bounds__(TX * TY) void bn_bwd_apply_kernel(const T* __restri
         raw[0] = load_raw<T>(dy + (size_t)pix * dy_cs + dy_coff + c);
         raw[1] = load_raw<T>(x + (size_t)pix * x_cs + x_coff + c);
         if constexpr (RELU == 1) raw[2] = load_raw<T>(y + (size_t)pix * y_cs + y_coff + c);
+        if constexpr (RELU == 3) raw[2].x = mask[(size_t)pix * groups + c / N];
       },
       [&](long long, long long pix, int c, const uint4 (&raw)[NTEN]) {
         float d[N], xv[N], yv[N], o[N];
@@ -461,7 +508,8 @@ __global__ __launch_bounds__(TX * TY) void bn_bwd_apply_kernel(const T* __restri
 #pragma unroll
         for (int k = 0; k < N; ++k) {
           const float xhat = (xv[k] - mu[k]) * is[k];
-          const bool off = RELU == 1 ? !(yv[k] > 0.f) : (RELU == 2 ? !(ga[k] * xhat + be[k] > 0.f) : false);
+          const bool off = RELU == 1 ? !(yv[k] > 0.f)
+                                     : (RELU == 2 ? !(ga[k] * xhat + be[k] > 0.f) : (RELU == 3 ? !((raw[2].x >> k) & 1u) : false));
           const float dz = off ? 0.f : d[k];
           d[k] = dz;
           o[k] = k0[k] * (dz - ka[k] - xhat * kb[k]);
@@ -716,11 +764,12 @@ extern "C" int jspsr_bn_forward(int dtype, const void* x, int x_cs, int x_coff, 
                                 float* running_mean, float* running_var, float momentum, float eps, int training,
                                 int relu, float res_scale, float* save_mean, float* save_invstd, long long npix, int C,
                                 const float* ext_partial, int ext_rows, const float* res_affine, float* affine_out,
-                                void* workspace, jspsr_stream_t stream) {
+                                void* mask_out, void* workspace, jspsr_stream_t stream) {
   if (int e = check_c(dtype, C, "bn_forward")) return e;
   if (!x || (!y && !affine_out) || !gamma || !beta || !save_mean || !save_invstd || !workspace || npix <= 0)
     return fail(JSPSR_EINVAL, "bn_forward: null pointer or empty tensor");
   if (res_affine && !res) return fail(JSPSR_EINVAL, "bn_forward: res_affine without a residual operand");
+  if (mask_out && (!res || !relu || !y)) return fail(JSPSR_EINVAL, "bn_forward: mask_out needs an output with residual and ReLU");
   if (!training && (!running_mean || !running_var)) return fail(JSPSR_EINVAL, "bn_forward: eval mode needs running stats");
   const int vec = dtype == JSPSR_F32 ? 4 : 8;
   if (x_cs % vec || x_coff % vec || y_cs % vec || y_coff % vec || (res && (r_cs % vec || r_coff % vec)))
@@ -754,10 +803,11 @@ extern "C" int jspsr_bn_forward(int dtype, const void* x, int x_cs, int x_coff, 
   if (int e = check_launch("bn_finalize")) return e;
   if (!y) return JSPSR_OK;      // statistics + (scale | shift) only: the consumer applies them (res_affine)
   const RedGeom ga = make_red(npix, 1, C, vec);
-#define BN_APPLY(R) DISPATCH(dtype, hipLaunchKernelGGL((bn_apply_kernel<T, R>), red_grid(ga, vec), dim3(TX, TY), 0, s,             \
+#define BN_APPLY(R, M) DISPATCH(dtype, hipLaunchKernelGGL((bn_apply_kernel<T, R, M>), red_grid(ga, vec), dim3(TX, TY), 0, s,       \
                                      static_cast<const T*>(x), x_cs, x_coff, static_cast<const T*>(res), r_cs, r_coff,        \
-                                     static_cast<T*>(y), y_cs, y_coff, scale, shift, res_affine, res_scale, relu, ga))
-  if (res) { BN_APPLY(true); } else { BN_APPLY(false); }
+                                     static_cast<T*>(y), y_cs, y_coff, scale, shift, res_affine, res_scale, relu,             \
+                                     static_cast<unsigned char*>(mask_out), ga))
+  if (mask_out) { BN_APPLY(true, true); } else if (res) { BN_APPLY(true, false); } else { BN_APPLY(false, false); }
 #undef BN_APPLY
   return check_launch("bn_apply");
 }
@@ -775,6 +825,12 @@ __global__ void bn_reduce_params_kernel(const float* __restrict__ gamma, const f
   par[3 * C + c] = -mean[c] * invstd[c];
 }
 
+extern "C" size_t jspsr_bn_mask_bytes(int dtype, long long npix, int C) {
+  const int vec = dtype == JSPSR_F32 ? 4 : 8;
+  if (npix <= 0 || C <= 0 || C % vec) return 0;
+  return (size_t)npix * (size_t)(C / vec);
+}
+
 extern "C" int jspsr_bn_reduce_params(const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, int C,
                                       float* par, jspsr_stream_t stream) {
   if (!gamma || !beta || !save_mean || !save_invstd || !par || C <= 0) return fail(JSPSR_EINVAL, "bn_reduce_params: bad arguments");
@@ -787,22 +843,29 @@ extern "C" int jspsr_bn_backward(int dtype, const void* dy, int dy_cs, int dy_co
                                  const void* x, int x_cs, int x_coff, const float* gamma, const float* beta, const float* save_mean,
                                  const float* save_invstd, int training, int relu, float res_scale, void* dx, void* dres,
                                  float* dgamma, float* dbeta, int accumulate, long long npix, int C, void* workspace,
-                                 const float* ext_partial, int ext_rows, jspsr_stream_t stream) {
+                                 const float* ext_partial, int ext_rows, const void* mask, jspsr_stream_t stream) {
   if (int e = check_c(dtype, C, "bn_backward")) return e;
   if (!dy || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace || npix <= 0 ||
-      (relu == 1 && !y) || (relu == 2 && !beta) || relu < 0 || relu > 2)
+      (relu == 1 && !y && !mask) || (relu == 2 && !beta) || relu < 0 || relu > 2)
     return fail(JSPSR_EINVAL, "bn_backward: null pointer, empty tensor or bad relu mode");
   const int vec = dtype == JSPSR_F32 ? 4 : 8;
-  if (dy_cs % vec || dy_coff % vec || x_cs % vec || x_coff % vec || (relu == 1 && (y_cs % vec || y_coff % vec)))
+  if (dy_cs % vec || dy_coff % vec || x_cs % vec || x_coff % vec || (relu == 1 && !mask && (y_cs % vec || y_coff % vec)))
     return fail(JSPSR_EINVAL, "bn_backward: channel pitches/offsets must be multiples of %d", vec);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
   float* coef = ws;
   float* partial = ws + 3 * C;
   const RedGeom g = make_red(npix, 1, C, vec);
-#define BN_BWD_REDUCE(R) DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, R>), red_grid(g, vec), dim3(TX, TY), 0, s, \
+  // relu == 1: the mask comes from the forward's bit mask where one is given (mode 3), from the saved output otherwise
+  const unsigned char* mk = relu == 1 ? static_cast<const unsigned char*>(mask) : nullptr;
+  const int mode = (relu == 1 && mk) ? 3 : relu;
+  // ... and where the residual branch's gradient is wanted, the reduce pass writes it and the apply pass reads it back as
+  // its dy, unmasked: 7 (6 with the bit mask) tensor passes instead of 8, the same values in the same order
+  const bool premask = relu == 1 && dres && !ext_partial;
+#define BN_BWD_REDUCE(R, D) DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, R, D>), red_grid(g, vec), dim3(TX, TY), 0, s, \
                                      static_cast<const T*>(dy), dy_cs, dy_coff, static_cast<const T*>(y), y_cs, y_coff,     \
-                                     static_cast<const T*>(x), x_cs, x_coff, save_mean, save_invstd, gamma, beta, g, partial))
+                                     static_cast<const T*>(x), x_cs, x_coff, save_mean, save_invstd, gamma, beta, mk,        \
+                                     static_cast<T*>(dres), g, partial))
   int rows = g.chunks;
   if (ext_partial) {
     // the two sums per channel came out of the producing data gradient's epilogue (jspsr_conv2d_dgrad: red_out), one row
@@ -817,18 +880,25 @@ extern "C" int jspsr_bn_backward(int dtype, const void* dy, int dy_cs, int dy_co
       rows = ext_rows;
     }
   } else {
-    if (relu == 0) { BN_BWD_REDUCE(0); } else if (relu == 1) { BN_BWD_REDUCE(1); } else { BN_BWD_REDUCE(2); }
+    if (mode == 0) { BN_BWD_REDUCE(0, false); }
+    else if (mode == 2) { BN_BWD_REDUCE(2, false); }
+    else if (mode == 1) { if (premask) { BN_BWD_REDUCE(1, true); } else { BN_BWD_REDUCE(1, false); } }
+    else { if (premask) { BN_BWD_REDUCE(3, true); } else { BN_BWD_REDUCE(3, false); } }
     if (int e = check_launch("bn_bwd_reduce")) return e;
   }
 #undef BN_BWD_REDUCE
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, rows, C, npix, gamma,
                      save_invstd, training, res_scale, accumulate, dgamma, dbeta, coef);
   if (int e = check_launch("bn_bwd_finalize")) return e;
-#define BN_BWD_APPLY(R) DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, R>), red_grid(g, vec), dim3(TX, TY), 0, s,  \
-                                     static_cast<const T*>(dy), dy_cs, dy_coff, static_cast<const T*>(y), y_cs, y_coff,     \
-                                     static_cast<const T*>(x), x_cs, x_coff, save_mean, save_invstd, gamma, beta, coef,     \
-                                     static_cast<T*>(dx), static_cast<T*>(dres), g))
-  if (relu == 0) { BN_BWD_APPLY(0); } else if (relu == 1) { BN_BWD_APPLY(1); } else { BN_BWD_APPLY(2); }
+#define BN_BWD_APPLY(R, DY, CS, OFF, DRES) DISPATCH(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, R>), red_grid(g, vec), dim3(TX, TY), 0, s, \
+                                     static_cast<const T*>(DY), CS, OFF, static_cast<const T*>(y), y_cs, y_coff,            \
+                                     static_cast<const T*>(x), x_cs, x_coff, save_mean, save_invstd, gamma, beta, coef, mk, \
+                                     static_cast<T*>(dx), static_cast<T*>(DRES), g))
+  if (premask) { BN_BWD_APPLY(0, dres, C, 0, nullptr); }
+  else if (mode == 0) { BN_BWD_APPLY(0, dy, dy_cs, dy_coff, dres); }
+  else if (mode == 1) { BN_BWD_APPLY(1, dy, dy_cs, dy_coff, dres); }
+  else if (mode == 2) { BN_BWD_APPLY(2, dy, dy_cs, dy_coff, dres); }
+  else { BN_BWD_APPLY(3, dy, dy_cs, dy_coff, dres); }
 #undef BN_BWD_APPLY
   return check_launch("bn_bwd_apply");
 }

@@ -224,11 +224,13 @@ def _workspace(dtype_code: int, C: int, nseg: int, device) -> torch.Tensor:
 
 
 def bn_forward(x, gamma, beta, running_mean, running_var, momentum, eps, training, relu=False, res=None,
-               res_scale=1.0, out=None, out_coff=0, partial=None, res_affine=None, stats_only=False):
+               res_scale=1.0, out=None, out_coff=0, partial=None, res_affine=None, stats_only=False, want_mask=False):
     """x (B,H,W,C) -> y = [relu](bn(x)*res_scale + res); returns (y, save_mean, save_invstd).
     partial: (rows, 2, C) statistics from conv2d_forward(stats=True) -- skips the statistics pass.
     stats_only: no output tensor; returns (affine, save_mean, save_invstd) with affine (2, C) fp32 = this BatchNorm's
-    per-channel (scale | shift) for a consumer to apply.  res_affine: such an affine for the residual operand."""
+    per-channel (scale | shift) for a consumer to apply.  res_affine: such an affine for the residual operand.
+    want_mask (needs relu and res): a fourth element, the ReLU's bit mask (opaque uint8 tensor) that bn_backward(relu=1)
+    takes as mask= in place of y."""
     _chk_s(x, "bn_forward")
     B, H, W, C = x.shape
     affine = torch.empty((2, C), dtype=torch.float32, device=x.device) if stats_only else None
@@ -239,6 +241,7 @@ def bn_forward(x, gamma, beta, running_mean, running_var, momentum, eps, trainin
     dt = _dt(x)
     ws = _workspace(dt, C, 1, x.device)
     lib = _lib.load()
+    mask = torch.empty(lib.jspsr_bn_mask_bytes(dt, B * H * W, C), dtype=torch.uint8, device=x.device) if want_mask else None
     _lib.check(lib.jspsr_bn_forward(dt, x.data_ptr(), pitch(x), 0, res.data_ptr() if res is not None else None,
                                     pitch(res) if res is not None else 0, 0, out.data_ptr() if out is not None else None,
                                     pitch(out) if out is not None else 0, out_coff,
@@ -250,8 +253,11 @@ def bn_forward(x, gamma, beta, running_mean, running_var, momentum, eps, trainin
                                     partial.data_ptr() if partial is not None else None,
                                     partial.shape[0] if partial is not None else 0,
                                     res_affine.data_ptr() if res_affine is not None else None,
-                                    affine.data_ptr() if affine is not None else None, ws.data_ptr(), _stream()),
+                                    affine.data_ptr() if affine is not None else None,
+                                    mask.data_ptr() if mask is not None else None, ws.data_ptr(), _stream()),
                "jspsr_bn_forward")
+    if want_mask:
+        return (affine if stats_only else out), mean, invstd, mask
     return (affine if stats_only else out), mean, invstd
 
 
@@ -267,8 +273,9 @@ def bn_fold(gamma, beta, running_mean, running_var, eps, res_scale=1.0):
 
 
 def bn_backward(dy, y, x, gamma, mean, invstd, training, relu, res_scale=1.0, want_dres=False, beta=None,
-                grads_into=None, ext_partial=None):
-    """-> (dx, dres or None, dgamma, dbeta).  relu: False/0, True/1 (mask from y) or 2 (mask from x, needs beta).
+                grads_into=None, ext_partial=None, mask=None):
+    """-> (dx, dres or None, dgamma, dbeta).  relu: False/0, True/1 (mask from y, or from mask= -- the bit mask of
+    bn_forward(want_mask=True) -- and then y may be None) or 2 (mask from x, needs beta).
     grads_into = (dgamma_buf, dbeta_buf): add the parameter gradients to those fp32 buffers instead of
     returning fresh tensors (then dgamma, dbeta come back as None)."""
     _chk_s(dy, "bn_backward")
@@ -286,6 +293,9 @@ def bn_backward(dy, y, x, gamma, mean, invstd, training, relu, res_scale=1.0, wa
     dt = _dt(x)
     ws = _workspace(dt, C, 1, x.device)
     lib = _lib.load()
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or
+                             mask.numel() != lib.jspsr_bn_mask_bytes(dt, B * H * W, C)):
+        raise ValueError("bn_backward: mask is not the bit mask bn_forward(want_mask=True) made for this shape")
     _lib.check(lib.jspsr_bn_backward(dt, dy.data_ptr(), pitch(dy), 0, y.data_ptr() if y is not None else None,
                                      pitch(y) if y is not None else 0, 0, x.data_ptr(), pitch(x), 0, gamma.data_ptr(),
                                      beta.data_ptr() if beta is not None else None,
@@ -294,7 +304,7 @@ def bn_backward(dy, y, x, gamma, mean, invstd, training, relu, res_scale=1.0, wa
                                      dbeta.data_ptr(), int(grads_into is not None), B * H * W, C, ws.data_ptr(),
                                      ext_partial.data_ptr() if ext_partial is not None else None,
                                      ext_partial.shape[0] if ext_partial is not None else 0,
-                                     _stream()), "jspsr_bn_backward")
+                                     mask.data_ptr() if mask is not None else None, _stream()), "jspsr_bn_backward")
     if grads_into is not None:
         return dx, dres, None, None
     return dx, dres, dgamma, dbeta

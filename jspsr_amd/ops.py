@@ -605,6 +605,9 @@ wgrad_async = os.environ.get("JSPSR_WGRAD_ASYNC", "1") != "0"
 wgrad_after_dgrad = os.environ.get("JSPSR_WGRAD_AFTER_DGRAD", "0") != "0"   # lab: weight gradients forked behind their layer's data gradient
 wgrad_one_stream = os.environ.get("JSPSR_WGRAD_ONE_STREAM", "0") != "0"   # lab: ONE weight-gradient stream for all home streams
 bn_reduce_fused = os.environ.get("JSPSR_BN_REDUCE_FUSE", "1") != "0"      # bn1's backward reduce in conv2's data-gradient epilogue
+# BatchNorm + residual + ReLU: the forward writes the ReLU's bit mask (1 bit per element) and the backward reads it in place
+# of the saved output
+bn_relu_mask = os.environ.get("JSPSR_BN_RELU_MASK", "1") != "0"
 
 
 def aux_streams():
@@ -841,23 +844,27 @@ class _BatchNorm(torch.autograd.Function):
         res_c = K.nhwc(res) if res is not None else None
         rs = float(res_scale) if res is not None else 1.0
         out = dest[0].slice(dest[1], x.shape[3], x.shape[:3]) if dest is not None else None
-        y, mean, invstd = K.bn_forward(x, gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
-                                       training, relu, res_c, rs, partial=partial if training else None, out=out)
         # without a residual the ReLU mask is a function of x alone: the backward recomputes it (mode 2)
-        # instead of reading the saved output
+        # instead of reading the saved output; with one it reads the forward's bit mask (or, switched off, the output)
         mode = 0 if not relu else (1 if res is not None else 2)
+        masked = mode == 1 and bn_relu_mask
+        y, mean, invstd, *mk = K.bn_forward(x, gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
+                                            training, relu, res_c, rs, partial=partial if training else None, out=out,
+                                            want_mask=masked)
         ctx.gb = tuple(p if isinstance(p, torch.nn.Parameter) else None for p in (gamma, beta))
         ctx.cfg = (training, mode, rs, res is not None)
-        ctx.save_for_backward(x, y if mode == 1 else None, gamma.detach(), beta.detach(), mean, invstd)
+        ctx.save_for_backward(x, y if mode == 1 and not masked else None, gamma.detach(), beta.detach(), mean, invstd,
+                              mk[0] if masked else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         training, relu, rs, has_res = ctx.cfg
-        x, y, gamma, beta, mean, invstd = ctx.saved_tensors
+        x, y, gamma, beta, mean, invstd, mask = ctx.saved_tensors
         sink = _bn_sink(*ctx.gb)
         dx, dres, dgamma, dbeta = K.bn_backward(K.nhwc(dy), y, x, gamma, mean, invstd, training, relu, rs,
-                                                want_dres=has_res and ctx.needs_input_grad[9], beta=beta, grads_into=sink)
+                                                want_dres=has_res and ctx.needs_input_grad[9], beta=beta, grads_into=sink,
+                                                mask=mask)
         if sink is not None:
             _bn_ready(*ctx.gb)
         if has_res and ctx.needs_input_grad[9] and dres is None:
@@ -905,13 +912,13 @@ class _ResUnit(torch.autograd.Function):
         g1d, b1d, g2d, b2d = g1.detach(), b1.detach(), g2.detach(), b2.detach()
 
         def conv_bn(inp, wt, k, st, pad, gam, bet, rm, rv, mom, eps, tr, relu, res=None, rs=1.0, out=None, par=None,
-                    res_affine=None, stats_only=False, in_affine=None):
+                    res_affine=None, stats_only=False, in_affine=None, want_mask=False):
             z = K.conv2d_forward(inp, _packed(par, wt, 0, inp.shape[3], cdt), None, st, pad, False, stats=tr,
                                  in_affine=in_affine, in_relu=in_affine is not None)
             z, part = z if tr else (z, None)
-            y, mean, invstd = K.bn_forward(z, gam, bet, rm, rv, mom, eps, tr, relu, res, rs, partial=part, out=out,
-                                           res_affine=res_affine, stats_only=stats_only)
-            return z, y, mean, invstd
+            y, mean, invstd, *mk = K.bn_forward(z, gam, bet, rm, rv, mom, eps, tr, relu, res, rs, partial=part, out=out,
+                                                res_affine=res_affine, stats_only=stats_only, want_mask=want_mask)
+            return (z, y, mean, invstd, mk[0]) if want_mask else (z, y, mean, invstd)
 
         OH1, OW1 = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
         fuse1 = fuse_bn1_input and K.fused_input_ok(cdt, B, OH1, OW1, O, O, 3, 3, 1, 1)
@@ -940,19 +947,21 @@ class _ResUnit(torch.autograd.Function):
             trd = False
             r = x
         out_v = dest[0].slice(dest[1], O, z1.shape[:3]) if dest is not None else None
-        z2, out, m2, i2 = conv_bn(z1 if fuse1 else y1, w2d, 3, 1, 1, g2d, b2d, rm2, rv2, mom2, eps2, tr2, bool(act), r, float(scale),
-                                  out_v, par=w2, res_affine=r_aff, in_affine=aff1)
+        # bn2 + residual + ReLU: the backward masks with the forward's bit mask instead of reading `out` again
+        masked = bool(act) and bn_relu_mask
+        z2, out, m2, i2, *mk2 = conv_bn(z1 if fuse1 else y1, w2d, 3, 1, 1, g2d, b2d, rm2, rv2, mom2, eps2, tr2, bool(act), r, float(scale),
+                                        out_v, par=w2, res_affine=r_aff, in_affine=aff1, want_mask=masked)
         ctx.cfg = (stride, float(scale), bool(act), has_d, tr1, tr2, trd)
         ctx.wparams = tuple(p if isinstance(p, torch.nn.Parameter) else None for p in (w1, w2, wd))
         ctx.bparams = tuple(p if isinstance(p, torch.nn.Parameter) else None for p in (g1, b1, g2, b2, gd, bd))
-        ctx.save_for_backward(x, w1d, g1d, b1d, z1, m1, i1, y1, w2d, g2d, b2d, z2, m2, i2, out if act else None,
-                              wdd, gdd, bdd, zd, md, idd, aff1)
+        ctx.save_for_backward(x, w1d, g1d, b1d, z1, m1, i1, y1, w2d, g2d, b2d, z2, m2, i2, out if act and not masked else None,
+                              wdd, gdd, bdd, zd, md, idd, aff1, mk2[0] if masked else None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         stride, scale, act, has_d, tr1, tr2, trd = ctx.cfg
-        (x, w1, g1, b1, z1, m1, i1, y1, w2, g2, b2, z2, m2, i2, out, wd, gd, bd, zd, md, idd, aff1) = ctx.saved_tensors
+        (x, w1, g1, b1, z1, m1, i1, y1, w2, g2, b2, z2, m2, i2, out, wd, gd, bd, zd, md, idd, aff1, mask2) = ctx.saved_tensors
         cdt = x.dtype
         B, H, W, Cin = x.shape
         O = w1.shape[0]
@@ -962,7 +971,7 @@ class _ResUnit(torch.autograd.Function):
         pg1, pb1, pg2, pb2, pgd, pbd = ctx.bparams
         sink2, sink1 = _bn_sink(pg2, pb2), _bn_sink(pg1, pb1)
         dz2, dres, dg2, db2 = K.bn_backward(dout, out, z2, g2, m2, i2, tr2, 1 if act else 0, scale,
-                                            want_dres=(need_x or has_d), beta=b2, grads_into=sink2)
+                                            want_dres=(need_x or has_d), beta=b2, grads_into=sink2, mask=mask2)
         if sink2 is not None:
             _bn_ready(pg2, pb2)
         if dres is None:
