@@ -484,6 +484,55 @@ size_t jspsr_scores_batch_workspace_bytes(int B, int H, int W);
 int jspsr_scores_batch_forward(const float* pred, const float* gt, int B, int H, int W, float border, float value_min,
                                float value_max, int elev_log, float* scores, void* workspace, jspsr_stream_t stream);
 
+/* K12 (ABI v22): the whole-set validation summary -- what the reference's --val path does on the host after the model has
+ * run (csrc/summary.hip).
+ *
+ * jspsr_scenes_assemble_f32: save_prediction_to_disk (evaluation/evaluate_utils.py:242-271: clip to [0,1], descale_data,
+ *   + base) and merge_dem(..., p.val_border, method = copyto_add) (utils/utils.py:914-967, called at :1272) for all S
+ *   scenes of a batch in ONE launch.  tiles [S * n_x * n_x][k][k] fp32 in the network's range, row-major over each scene's
+ *   cover; base [S] (device) the scenes' base elevations; ramp [p] as for the K8 merge (NULL when p = 0 or n_x = 1);
+ *   out_off [S] (device, int64) the element offset of mosaic s in the pooled buffer `out` of out_numel elements (a mosaic
+ *   that would leave it is not written).  Mosaic side: stride (n_x - 1) + k - 2 border_px; n_x = 1 is the 8 m case: the
+ *   de-scaled tile, k x k, uncropped (border_px and stride ignored; the crop happens at summary time, utils.py:1300-1306).
+ *   Bit-equal to clamp -> jspsr_elev_scale_f32 (descale) -> + base -> the K8 merge run scene by scene.
+ *
+ * jspsr_summary_forward: summarise_evaluation (utils/utils.py:1238-1356) -- RMSE, median, NMAD, LE95 and PSNR of the errors
+ *   of n_cand candidates (1..8: the prediction and the baseline DEMs, fp32 metres) against one ground truth, pooled over
+ *   SEGMENTS of pitched windows (one segment of all scenes: the reference's "offline" numbers; one per scene: its
+ *   "online" ones).  cands / cand_numel: HOST arrays of n_cand device pointers and their element counts; gt likewise.
+ *   windows (device, int64 [n_windows][22]) = { segment, h, w, offset of the window's first error in the pooled error
+ *     array, gt offset, gt row pitch, then { offset, row pitch } of candidate 0..7 } in elements; rows ascending in the
+ *     error offset, the windows of a segment back to back, the error array without gaps.  A read outside its buffer, and
+ *     an element no window of its segment covers, give NaN.  Crops are read in place.
+ *   segments (device, int64 [n_segments][8]) = { start in the error array, n, first chunk, median ranks (n - 1) / 2 and
+ *     n / 2, LE95 ranks l = floor(0.95 (n - 1)) and min(l + 1, n - 1), the bits of the double g = 0.95 (n - 1) - l };
+ *     chunks are runs of 8192 elements of ONE segment, numbered through the segments in order.  total = sum of n;
+ *     total_chunks = sum of ceil(n / 8192).  The table is made by one host function (jspsr_amd/summary.py: segment_ranks).
+ *   out (device, [n_cand * n_segments][11], row = candidate * n_segments + segment) =
+ *     { RMSE, Median, NMAD, LE95, PSNR, median lo, hi, MAD lo, hi, LE95 lo, hi }, the last six the bracketing order
+ *     statistics (exact elements of e, |e - median|, |e|).
+ *   e = cand - gt in fp32.  RMSE = sqrt(sum e^2 / n), squares and sum in fp64 folded in an order the segment's size alone
+ *     fixes, rounded once (the reference's fp32 pairwise np.mean of fp32 squares is NOT reproduced).  Median = (lo + hi) *
+ *     0.5f, bit for bit np.median of a float32 array.  NMAD = fp32(1.4826 * double((lo + hi) * 0.5f)) over |e - Median| in
+ *     fp32.  LE95 = fp32(lo + (hi - lo) g) in double: np.percentile(|e| as float64, 95); on float32 input numpy 2 forms the
+ *     virtual index in float32 and numpy 1 in float64, so the reference's own value depends on the numpy version (up to
+ *     2.4e-4 relative apart in random trials) -- not chased.  PSNR = 20 log10(value_max / rmse) in double, +inf at rmse = 0
+ *     (the 1e-8 that the reference's online form adds for the baselines is NOT reproduced).  A NaN among a segment's
+ *     errors makes the row's five scores NaN.
+ *   16 launches whatever n_windows, n_segments and n_cand are; a row has the same bits for every n_cand, whatever other
+ *   segments the call holds, on every run.  No host synchronisation.
+ *   JSPSR_EINVAL: a null pointer, n_cand outside 1..8, an empty table or total <= 0, total >= 2^32 (32-bit rank counters),
+ *   sizes that do not fit together.  workspace: jspsr_summary_workspace_bytes(...) bytes (0 = bad arguments), 16-byte
+ *   aligned (JSPSR_EALIGN). */
+int jspsr_scenes_assemble_f32(const float* tiles, const float* base, const float* ramp, float* out, const long long* out_off,
+                              long long out_numel, int S, int n_x, int k, int border_px, int stride, int elev_log,
+                              double elev_min, double elev_max, jspsr_stream_t stream);
+size_t jspsr_summary_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks);
+int jspsr_summary_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                          long long gt_numel, const long long* windows, int n_windows, const long long* segments,
+                          int n_segments, long long total, long long total_chunks, double value_max, float* out,
+                          void* workspace, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _lock = threading.Lock()
 _lib = None
@@ -83,6 +83,9 @@ SIGNATURES = {
     "jspsr_metrics_forward": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p]),
     "jspsr_scores_batch_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_scores_batch_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p]),
+    "jspsr_scenes_assemble_f32": (c_i, [c_p] * 5 + [c_ll] + [c_i] * 6 + [ctypes.c_double, ctypes.c_double, c_p]),
+    "jspsr_summary_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_ll, c_ll]),
+    "jspsr_summary_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_i, c_p, c_i, c_ll, c_ll, ctypes.c_double, c_p, c_p, c_p]),
     "jspsr_adamw_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p]),
     "jspsr_adamw_step_dev": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_p, c_p]),
     "jspsr_optim_workspace_bytes": (ctypes.c_size_t, []),

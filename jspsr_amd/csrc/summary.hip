@@ -1,0 +1,520 @@
+// K12 -- the whole-set validation summary on the device: what the reference's --val path
+// does on the host after the model has run, through GeoTIFF files and numpy:
+//   * save_prediction_to_disk    evaluation/evaluate_utils.py:242-271   clip to [0,1], descale_data, + base
+//   * merge_dem(copyto_add)      utils/utils.py:914-967 (called at :1272)   the feather merge of a scene's 9 / 4 tiles
+//   * summarise_evaluation       utils/utils.py:1238-1356   RMSE, median, NMAD, LE95, PSNR of the errors of ALL scenes
+//                                pooled, for the prediction and every baseline DEM against the ground truth
+// (a) jspsr_scenes_assemble_f32: clamp, de-scale, + base and the feather merge of every scene of a batch in ONE launch,
+//     each mosaic written at its own offset of one pooled buffer.  The expressions of elev_scale_kernel and
+//     tiles_merge_kernel (csrc/tiles.hip), rounded one by one (this file is built with -ffp-contract=off): the bits of
+//     clamp -> descale_data -> + base -> merge_tiles run scene by scene.
+// (b) jspsr_summary_forward: pooled scores of n_cand candidates against one ground truth over a table of pitched
+//     windows grouped into segments.  A streaming selection:
+//       prepare   reads the candidate and the ground truth through the window table, writes e = cand - gt once
+//                 (candidate-major, a segment's windows back to back), folds sum e^2 in double per CHUNK of a segment and
+//                 counts the top digit of the keys of e and |e|;
+//       select    8 bits per pass on the order-preserving keys of csrc/metrics.hip.  Both ranks of a statistic are
+//                 carried as two states whose prefixes may diverge (while they agree, one histogram serves both); the
+//                 median and the LE95 select share each read of e; the |e - median| select follows.
+//     16 launches whatever the number of windows, segments and candidates is: prepare, 4 scans + 3 reads of e for the
+//     median / LE95 digits, 4 + 4 for the MAD.  A workgroup owns one CHUNK of one segment, so every sum is folded in an
+//     order that depends on the segment's own size only: a row has the same bits for every n_cand, for every set of
+//     other segments in the call, on every run.  The workgroups of a row flush their LDS counts into one of up to 16
+//     replicas of the row's counters (hist_replicas): global adds to one address serialise.
+// Departures from the reference (numpy on float32 arrays), see include/jspsr_hip.h: RMSE from an fp64 sum rounded once
+// (not numpy's fp32 pairwise mean); LE95's virtual index in double (numpy 2 forms it in float32 for float32 input); PSNR
+// without the 1e-8 the reference's online form adds for the baselines.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+using namespace jspsr;
+
+constexpr int MT = 256;
+constexpr int UNROLL = 4;
+constexpr int CHUNK = 8192;                   // elements of a segment per workgroup (jspsr_amd/summary.py: CHUNK)
+constexpr int NSTATE = 6;                     // ranks: median lo, hi | LE95 lo, hi | MAD lo, hi
+constexpr int NOUT = 11;                      // RMSE, Median, NMAD, LE95, PSNR, med lo, hi, mad lo, hi, le lo, hi
+constexpr int MAXC = 8;
+constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // segment, h, w, e offset, {offset, pitch} of gt, cand 0..7
+constexpr int SEG_WORDS = 8;                  // e start, n, first chunk, 4 ranks, g (fp64 bits)
+static_assert(CHUNK % (MT * UNROLL) == 0, "a chunk is a whole number of unrolled steps");
+
+__device__ __forceinline__ unsigned order_key(float f) {      // float -> unsigned key with the same ordering (NaNs last)
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// One wave-instruction's worth of histogram increments (csrc/scores.hip: hist_add).  The top digit of a good
+// prediction's errors falls into a handful of bins, and 64 lanes adding to one LDS address serialise: up to two rounds
+// take the bin of the first pending lane, count its lanes with a ballot and let that lane add the count once.
+// Every lane of the wave must arrive (wave-uniform trip counts at the call sites).
+__device__ __forceinline__ void hist_add(unsigned* __restrict__ hist, bool match, unsigned bin) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const unsigned long long act = __ballot(match);
+    if (act == 0ull) return;                                   // wave-uniform
+    const int leader = __ffsll((long long)act) - 1;
+    const unsigned b = (unsigned)__shfl((int)bin, leader, 64);
+    const bool mine = match && bin == b;
+    const unsigned long long m = __ballot(mine);
+    if (lane == leader) atomicAdd(&hist[b], (unsigned)__popcll(m));
+    match = match && !mine;
+  }
+  if (match) atomicAdd(&hist[bin], 1u);
+}
+
+// ---- (a) scene assembly --------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ramp_weight(const float* __restrict__ ramp, int p, int w_l_c, int n_x, int pos, int j) {
+  float w = 1.f;
+  if (pos > 0 && j < p) w = ramp[p - 1 - j];
+  if (pos < n_x - 1 && j >= w_l_c - p) w = ramp[j - (w_l_c - p)];
+  return w;
+}
+
+// network range -> metres: clamp (a NaN stays a NaN, as torch.clamp leaves it), descale_data's two roundings, + base
+__device__ __forceinline__ float to_metres(float t, int elev_log, float lo, float span, float log_span, float base) {
+  const float v = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+  const float d = elev_log ? __fadd_rn(expf(__fmul_rn(v, log_span)), lo) : __fadd_rn(__fmul_rn(v, span), lo);
+  return __fadd_rn(d, base);
+}
+
+__global__ __launch_bounds__(256) void scenes_assemble_kernel(const float* __restrict__ tiles, const float* __restrict__ base,
+                                                             const float* __restrict__ ramp, float* __restrict__ out,
+                                                             const long long* __restrict__ out_off, long long out_numel, int n_x,
+                                                             int k, int b, int s, int w_l_c, int w_h_c, int elev_log, float lo,
+                                                             float span, float log_span) {
+  const int scene = blockIdx.y;
+  const long long total = (long long)w_h_c * w_h_c;
+  const long long off = out_off[scene];
+  if (off < 0 || off + total > out_numel) return;               // a mosaic that leaves the pooled buffer is not written
+  const float* __restrict__ t0 = tiles + (size_t)scene * n_x * n_x * k * k;
+  float* __restrict__ o = out + off;
+  const float bs = base[scene];
+  const int p = w_l_c - s;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int X = (int)(i % w_h_c), Y = (int)(i / w_h_c);
+    if (n_x == 1) {                                             // the 8 m case: the de-scaled tile, uncropped
+      o[i] = to_metres(t0[i], elev_log, lo, span, log_span, bs);
+      continue;
+    }
+    float acc = 0.f;
+    for (int r = 0; r < n_x; ++r) {
+      const int jy = Y - s * r;
+      if (jy < 0 || jy >= w_l_c) continue;
+      const float wy = ramp_weight(ramp, p, w_l_c, n_x, r, jy);
+      for (int c = 0; c < n_x; ++c) {
+        const int jx = X - s * c;
+        if (jx < 0 || jx >= w_l_c) continue;
+        const float wx = ramp_weight(ramp, p, w_l_c, n_x, c, jx);
+        const float t = to_metres(t0[((size_t)(r * n_x + c) * k + b + jy) * k + b + jx], elev_log, lo, span, log_span, bs);
+        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(t, wx), wy));      // (t * wx) * wy, then the add, as tiles_merge_kernel
+      }
+    }
+    o[i] = acc;
+  }
+}
+
+// ---- (b) pooled scores ---------------------------------------------------------------------------------------------
+struct RowState {            // one per (candidate, segment), in device memory; 64 bytes
+  unsigned prefix[NSTATE];   // key bits fixed so far (high bits)
+  unsigned k[NSTATE];        // rank still to find inside the current prefix class (0-based)
+  float center;              // the median, for |e - median|
+  unsigned has_nan;          // the fp64 sum is NaN: a NaN among the errors
+  unsigned pad[2];
+};
+static_assert(sizeof(RowState) == 64, "RowState layout");
+
+struct Buffers {             // by value in the kernel arguments
+  const float* cand[MAXC];
+  long long cand_numel[MAXC];
+  const float* gt;
+  long long gt_numel;
+};
+
+// last row whose word `col` is <= v (rows ascending in that word; row 0 if none is)
+__device__ __forceinline__ int find_row(const long long* __restrict__ tab, int rows, int words, int col, long long v) {
+  int lo = 0, hi = rows - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[(size_t)mid * words + col] <= v) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The chunk of a segment this workgroup owns: segment, its start in e, the element range [lo, hi) inside the segment.
+__device__ __forceinline__ bool my_chunk(const long long* __restrict__ seg, int n_seg, long long total, int reps, int& s, long long& e_start,
+                                         long long& lo, long long& hi, int& rep) {
+  s = find_row(seg, n_seg, SEG_WORDS, 2, (long long)blockIdx.x);
+  const long long* sg = seg + (size_t)s * SEG_WORDS;
+  e_start = sg[0];
+  const long long n = sg[1];
+  const long long ch = (long long)blockIdx.x - sg[2];
+  rep = (int)(ch & (reps - 1));                                  // reps is a power of two
+  lo = ch * CHUNK;
+  if (lo < 0 || lo >= n || e_start < 0 || e_start + n > total) return false;   // a table that leaves the workspace: nothing is touched
+  hi = lo + CHUNK < n ? lo + CHUNK : n;
+  return true;
+}
+
+__global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const long long* __restrict__ win, int n_win,
+                                                            const long long* __restrict__ seg, int n_seg, long long total,
+                                                            long long total_chunks, int reps, float* __restrict__ e_all,
+                                                            double* __restrict__ partial, unsigned* __restrict__ hist) {
+  __shared__ unsigned lh[2][256];
+  __shared__ double red[MT / 64];
+  const int tid = threadIdx.x, c = blockIdx.y;
+  lh[0][tid] = 0u;
+  lh[1][tid] = 0u;
+  int s, rep;
+  long long e_start, lo, hi;
+  if (!my_chunk(seg, n_seg, total, reps, s, e_start, lo, hi, rep)) return;      // workgroup-uniform
+  __syncthreads();
+  const float* __restrict__ cp = B.cand[c];
+  const float* __restrict__ gp = B.gt;
+  const long long cn = B.cand_numel[c], gn = B.gt_numel;
+  float* __restrict__ e = e_all + (size_t)c * total;
+  long long w_lo = 0, w_hi = 0, w_w = 1, goff = 0, gpitch = 0, coff = 0, cpitch = 0;   // the window of the last element
+  bool w_ok = false;
+  double sum = 0.0;
+  for (long long base = lo; base < hi; base += MT * UNROLL) {
+    float err[UNROLL];
+    bool valid[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const long long i = base + u * MT + tid;
+      valid[u] = i < hi;
+      err[u] = 0.f;
+      if (!valid[u]) continue;
+      const long long p = e_start + i;
+      if (p < w_lo || p >= w_hi) {
+        const long long* wr = win + (size_t)find_row(win, n_win, WIN_WORDS, 3, p) * WIN_WORDS;
+        w_w = wr[2];
+        w_lo = wr[3];
+        w_hi = w_lo + wr[1] * w_w;
+        w_ok = wr[0] == s && wr[1] > 0 && w_w > 0;
+        goff = wr[4]; gpitch = wr[5];
+        coff = wr[6 + 2 * c]; cpitch = wr[7 + 2 * c];
+      }
+      float v = __builtin_nanf("");                             // an element no window covers, or a read outside a buffer
+      if (w_ok && p >= w_lo && p < w_hi) {
+        const long long local = p - w_lo;
+        long long y;
+        if (local < 0x100000000ll && w_w < 0x100000000ll) y = (long long)((unsigned)local / (unsigned)w_w);   // the usual case: a 32-bit division
+        else y = local / w_w;
+        const long long x = local - y * w_w;
+        const long long jc = coff + y * cpitch + x, jg = goff + y * gpitch + x;
+        if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) v = __fsub_rn(cp[jc], gp[jg]);
+      }
+      err[u] = v;
+      e[p] = v;
+      sum += (double)v * (double)v;
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      hist_add(lh[0], valid[u], order_key(err[u]) >> 24);
+      hist_add(lh[1], valid[u], order_key(fabsf(err[u])) >> 24);
+    }
+  }
+  const double v = wave_sum(sum);
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int q = 0; q < MT / 64; ++q) t += red[q];
+    partial[(size_t)c * total_chunks + blockIdx.x] = t;
+  }
+  unsigned* hrow = hist + (((size_t)c * n_seg + s) * reps + rep) * NSTATE * 256;
+  if (lh[0][tid]) atomicAdd(&hrow[0 * 256 + tid], lh[0][tid]);
+  if (lh[1][tid]) atomicAdd(&hrow[2 * 256 + tid], lh[1][tid]);
+}
+
+// histograms of byte `pass` of the keys that carry their state's prefix.  group 0: states 0..3 (e and |e|, one read for
+// both); group 1: states 4, 5 (|e - median|).  While the two states of a pair agree on the higher bytes, only the lower
+// one is counted (the scan reads it for both).
+__global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restrict__ e_all, const long long* __restrict__ seg, int n_seg,
+                                                           long long total, int reps, int group, int pass, const RowState* __restrict__ st,
+                                                           unsigned* __restrict__ hist) {
+  __shared__ unsigned lh[4][256];
+  const int tid = threadIdx.x, c = blockIdx.y;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) lh[q][tid] = 0u;
+  int s, rep;
+  long long e_start, lo, hi;
+  if (!my_chunk(seg, n_seg, total, reps, s, e_start, lo, hi, rep)) return;
+  __syncthreads();
+  const size_t row = (size_t)c * n_seg + s;
+  const RowState* my = st + row;
+  const int shift = pass * 8;
+  const unsigned himask = pass == 3 ? 0u : (0xffffffffu << (shift + 8));
+  const int q0 = group ? 4 : 0;
+  const unsigned pa0 = my->prefix[q0] & himask, pa1 = my->prefix[q0 + 1] & himask;
+  const unsigned pb0 = group ? 0u : my->prefix[2] & himask, pb1 = group ? 0u : my->prefix[3] & himask;
+  const bool split_a = pa0 != pa1, split_b = pb0 != pb1;      // workgroup-uniform
+  const float center = my->center;
+  const float* __restrict__ e = e_all + (size_t)c * total + e_start;
+  for (long long base = lo; base < hi; base += MT * UNROLL) {
+    float x[UNROLL];
+    bool valid[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const long long i = base + u * MT + tid;
+      valid[u] = i < hi;
+      x[u] = valid[u] ? e[i] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const unsigned ka = order_key(group ? fabsf(__fsub_rn(x[u], center)) : x[u]);
+      const unsigned bin_a = (ka >> shift) & 0xffu;
+      hist_add(lh[0], valid[u] && (ka & himask) == pa0, bin_a);
+      if (split_a) hist_add(lh[1], valid[u] && (ka & himask) == pa1, bin_a);
+      if (!group) {
+        const unsigned kb = order_key(fabsf(x[u]));
+        const unsigned bin_b = (kb >> shift) & 0xffu;
+        hist_add(lh[2], valid[u] && (kb & himask) == pb0, bin_b);
+        if (split_b) hist_add(lh[3], valid[u] && (kb & himask) == pb1, bin_b);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned* hrow = hist + (row * reps + rep) * NSTATE * 256;
+  const int nq = group ? 2 : 4;
+  for (int q = 0; q < nq; ++q)
+    if (lh[q][tid]) atomicAdd(&hrow[(q0 + q) * 256 + tid], lh[q][tid]);
+}
+
+// One workgroup per (candidate, segment), a wave per state: find the bin holding the state's rank, fix its byte, reduce
+// the rank; clear the row's histograms.  init: the first scan of a call -- the states come from the segment table and
+// RMSE / PSNR from the chunk sums, folded in chunk order.  After byte 0 the keys are complete: the scores are written.
+__global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restrict__ partial, long long total_chunks,
+                                                         const long long* __restrict__ seg, int n_seg, int reps, int group,
+                                                         int pass, int init, double value_max, RowState* __restrict__ st,
+                                                         unsigned* __restrict__ hist, float* __restrict__ out) {
+  __shared__ RowState cur;
+  __shared__ double red[MT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t row = blockIdx.x;
+  const int c = (int)(row / n_seg), s = (int)(row % n_seg);
+  const long long* sg = seg + (size_t)s * SEG_WORDS;
+  const long long n = sg[1];
+  unsigned* hrow = hist + row * reps * NSTATE * 256;           // the row's `reps` replicas, back to back
+  float* o = out + row * NOUT;
+  if (init) {
+    if (tid == 0) {
+      for (int q = 0; q < NSTATE; ++q) cur.prefix[q] = 0u;
+      cur.k[0] = cur.k[4] = (unsigned)sg[3];
+      cur.k[1] = cur.k[5] = (unsigned)sg[4];
+      cur.k[2] = (unsigned)sg[5];
+      cur.k[3] = (unsigned)sg[6];
+      cur.center = 0.f;
+      cur.has_nan = 0u;
+      cur.pad[0] = cur.pad[1] = 0u;
+    }
+    const long long nchunks = (n + CHUNK - 1) / CHUNK;
+    const double* src = partial + (size_t)c * total_chunks + sg[2];
+    double a = 0.0;
+    if (sg[2] >= 0 && sg[2] + nchunks <= total_chunks)
+      for (long long j = tid; j < nchunks; j += MT) a += src[j];
+    a = wave_sum(a);
+    if (lane == 0) red[wave] = a;
+  } else if (tid < (int)(sizeof(RowState) / 4)) {
+    reinterpret_cast<unsigned*>(&cur)[tid] = reinterpret_cast<const unsigned*>(st + row)[tid];
+  }
+  __syncthreads();
+  if (init && tid == 0) {
+    double t = 0.0;
+    for (int q = 0; q < MT / 64; ++q) t += red[q];
+    const double rm = sqrt(t / (double)n);
+    o[0] = (float)rm;
+    o[4] = (float)(20.0 * log10(value_max / rm));               // +inf at rm == 0; NaN stays NaN
+    cur.has_nan = (t != t) ? 1u : 0u;
+  }
+  // a wave per state
+  const int q = (group ? 4 : 0) + wave, ql = q & ~1;
+  const bool active = group ? wave < 2 : true;
+  const int shift = pass * 8;
+  const unsigned himask = pass == 3 ? 0u : (0xffffffffu << (shift + 8));
+  unsigned new_prefix = 0u, new_k = 0u;
+  bool found = false;
+  if (active) {
+    const unsigned prefix = cur.prefix[q], k = cur.k[q];
+    const bool same = ((prefix ^ cur.prefix[ql]) & himask) == 0u;       // counted once, under the pair's lower state
+    const unsigned* h = hrow + (same ? ql : q) * 256 + 4 * lane;         // lane l owns bins 4l .. 4l+3
+    unsigned c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u;
+    for (int r = 0; r < reps; ++r) {
+      const uint4 v = *reinterpret_cast<const uint4*>(h + (size_t)r * NSTATE * 256);
+      c0 += v.x; c1 += v.y; c2 += v.z; c3 += v.w;
+    }
+    const unsigned own = c0 + c1 + c2 + c3;
+    unsigned incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = (unsigned)__shfl_up((int)incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    const unsigned excl = incl - own;
+    if (k >= excl && k < incl) {                                 // exactly one lane: the counts sum to more than k
+      unsigned run = excl;
+      int b = 0;
+      if (k >= run + c0) { run += c0; b = 1;
+        if (k >= run + c1) { run += c1; b = 2;
+          if (k >= run + c2) { run += c2; b = 3; } } }
+      new_k = k - run;
+      new_prefix = prefix | ((unsigned)(4 * lane + b) << shift);
+      found = true;
+    }
+  }
+  __syncthreads();                                               // every wave has read the states and its histogram
+  if (found) { cur.prefix[q] = new_prefix; cur.k[q] = new_k; }
+  {                                                              // clear what this group's passes count into: states 0..3 or 4, 5
+    const int first = group ? 4 : 0, quads = (group ? 2 : 4) * 64; // uint4 per replica
+    for (int i = tid; i < reps * quads; i += MT)
+      reinterpret_cast<uint4*>(hrow + ((size_t)(i / quads) * NSTATE + first) * 256)[i % quads] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  if (pass == 0 && tid == 0) {
+    const float nanv = __builtin_nanf("");
+    const bool bad = cur.has_nan != 0u;
+    if (!group) {
+      const float m0 = key_value(cur.prefix[0]), m1 = key_value(cur.prefix[1]);
+      const float l0 = key_value(cur.prefix[2]), l1 = key_value(cur.prefix[3]);
+      const float med = __fmul_rn(__fadd_rn(m0, m1), 0.5f);      // np.median of a float32 array: mean of the two middle elements
+      double g;
+      const long long gb = sg[7];
+      __builtin_memcpy(&g, &gb, 8);
+      const float le = (float)((double)l0 + ((double)l1 - (double)l0) * g);
+      cur.center = med;
+      o[1] = bad ? nanv : med;
+      o[3] = bad ? nanv : le;
+      o[5] = m0; o[6] = m1; o[9] = l0; o[10] = l1;
+      if (bad) { o[0] = nanv; o[4] = nanv; }
+    } else {
+      const float d0 = key_value(cur.prefix[4]), d1 = key_value(cur.prefix[5]);
+      const float mad = __fmul_rn(__fadd_rn(d0, d1), 0.5f);
+      o[2] = bad ? nanv : (float)(1.4826 * (double)mad);
+      o[7] = d0; o[8] = d1;
+    }
+  }
+  __syncthreads();
+  if (tid < (int)(sizeof(RowState) / 4)) reinterpret_cast<unsigned*>(st + row)[tid] = reinterpret_cast<const unsigned*>(&cur)[tid];
+}
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// Replicas of a row's histograms.  Every workgroup of a row ends in global adds to the row's 256 counters per state; to one
+// address they serialise, and a 4096 x 4096 segment has 2048 workgroups.  Chunk c of a segment adds to replica c % reps,
+// the scan sums the replicas: integer counts, so the result does not depend on reps.  A power of two, at most 16, one per
+// 64 chunks of the call, and at most 64 MiB of counters.
+int hist_replicas(size_t rows, long long total_chunks) {
+  int r = 1;
+  while (r < 16 && (long long)r * 64 < total_chunks && rows * (size_t)(2 * r) * NSTATE * 256 * sizeof(unsigned) <= ((size_t)64 << 20)) r *= 2;
+  return r;
+}
+
+bool sizes_ok(int n_cand, int n_segments, long long total, long long total_chunks) {
+  if (n_cand < 1 || n_cand > MAXC || n_segments <= 0 || total <= 0 || total >= 0x100000000ll) return false;
+  // every segment holds at least one element and ends in at most one partly filled chunk
+  return n_segments <= total && total_chunks >= (total + CHUNK - 1) / CHUNK && total_chunks <= total / CHUNK + n_segments &&
+         total_chunks < 0x7fffffffll;
+}
+
+}  // namespace
+
+extern "C" int jspsr_scenes_assemble_f32(const float* tiles, const float* base, const float* ramp, float* out, const long long* out_off,
+                                         long long out_numel, int S, int n_x, int k, int border_px, int stride, int elev_log,
+                                         double elev_min, double elev_max, jspsr_stream_t stream) {
+  if (!tiles || !base || !out || !out_off || out_numel <= 0 || S <= 0 || n_x <= 0 || k <= 0 || border_px < 0)
+    return fail(JSPSR_EINVAL, "scenes_assemble: bad arguments");
+  if (S > 65535) return fail(JSPSR_EINVAL, "scenes_assemble: S = %d exceeds the grid (65535)", S);
+  if (!(elev_max > elev_min)) return fail(JSPSR_EINVAL, "scenes_assemble: elev_max must exceed elev_min");
+  int w_l_c = k, w_h_c = k, b = 0, p = 0;
+  if (n_x > 1) {
+    b = border_px;
+    w_l_c = k - 2 * b;
+    w_h_c = stride * (n_x - 1) + w_l_c;
+    p = w_l_c - stride;
+    if (w_l_c <= 0 || stride <= 0 || p < 0 || (p > 0 && !ramp) || p > w_l_c) return fail(JSPSR_EINVAL, "scenes_assemble: bad cover");
+  }
+  const long long total = (long long)w_h_c * w_h_c;
+  long long blocks = (total + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  // the constants as jspsr_elev_scale_f32 forms them: the reference's Python doubles, rounded once to fp32
+  hipLaunchKernelGGL(scenes_assemble_kernel, dim3((unsigned)blocks, S), dim3(256), 0, static_cast<hipStream_t>(stream), tiles, base, ramp,
+                     out, out_off, out_numel, n_x, k, b, stride, w_l_c, w_h_c, elev_log ? 1 : 0, (float)elev_min,
+                     (float)(elev_max - elev_min), (float)log(elev_max - elev_min));
+  return check_launch("scenes_assemble");
+}
+
+extern "C" size_t jspsr_summary_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks) {
+  if (!sizes_ok(n_cand, n_segments, total, total_chunks)) return 0;
+  const size_t rows = (size_t)n_cand * n_segments;
+  return up16((size_t)n_cand * total * sizeof(float)) + up16((size_t)n_cand * total_chunks * sizeof(double)) +
+         rows * hist_replicas(rows, total_chunks) * NSTATE * 256 * sizeof(unsigned) + rows * sizeof(RowState) + 64;
+}
+
+extern "C" int jspsr_summary_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                                     long long gt_numel, const long long* windows, int n_windows, const long long* segments,
+                                     int n_segments, long long total, long long total_chunks, double value_max, float* out,
+                                     void* workspace, jspsr_stream_t stream) {
+  if (n_cand < 1 || n_cand > MAXC) return fail(JSPSR_EINVAL, "summary_forward: n_cand = %d is outside 1..%d", n_cand, MAXC);
+  if (!cands || !cand_numel || !gt || !windows || !segments || !out || !workspace) return fail(JSPSR_EINVAL, "summary_forward: null pointer");
+  if (n_windows <= 0 || n_segments <= 0 || total <= 0 || gt_numel <= 0) return fail(JSPSR_EINVAL, "summary_forward: empty window or segment table");
+  if (total >= 0x100000000ll) return fail(JSPSR_EINVAL, "summary_forward: %lld pooled elements, the rank counters hold fewer than 2^32", total);
+  if (n_windows < n_segments || !sizes_ok(n_cand, n_segments, total, total_chunks))
+    return fail(JSPSR_EINVAL, "summary_forward: %d windows, %d segments, %lld elements and %lld chunks do not fit together", n_windows,
+                n_segments, total, total_chunks);
+  if ((long long)n_cand * n_segments > 0x7fffffffll) return fail(JSPSR_EINVAL, "summary_forward: too many rows");
+  Buffers B;
+  for (int c = 0; c < MAXC; ++c) {
+    B.cand[c] = c < n_cand ? cands[c] : nullptr;
+    B.cand_numel[c] = c < n_cand ? cand_numel[c] : 0;
+    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "summary_forward: candidate %d is null or empty", c);
+    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "summary_forward: candidate %d not 4-byte aligned", c);
+  }
+  B.gt = gt;
+  B.gt_numel = gt_numel;
+  if (!aligned4(gt) || !aligned4(out)) return fail(JSPSR_EALIGN, "summary_forward: tensors not 4-byte aligned");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "summary_forward: workspace not 16-byte aligned");
+  const size_t rows = (size_t)n_cand * n_segments;
+  char* ws = static_cast<char*>(workspace);
+  float* e = reinterpret_cast<float*>(ws);
+  size_t off = up16((size_t)n_cand * total * sizeof(float));
+  double* partial = reinterpret_cast<double*>(ws + off);
+  off += up16((size_t)n_cand * total_chunks * sizeof(double));
+  unsigned* hist = reinterpret_cast<unsigned*>(ws + off);
+  const int reps = hist_replicas(rows, total_chunks);
+  const size_t hist_bytes = rows * reps * NSTATE * 256 * sizeof(unsigned);
+  off += hist_bytes;
+  RowState* st = reinterpret_cast<RowState*>(ws + off);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(hist, 0, hist_bytes, s) != hipSuccess)
+    return fail(JSPSR_EINVAL, "summary_forward: clearing the histograms failed: %s", hipGetErrorString(hipGetLastError()));
+  const dim3 grid((unsigned)total_chunks, n_cand);
+  hipLaunchKernelGGL(summary_prepare_kernel, grid, dim3(MT), 0, s, B, windows, n_windows, segments, n_segments, total, total_chunks, reps,
+                     e, partial, hist);
+  if (int err = check_launch("summary_prepare")) return err;
+  for (int group = 0; group < 2; ++group) {
+    for (int pass = 3; pass >= 0; --pass) {
+      const int init = group == 0 && pass == 3;                  // the top digit of e and |e| was counted by the first pass
+      if (!init) {
+        hipLaunchKernelGGL(summary_select_kernel, grid, dim3(MT), 0, s, e, segments, n_segments, total, reps, group, pass, st, hist);
+        if (int err = check_launch("summary_select")) return err;
+      }
+      hipLaunchKernelGGL(summary_scan_kernel, dim3((unsigned)rows), dim3(MT), 0, s, partial, total_chunks, segments, n_segments, reps,
+                         group, pass, init, value_max, st, hist, out);
+      if (int err = check_launch("summary_select")) return err;
+    }
+  }
+  return JSPSR_OK;
+}

@@ -7,8 +7,9 @@ runs the model and one meter object per score on ONE tile per step (valid_batch_
 `.item()`; here a batch of any size is scored by one launch (`metrics.batch_scores`, K10), the rows stay in a device
 table, and a pass ends in one device-to-host copy.
 
-Left out: plotting, GeoTIFF output, summarise_evaluation, the skimage and richdem packages and the bicubic resize of a
-smaller input.  (EarlyStopper is in jspsr_amd/train.py.)
+Left out: plotting, GeoTIFF output, the skimage and richdem packages and the bicubic resize of a smaller input.
+(EarlyStopper is in jspsr_amd/train.py; the scene mosaics and summarise_evaluation's table in jspsr_amd/summary.py, fed
+through `evaluate(..., collector=)`.)
 """
 from __future__ import annotations
 
@@ -215,7 +216,7 @@ def _sample_additive(criterion):
 
 
 @torch.no_grad()
-def evaluate(model, batches, criterion, meter, model_name, input_data, compare_input=False):
+def evaluate(model, batches, criterion, meter, model_name, input_data, compare_input=False, collector=None):
     """eval_model (evaluate_utils.py:274-357) without plotting and disk output: `model.eval()`, no gradients, and for each
     batch of `batches` (e.g. `data.TileCropBatches`, any batch size): `criterion.reset()`, `data.batch_pair`, the
     forward, the criterion, `meter.update`.  `meter` is reset first (the reference builds a new one per call).
@@ -234,7 +235,10 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
     depend on it.  A criterion that holds BerHu is therefore fed one sample at a time (all its terms, so that Total stays
     the weighted sum of what is reported); so is a criterion of a type this module does not know.
 
-    Loss values and scores stay on the device until the end: the pass synchronises once (one device-to-host copy)."""
+    Loss values and scores stay on the device until the end: the pass synchronises once (one device-to-host copy).
+
+    collector: e.g. a `summary.ScenePredictions`; its `add(pred, meta)` is called after each forward (the scene mosaics in
+    metres for `summary.summarise`, the whole-set table of summarise_evaluation).  None (the default) changes nothing."""
     model.eval()
     meter.reset()
     meter_in = meter.clone() if compare_input else None
@@ -244,6 +248,8 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
         criterion.reset()
         inputs, gt, _base, meta = batch_pair(batch, model_name, input_data)
         pred = model(*inputs)
+        if collector is not None:
+            collector.add(pred, meta)
         B = gt.size(0)
         spans = [(0, B)] if additive else [(i, i + 1) for i in range(B)]
         for lo, hi in spans:

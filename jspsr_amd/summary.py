@@ -1,0 +1,382 @@
+"""The whole-set validation summary on the device (K12, csrc/summary.hip): scene mosaics in metres and the pooled scores
+the reference publishes.
+
+Restates the last stage of the reference's `--val` path: `save_prediction_to_disk` (evaluation/evaluate_utils.py:242-271:
+clip to [0,1], `descale_data`, `+ base`), `merge_dem(..., p.val_border, method=copyto_add)` (utils/utils.py:914-967,
+called at :1272) and `summarise_evaluation` (utils/utils.py:970-1368), which scores the whole validation set twice:
+"offline", pooled over all pixels of all scenes (the accuracy table of its ReadMe), and "online", per scene and averaged;
+both for the prediction and for every baseline DEM against the ground truth.
+
+    c = ScenePredictions(scenes, 128, 9, border=0.05)
+    evaluate(model, TileCropBatches(scenes, 50, 128, 9), criterion, meter, "JSPSR", input_data, collector=c)
+    table = summarise(scenes, c, baselines={"COP30": "lr_dem"}, value_max=933, border=0.05, patch_size=128)
+
+The pooled numbers differ from the per-tile meters of `metrics.batch_scores` (K10) by definition: numpy's median is the
+mean of the two middle elements (torch.median: the lower one) and numpy's percentile interpolates (kthvalue: one element).
+Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K12.  GeoTIFF output, plotting,
+`upscale_dem` and the richdem slope stay out.
+
+Device fp32 tensors go through the HIP kernels; host tensors through the same formulas as numpy / torch operators.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from math import floor
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import metrics as M
+from . import tiles as T
+
+CHUNK = 8192                  # csrc/summary.hip: elements of a segment per workgroup
+MAX_CANDIDATES = 8
+COLUMNS = ("RMSE", "Median", "NMAD", "LE95", "PSNR")
+ROW = COLUMNS + ("median_lo", "median_hi", "mad_lo", "mad_hi", "le95_lo", "le95_hi")
+_WIN_WORDS = 4 + 2 * (1 + MAX_CANDIDATES)
+_SEG_WORDS = 8
+
+
+def segment_ranks(n: int):
+    """The 0-based ranks and the weight every order statistic of a segment of n elements is read at:
+    (median lo, median hi, LE95 lo, LE95 hi, g).  Median: the elements of ranks (n - 1) // 2 and n // 2 (np.median).
+    LE95: v = 0.95 (n - 1) in double, l = floor(v), g = v - l, the elements of ranks l and min(l + 1, n - 1), value
+    lo + (hi - lo) g (np.percentile(., 95) on a float64 array).  The one place these are formed: the device reads them from
+    the segment table."""
+    if n < 1:
+        raise ValueError(f"segment_ranks: n = {n}")
+    v = 0.95 * (n - 1)
+    lo = int(floor(v))
+    return (n - 1) // 2, n // 2, lo, min(lo + 1, n - 1), v - lo
+
+
+def _row_host(e: np.ndarray, value_max: float) -> np.ndarray:
+    """One output row from a float32 error vector, as numpy operators."""
+    n = e.size
+    m0, m1, l0, l1, g = segment_ranks(n)
+    with np.errstate(all="ignore"):
+        srt = np.sort(e)
+        med = np.float32((srt[m0] + srt[m1]) * np.float32(0.5))
+        d = np.sort(np.abs(e - med))
+        mad = np.float32((d[m0] + d[m1]) * np.float32(0.5))
+        a = np.sort(np.abs(e))
+        le = np.float32(float(a[l0]) + (float(a[l1]) - float(a[l0])) * g)
+        rm = math.sqrt(float(np.sum(e.astype(np.float64) ** 2)) / n)
+        psnr = 20.0 * np.log10(np.float64(value_max) / np.float64(rm))          # +inf at rm == 0
+        row = np.array([rm, med, np.float32(1.4826 * float(mad)), le, psnr, srt[m0], srt[m1], d[m0], d[m1], a[l0], a[l1]],
+                       dtype=np.float32)
+    if np.isnan(e).any():
+        row[:5] = np.nan
+    return row
+
+
+def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], n_segments: int, value_max: float):
+    """The raw table call.  cands: 1..8 flat fp32 buffers, gt one, all on one device; windows: (segment, h, w, (gt offset,
+    gt pitch), [(offset, pitch) per candidate]) in elements -- crops are read in place; a segment pools its windows in the
+    order given.  -> (n_cand, n_segments, 11) fp32 tensor, columns `ROW`, on the buffers' device.  No host
+    synchronisation on the device path (K12(b): one call, 16 launches)."""
+    n_cand = len(cands)
+    if not 1 <= n_cand <= MAX_CANDIDATES:
+        raise ValueError(f"pooled_rows: {n_cand} candidates, 1..{MAX_CANDIDATES} are taken")
+    bufs = [gt] + list(cands)
+    if any(b.dtype != torch.float32 or b.dim() != 1 or not b.is_contiguous() for b in bufs):
+        raise ValueError("pooled_rows: flat contiguous float32 buffers")
+    if len({b.device for b in bufs}) != 1:
+        raise ValueError("pooled_rows: buffers on several devices")
+    if n_segments < 1 or not windows:
+        raise ValueError("pooled_rows: no windows or no segments")
+    order = sorted(range(len(windows)), key=lambda i: windows[i][0])          # stable: a segment keeps its window order
+    seg_n = [0] * n_segments
+    for sg, h, w, g_, cs in windows:
+        if not 0 <= sg < n_segments:
+            raise ValueError(f"pooled_rows: segment {sg} of {n_segments}")
+        if h <= 0 or w <= 0:
+            raise ValueError(f"pooled_rows: an empty window ({h} x {w})")
+        if len(cs) != n_cand:
+            raise ValueError(f"pooled_rows: a window names {len(cs)} candidates, {n_cand} were given")
+        for (off, pitch), b in zip([g_] + list(cs), bufs):
+            if off < 0 or pitch < 0 or off + (h - 1) * pitch + w > b.numel():
+                raise ValueError(f"pooled_rows: window {h} x {w} at {off} (pitch {pitch}) leaves its buffer of {b.numel()}")
+        seg_n[sg] += h * w
+    if min(seg_n) == 0:
+        raise ValueError("pooled_rows: a segment without windows")
+    total = sum(seg_n)
+    if gt.is_cuda:
+        return _pooled_device(cands, gt, [windows[i] for i in order], seg_n, total, value_max)
+    out = np.empty((n_cand, n_segments, len(ROW)), dtype=np.float32)
+    g_np = gt.numpy()
+    for c, cand in enumerate(cands):
+        c_np = cand.numpy()
+        parts = [[] for _ in range(n_segments)]
+        for i in order:
+            sg, h, w, (go, gp), cs = windows[i]
+            co, cp = cs[c]
+            rows = np.arange(h)[:, None]
+            cols = np.arange(w)[None, :]
+            parts[sg].append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
+        for sg in range(n_segments):
+            out[c, sg] = _row_host(np.concatenate(parts[sg]).astype(np.float32, copy=False), value_max)
+    return torch.from_numpy(out)
+
+
+def _pooled_device(cands, gt, windows, seg_n, total, value_max):
+    n_cand, n_seg, n_win = len(cands), len(seg_n), len(windows)
+    tab = np.zeros(n_win * _WIN_WORDS + n_seg * _SEG_WORDS, dtype=np.int64)
+    win = tab[:n_win * _WIN_WORDS].reshape(n_win, _WIN_WORDS)
+    seg = tab[n_win * _WIN_WORDS:].reshape(n_seg, _SEG_WORDS)
+    e_off = 0
+    for i, (sg, h, w, (go, gp), cs) in enumerate(windows):
+        win[i, :6] = (sg, h, w, e_off, go, gp)
+        for c, (co, cp) in enumerate(cs):
+            win[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
+        e_off += h * w
+    start = chunk = 0
+    for sg, n in enumerate(seg_n):
+        m0, m1, l0, l1, g = segment_ranks(n)
+        seg[sg] = (start, n, chunk, m0, m1, l0, l1, np.float64(g).view(np.int64))
+        start += n
+        chunk += (n + CHUNK - 1) // CHUNK
+    lib = _lib.load()
+    nbytes = lib.jspsr_summary_workspace_bytes(n_cand, n_seg, total, chunk)
+    if nbytes == 0:
+        raise ValueError(f"pooled_rows: {n_cand} candidates, {n_seg} segments, {total} pooled elements: not a size K12 takes "
+                         "(fewer than 2^32 elements per call)")
+    dev = gt.device
+    host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)        # one stream-ordered upload, never written again
+    host.numpy()[...] = tab
+    table = host.to(dev, non_blocking=True)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((n_cand, n_seg, len(ROW)), dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
+    numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+    _lib.check(lib.jspsr_summary_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), table.data_ptr(), n_win,
+                                         table.data_ptr() + n_win * _WIN_WORDS * 8, n_seg, total, chunk, float(value_max),
+                                         out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+               "jspsr_summary_forward")
+    return out
+
+
+def scores_pooled(cands, gt, segments=None, value_max: float = 1.0):
+    """Pooled scores of equal-shape tensors, e.g. a 4096 x 4096 scene from `tiling.sharded_forward_owned` against its
+    target.  cands: a tensor or a list of up to 8, each of gt's shape (..., H, W), fp32 metres.  segments: None pools
+    everything into one segment; otherwise a list of segments, each a list of windows (plane, y0, x0, h, w) over the
+    tensors flattened to (planes, H, W).  value_max: the numerator of PSNR = 20 log10(value_max / RMSE).
+    -> (n_cand, n_segments, 11) fp32 tensor on the inputs' device, columns `ROW`; no host synchronisation."""
+    cands = [cands] if isinstance(cands, torch.Tensor) else list(cands)
+    if gt.dim() < 2 or any(c.shape != gt.shape for c in cands):
+        raise ValueError(f"scores_pooled: equal (..., H, W) tensors, got {[tuple(c.shape) for c in cands]} / {tuple(gt.shape)}")
+    H, W = gt.shape[-2:]
+    planes = gt.numel() // (H * W) if H * W else 0
+    if segments is None:
+        segments = [[(p, 0, 0, H, W) for p in range(planes)]]
+    windows = []
+    for sg, wins in enumerate(segments):
+        for p, y0, x0, h, w in wins:
+            if not (0 <= p < planes and 0 <= y0 and 0 <= x0 and y0 + h <= H and x0 + w <= W):
+                raise ValueError(f"scores_pooled: window {(p, y0, x0, h, w)} leaves the ({planes}, {H}, {W}) tensor")
+            at = ((p * H + y0) * W + x0, W)
+            windows.append((sg, h, w, at, [at] * len(cands)))
+    flat = [t.detach().float().contiguous().reshape(-1) for t in cands]
+    return pooled_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, len(segments), value_max)
+
+
+class ScenePredictions:
+    """Collects the predictions of a `data.TileCropBatches(scenes, B, patch_size, patches_per_image)` pass as metre mosaics.
+
+    add(pred, meta): pred (B, 1, k, k) in the network's range with the batch's meta, any batch size, scenes possibly split
+    across batches, in the pass's order.  Whole scenes are assembled by ONE launch per call (K12(a): clamp, de-scale,
+    + base, feather merge) into one pooled device buffer; the tiles of a scene still incomplete wait for the next call.
+    With `patch_size` not smaller than the scenes (the 8 m set-up, one patch per image) the raster is the de-scaled tile,
+    uncropped.  All scenes must be square and of one size (one cover per launch).
+    rasters(): {scene id: (h, w) float32 numpy array} with one device-to-host copy -- what the reference writes to GeoTIFF.
+    `buffer` (flat fp32), `offsets` (per scene, elements) and `shape` describe the pool for `summarise`."""
+
+    def __init__(self, scenes, patch_size: int, patches_per_image: int, border: float = 0.0):
+        shapes = set(scenes.shapes)
+        if len(shapes) != 1 or scenes.shapes[0][0] != scenes.shapes[0][1]:
+            raise ValueError(f"ScenePredictions: square scenes of one size, got {sorted(shapes)}")
+        self.scenes, self.k, self.n, self.border = scenes, int(patch_size), int(patches_per_image), float(border)
+        full = scenes.shapes[0][0]
+        self.full = full
+        if self.k >= full:                                    # no crop (data_utils.py:108-109): one k = full tile per scene
+            if self.n != 1:
+                raise NotImplementedError(f"ScenePredictions: uncropped scenes with {self.n} patches per image (1 is built)")
+            self.k = self.side = full
+            self.n_x, self.b, self.stride = 1, 0, 0
+        else:
+            self.n_x = math.isqrt(self.n)
+            if self.n_x * self.n_x != self.n or self.n_x not in (2, 3):
+                raise NotImplementedError(f"n {self.n} is not 9 or 4")
+            self.b = int(self.k * self.border)
+            w_l_c = self.k - 2 * self.b
+            self.side = full - 2 * self.b
+            self.stride, n2 = T.get_tile(self.side, w_l_c)
+            if n2 != self.n or self.stride != T.get_tile(full, self.k, self.n)[0]:
+                raise ValueError(f"ScenePredictions: {self.n} tiles of {self.k} do not cover a {full}-pixel scene")
+        self.shape = (self.side, self.side)
+        S, dev = len(scenes), scenes.device
+        self.offsets = [i * self.side * self.side for i in range(S)]
+        self.buffer = torch.empty(S * self.side * self.side, dtype=torch.float32, device=dev)
+        self._base = torch.tensor([float(np.float32(b)) for b in scenes.base], dtype=torch.float32, device=dev)
+        self._off = torch.tensor(self.offsets, dtype=torch.int64, device=dev)
+        p = self.k - 2 * self.b - self.stride if self.n_x > 1 else 0
+        self._ramp = (torch.linspace(1, 0, p + 2, dtype=torch.float64)[1:-1].to(device=dev, dtype=torch.float32).contiguous()
+                      if p > 0 else None)
+        self.reset()
+
+    def reset(self):
+        self._pending, self._tiles = None, 0
+
+    @property
+    def complete(self) -> bool:
+        return self._tiles == len(self.scenes) * self.n
+
+    @torch.no_grad()
+    def add(self, pred: torch.Tensor, meta=None):
+        if pred.dim() != 4 or pred.shape[1] != 1 or pred.shape[2] != self.k or pred.shape[3] != self.k:
+            raise ValueError(f"ScenePredictions.add: (B, 1, {self.k}, {self.k}) predictions, got {tuple(pred.shape)}")
+        if pred.device != self.buffer.device:
+            raise ValueError(f"ScenePredictions.add: predictions on {pred.device}, the scenes on {self.buffer.device}")
+        B = pred.shape[0]
+        if self._tiles + B > len(self.scenes) * self.n:
+            raise ValueError("ScenePredictions.add: more tiles than the scenes hold")
+        if meta is not None:
+            if len(meta) != B:
+                raise ValueError(f"ScenePredictions.add: {len(meta)} meta entries for a batch of {B}")
+            for j, m in enumerate(meta):
+                want = self.scenes.ids[(self._tiles + j) // self.n]
+                if isinstance(m, dict) and "id" in m and str(m["id"]) != want:
+                    raise ValueError(f"ScenePredictions.add: tile {self._tiles + j} belongs to scene {want}, its meta says {m['id']}")
+        t = pred.detach().float()
+        if self._pending is not None:
+            t = torch.cat((self._pending, t))
+        s0 = (self._tiles - (0 if self._pending is None else self._pending.shape[0])) // self.n
+        whole = t.shape[0] // self.n
+        self._tiles += B
+        if whole:
+            self._assemble(t[:whole * self.n].contiguous(), s0, whole)
+        rest = t[whole * self.n:]
+        self._pending = rest.clone() if rest.shape[0] else None
+
+    def _assemble(self, t, s0, S):
+        sc = self.scenes
+        if t.is_cuda:
+            _lib.check(_lib.load().jspsr_scenes_assemble_f32(
+                t.data_ptr(), self._base.data_ptr() + 4 * s0, self._ramp.data_ptr() if self._ramp is not None else None,
+                self.buffer.data_ptr(), self._off.data_ptr() + 8 * s0, self.buffer.numel(), S, self.n_x, self.k, self.b, self.stride,
+                int(bool(sc.elev_log)), float(sc.elev_min), float(sc.elev_max), torch.cuda.current_stream(t.device).cuda_stream),
+                "jspsr_scenes_assemble_f32")
+            return
+        for i in range(S):                                     # the composition itself, as torch operators
+            m = compose_scene(t[i * self.n:(i + 1) * self.n], self._base[s0 + i], self.full, self.border, sc.elev_min, sc.elev_max,
+                              sc.elev_log)
+            o = self.offsets[s0 + i]
+            self.buffer[o:o + m.numel()] = m.reshape(-1)
+
+    def rasters(self) -> dict:
+        if not self.complete:
+            raise ValueError(f"ScenePredictions.rasters: {self._tiles} of {len(self.scenes) * self.n} tiles were added")
+        host = self.buffer.cpu().numpy()
+        n = self.side * self.side
+        return {sid: host[o:o + n].reshape(self.shape).copy() for sid, o in zip(self.scenes.ids, self.offsets)}
+
+
+def compose_scene(tiles, base, full, border, elev_min, elev_max, elev_log):
+    """One scene the way the package's own steps give it: clamp -> `metrics.descale_data` -> + base -> `tiles.merge_tiles`
+    (a single uncropped tile is returned de-scaled).  tiles (n, 1, k, k) in the network's range; base a number or a 0-d
+    fp32 tensor.  K12(a) gives these bits for all scenes of a batch in one launch."""
+    m = M.descale_data(tiles.float().clamp(0.0, 1.0), elev_min, elev_max, elev_log) + base
+    if tiles.shape[0] == 1 and tiles.shape[-1] >= full:
+        return m[0, 0]
+    return T.merge_tiles(m, full, border)
+
+
+def store_layout(scenes, rasters, name="baseline"):
+    """A list of (h, w) metre rasters -> one flat fp32 buffer in the store's layout, uploaded once."""
+    if len(rasters) != len(scenes):
+        raise ValueError(f"summarise: baseline {name!r} has {len(rasters)} rasters, the store {len(scenes)} scenes")
+    flat = []
+    for i, r in enumerate(rasters):
+        a = r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else np.asarray(r)
+        a = a.reshape(a.shape[:2]) if a.ndim == 3 and a.shape[2] == 1 else a
+        if tuple(a.shape) != tuple(scenes.shapes[i]):
+            raise ValueError(f"summarise: baseline {name!r}[{i}] is {a.shape}, the scene {scenes.shapes[i]}")
+        flat.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
+    return torch.from_numpy(np.concatenate(flat)).to(scenes.device)
+
+
+def summarise(scenes, predictions, baselines=None, *, value_max: float, border: float = 0.0, patch_size: int, online: bool = False):
+    """summarise_evaluation (utils/utils.py:970-1368) on the device.
+
+    scenes: the `data.DeviceScenes` store; the ground truth is `scenes.store["hr_dem"]`, read in place.
+    predictions: a complete `ScenePredictions`, or a list of per-scene metre rasters (whole scenes or border-cropped mosaics).
+    baselines: {name: "lr_dem" (the store's own input DEM) | a list of (h, w) metre rasters, one per scene, uploaded once
+    in store layout (`store_layout` does it ahead of time; its flat tensor is accepted here too)}.
+    Every raster loses int(patch_size * border) pixels per side (utils.py:1276-1306); a prediction that already has the
+    cropped size is taken whole.  value_max: tensor_kwargs.max, PSNR's numerator.
+    -> {name: {"RMSE", "Median", "NMAD", "LE95", "PSNR"}} pooled over all pixels of all scenes ("offline"), for "SR" and
+    each baseline.  online=True: -> (that dict, {name: the means of the per-scene values}, {name: {scene id: the five
+    values}}).  One K12(b) call, one device-to-host copy at the end, no other synchronisation."""
+    names = ["SR"] + list(baselines or {})
+    if len(names) > MAX_CANDIDATES:
+        raise ValueError(f"summarise: {len(names)} candidates, at most {MAX_CANDIDATES}")
+    if "SR" in (baselines or {}):
+        raise ValueError("summarise: 'SR' names the prediction")
+    S = len(scenes)
+    b = int(patch_size * border)
+    offs = [0]
+    for h, w in scenes.shapes:
+        offs.append(offs[-1] + h * w)
+    gt = scenes.store["hr_dem"]
+    if isinstance(predictions, ScenePredictions):
+        if predictions.scenes is not scenes or not predictions.complete:
+            raise ValueError("summarise: the collector must be complete and made on the same scenes")
+        sr, sr_off, sr_shape = predictions.buffer, predictions.offsets, [predictions.shape] * S
+    else:
+        if len(predictions) != S:
+            raise ValueError(f"summarise: {len(predictions)} predictions for {S} scenes")
+        arrs = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float32) for p in predictions]
+        sr_shape = [tuple(a.shape) for a in arrs]
+        sr_off = [0]
+        for a in arrs:
+            sr_off.append(sr_off[-1] + a.size)
+        sr = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs])).to(scenes.device)
+    cands = [sr]
+    for name, src in (baselines or {}).items():
+        if isinstance(src, str):
+            if src != "lr_dem":
+                raise ValueError(f"summarise: baseline {name!r}: {src!r} is not a raster of the store ('lr_dem')")
+            cands.append(scenes.store["lr_dem"])
+        elif isinstance(src, torch.Tensor) and src.dim() == 1:           # already in store layout, e.g. uploaded by an earlier call
+            if src.numel() != gt.numel() or src.dtype != torch.float32 or src.device != gt.device:
+                raise ValueError(f"summarise: baseline {name!r}: a flat tensor must have the store's layout, dtype and device")
+            cands.append(src.contiguous())
+        else:
+            cands.append(store_layout(scenes, src, name))
+    windows = []
+    for i, (h, w) in enumerate(scenes.shapes):
+        ch, cw = h - 2 * b, w - 2 * b
+        if ch <= 0 or cw <= 0:
+            raise ValueError(f"summarise: nothing left of scene {scenes.ids[i]} ({h} x {w}) after a crop of {b}")
+        at = (offs[i] + b * w + b, w)
+        if sr_shape[i] == (h, w):
+            sr_at = (sr_off[i] + b * w + b, w)
+        elif sr_shape[i] == (ch, cw):
+            sr_at = (sr_off[i], cw)
+        else:
+            raise ValueError(f"summarise: prediction {scenes.ids[i]} is {sr_shape[i]}, expected {(h, w)} or {(ch, cw)}")
+        windows.append((0, ch, cw, at, [sr_at] + [at] * (len(cands) - 1)))
+    if online:
+        windows += [(1 + i,) + wdw[1:] for i, wdw in enumerate(windows)]
+    rows = pooled_rows(cands, gt, windows, 1 + S if online else 1, value_max)
+    host = rows.cpu().numpy().astype(np.float64)              # the one device-to-host copy
+    pooled = {name: {k: float(host[c, 0, j]) for j, k in enumerate(COLUMNS)} for c, name in enumerate(names)}
+    if not online:
+        return pooled
+    per_scene = {name: {sid: {k: float(host[c, 1 + i, j]) for j, k in enumerate(COLUMNS)} for i, sid in enumerate(scenes.ids)}
+                 for c, name in enumerate(names)}
+    means = {name: {k: sum(v[k] for v in per_scene[name].values()) / S for k in COLUMNS} for name in names}
+    return pooled, means, per_scene
