@@ -533,6 +533,42 @@ int jspsr_summary_forward(const float* const* cands, const long long* cand_numel
                           int n_segments, long long total, long long total_chunks, double value_max, float* out,
                           void* workspace, jspsr_stream_t stream);
 
+/* ---- K13 (ABI v23): whole-scene inference, the steps either side of the forward (csrc/scene.hip) ----------
+ * What upscale_dem does around the model call (utils/utils.py:1556-1654): add_padding (:1501-1520) and ToTensor
+ * (data/data_utils.py:217-312) before it, remove_padding (:1523-1531) after it -- and, for metres, the clip, descale_data
+ * and + base of save_prediction_to_disk (evaluation/evaluate_utils.py:242-271) -- each side ONE launch for a batch of B
+ * equally sized scenes.
+ *
+ * jspsr_scene_prepare: the raw HWC scene store -> the model's fp32 NCHW inputs.  src, src_bytes, out, channels, coff, cpitch
+ *   (HOST arrays of 6), scenes, n_scenes, flags, elev_min / elev_max and mask_div exactly as for jspsr_batch_make (K9); kind 1
+ *   (hr_dem) is no input of a model and must be absent (out[1] NULL).  out[kind] is (B, cpitch, Hp, Wp).
+ *   samples device int32 [B][2] = {scene, base elevation (fp32 bit pattern)}.
+ *   rows    device int32 [Hp], cols device int32 [Wp]: out[b][c][Y][X] = ToTensor_kind(scene[rows[Y]][cols[X]][c]).  The
+ *     mirror border of add_padding is separable (left / right depend on X only, top / bottom -- the bottom with its
+ *     off-by-one -- on Y only), so the two maps carry it index for index, and the extension of the frame to a multiple of
+ *     the model's stride and plain crops as well; the policy lives with the caller (jspsr_amd/infer.py: frame_maps).
+ *     coord writes rows[Y] / (H - 1) and cols[X] / (W - 1): the local coordinates of the SOURCE pixel.  A sample whose
+ *     scene index or store extent is bad, and a map entry outside [0, H) / [0, W), write NaN; nothing is read there.
+ *   The per-kind arithmetic is K9's (csrc/totensor.h, shared by both translation units): image, mask, canopy and coord are
+ *   the reference's bits, DEM values within 1 ulp of numpy's fp32 log.  16-byte stores when Wp % 4 == 0 and out[kind] is
+ *   16-byte aligned; otherwise any 4-byte aligned output.
+ *
+ * jspsr_scene_finish: pred [B][1][Hp][Wp] in the network's range (dtype JSPSR_F32 or JSPSR_BF16) -> out [B][H][W] fp32,
+ *   the window whose corner is (top, left).  metres != 0: clamp to [0, 1] (a NaN stays a NaN, as under torch.clamp), then
+ *   v * (max - min) + min, or exp(v * log(max - min)) + min with elev_log, then + base (samples[b][1]), every operation
+ *   rounded on its own in fp32 with the constants formed as jspsr_elev_scale_f32 forms them: bit-equal to clamp ->
+ *   jspsr_elev_scale_f32 (descale) -> + base.  metres == 0: the window is copied (converted to fp32), nothing else.
+ *   samples as above (only the base is read).
+ *
+ * JSPSR_EINVAL: a null pointer, B <= 0, sizes that do not fit together, a window that leaves the frame.  No host
+ * synchronisation. */
+int jspsr_scene_prepare(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
+                        const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples, int B,
+                        const int* rows, const int* cols, int Hp, int Wp, int flags, double elev_min, double elev_max,
+                        int mask_div, jspsr_stream_t stream);
+int jspsr_scene_finish(int dtype, const void* pred, float* out, const int* samples, int B, int Hp, int Wp, int top, int left,
+                       int H, int W, int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -34,6 +34,7 @@ class ResBlock(nn.Module):
 
 
 class EDSR(HotPathModule):
+    size_multiple = 1             # no stride: any frame size
     receptive_radius = None      # sharded inference (tiling.py): spn=True is not certified (check_reach=False only)
 
     def __init__(self, in_channels=3, out_channels=3, n_resblocks=16, n_features=64, scale=2, res_scale=0.1,

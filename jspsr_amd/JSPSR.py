@@ -29,6 +29,7 @@ class Model(HotPathModule):
     # spn=False (the no-propagation ablation, JSPSR.py:195-204,378): the 3x3 conv head replaces generator + sampler, so the
     # radius is 97 - 5 - 1 + 1 = 92 and there are no learned offsets (tiling.py certifies on the radius alone)
     plain_receptive_radius = 92
+    size_multiple = 8             # three stride-2 stages: whole-scene inference (infer.py) brings the frame to a multiple of it
 
     def __init__(self, in_channels: dict, out_channels: int = 1, num_feature: int = 32,
                  layers: tuple = (2, 2, 2, 2), res_scale: tuple = (1, 1, 1, 1), spn: bool = True,

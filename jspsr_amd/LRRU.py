@@ -100,6 +100,7 @@ class Model(HotPathModule):
     # propagation steps applied to their own output) -> strips run only with check_reach=False; the steps still report
     # their learned offsets, and their reaches add up
     receptive_radius = None
+    size_multiple = 16            # five stride-2 stages, the first at full size (forward refuses other sizes)
     offsets_chain = True
 
     def __init__(self, args, layers=(2, 2, 2, 2, 2)):

@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _lock = threading.Lock()
 _lib = None
@@ -100,6 +100,8 @@ SIGNATURES = {
     "jspsr_gate_mlp_backward_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_gate_mlp_backward": (c_i, [c_p] * 7 + [c_i, c_i, c_i] + [c_p] * 6),
     "jspsr_batch_make": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_scene_prepare": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_scene_finish": (c_i, [c_i, c_p, c_p, c_p] + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_nchw_to_nhwc": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
 }
 

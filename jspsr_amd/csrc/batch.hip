@@ -9,17 +9,16 @@
 // dwords, so the column walk of a rotated tile hits a different bank per row.  Each thread then writes four consecutive
 // output pixels of a channel row at once (one 16-byte store when k % 4 == 0 and the output is 16-byte aligned).
 #include "common.h"
+#include "totensor.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kTile = 32;                                   // output tile side
-constexpr int kMaxC = 16;                                   // channels per kind
-constexpr int kPitch = (kTile * kMaxC + 8) / 4 | 1;        // LDS row pitch in dwords: 32 px x 16 B + the unaligned head, odd
-constexpr int kKinds = 6;
+using namespace jspsr;                                      // Kind, kKinds, kMaxC, scale_dem, transform (totensor.h)
 
-enum Kind { LR_DEM = 0, HR_DEM = 1, IMAGE = 2, MASK = 3, CANOPY = 4, COORD = 5 };
+constexpr int kTile = 32;                                   // output tile side
+constexpr int kPitch = (kTile * kMaxC + 8) / 4 | 1;        // LDS row pitch in dwords: 32 px x 16 B + the unaligned head, odd
 
 struct KindDesc {
   const unsigned char* src;   // scene store of this kind (HWC, C channels of 1 or 4 bytes); NULL for COORD
@@ -51,42 +50,7 @@ __device__ __forceinline__ void d4_source(int code, int k, int i, int j, int& sy
   }
 }
 
-// ToTensor, per kind (data_utils.py:217-312); every operation rounded on its own (-ffp-contract=off, csrc/Makefile)
-__device__ __forceinline__ float scale_dem(float z, float base, int is_label, const BatchArgs& a) {
-  float v = z;
-  if (base != 0.f) v = __fsub_rn(v, base);                            // data - base_elev (fp32)
-  v = __fsub_rn(v, a.lo);                                             // data - elev_min (fp32)
-  const bool to11 = (a.flags & (is_label ? JSPSR_BATCH_LABEL_11 : JSPSR_BATCH_IMAGE_11)) != 0;
-  if (a.flags & JSPSR_BATCH_LOG) {
-    // np.log(fp32) / np.log(<Python number>) is fp32 / float64 -> float64 under NumPy 2, and so are + 1e-8 and * 2 - 1
-    double o = __dadd_rn(__ddiv_rn((double)logf(v), a.log_span), 1e-8);
-    if (to11) o = __dsub_rn(__dmul_rn(o, 2.0), 1.0);
-    return (float)o;
-  }
-  float o = __fdiv_rn(v, a.span);                                     // (data - min) / (max - min), fp32
-  if (to11) o = __fsub_rn(__fmul_rn(o, 2.f), 1.f);
-  return o;
-}
-
-__device__ __forceinline__ float transform(int kind, int c, const unsigned char* p, float base, int Y, int X, long long H,
-                                           long long W, const BatchArgs& a) {
-  switch (kind) {
-    case LR_DEM: return scale_dem(*reinterpret_cast<const float*>(p), base, 0, a);
-    case HR_DEM: return scale_dem(*reinterpret_cast<const float*>(p), base, 1, a);
-    case IMAGE: {
-      float o = __fdiv_rn((float)*p, 255.f);                          // to_tensor: uint8 -> float, div(255)
-      if (a.flags & JSPSR_BATCH_IMAGE_11) o = __fsub_rn(__fmul_rn(2.f, o), 1.f);
-      else if (a.flags & JSPSR_BATCH_IMAGE_255) o = __fdiv_rn(o, 255.f);
-      return o;
-    }
-    case MASK:
-      if (a.flags & JSPSR_BATCH_SCALE_MASK) return __fdiv_rn(__fmul_rn((float)*p, (float)(c + 1)), (float)a.mask_div);
-      return (float)*p;
-    case CANOPY: return __fdiv_rn((float)*p, 68.f);
-    default:                                                          // local coordinates over the whole scene
-      return c == 0 ? __fdiv_rn((float)Y, (float)(H - 1)) : __fdiv_rn((float)X, (float)(W - 1));
-  }
-}
+// ToTensor, per kind (data_utils.py:217-312): scale_dem / transform of totensor.h, shared with K13 (scene.hip)
 
 __global__ __launch_bounds__(256) void batch_kernel(BatchArgs a, int tiles_x) {
   __shared__ unsigned int lds[kTile * kPitch];

@@ -60,6 +60,17 @@ class DeviceScenes:
                  relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
                  normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda"):
+        if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
+            raise KeyError("hr_dem")
+        self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
+                    elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
+                    image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device)
+
+    def _setup(self, raw: dict, coord, *, relative, elev_min, elev_max, elev_log, scale_mask, mask_channel, image_range,
+               label_range, normalize, ids, device, base=None):
+        """Checks, layout and upload of a store holding the kinds of `raw` that are not None (`infer.InferenceScenes` is
+        the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`."""
+        lr_dem = raw["lr_dem"]
         if coord not in (None, "local"):
             if str(coord).lower() == "global":
                 raise NotImplementedError("coord='global' needs the scenes' georeferencing; only 'local' is built")
@@ -75,7 +86,6 @@ class DeviceScenes:
         self.relative, self.elev_min, self.elev_max, self.elev_log = relative, elev_min, elev_max, elev_log
         self.scale_mask, self.image_range, self.label_range = scale_mask, image_range, label_range
         self.mask_channel = list(mask_channel) if mask_channel else [*range(15)]      # ToTensor's default (data_utils.py:215)
-        raw = {"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}
         n = len(lr_dem)
         if n == 0:
             raise ValueError("no scenes")
@@ -105,6 +115,10 @@ class DeviceScenes:
             raise ValueError("local coordinates need scenes of at least 2 x 2 pixels")
         self.ids = [str(i) for i in range(n)] if ids is None else [str(i) for i in ids]
         self.base = [np.min(a) if relative else 0 for a in host["lr_dem"]]
+        if base is not None:
+            if len(base) != n:
+                raise ValueError(f"base: {len(base)} values, lr_dem has {n} scenes")
+            self.base = list(base)
         for i in range(n):
             self._check_scene(i, {k: v[i] for k, v in host.items()})
         offs = np.zeros(n + 1, dtype=np.int64)
@@ -133,6 +147,8 @@ class DeviceScenes:
     def _check_scene(self, i: int, s: dict):
         """The reference's per-crop range asserts, once over the whole scene (see the class docstring)."""
         for kind in ("lr_dem", "hr_dem"):
+            if kind not in s:
+                continue
             v = self.scale_dem(s[kind], self.base[i])
             if not (v.min() >= 0 and v.max() <= 1):
                 raise AssertionError(f"scene {self.ids[i]} {kind}: scaled to [{v.min()}, {v.max()}], not within [0, 1]")

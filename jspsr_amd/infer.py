@@ -1,0 +1,376 @@
+"""Whole-scene inference on the device (K13, csrc/scene.hip): raw rasters in, metres out.
+
+The reference's `upscale_dem` (utils/utils.py:1556-1654) pads a decoded scene to a power of two with a mirrored border
+(`cal_pad` / `add_padding`, :1501-1553), runs `ToTensor` (data/data_utils.py:217-312) on every raster, calls the model and
+removes the border again.  Here each side of the forward is ONE launch, for a batch of equally sized scenes:
+
+    scenes = InferenceScenes(lr_dem=[...], image=[...], mask=[...], relative=True, elev_min=-80, elev_max=933,
+                             elev_log=True, scale_mask=True)
+    result = predict_scenes(model, scenes, batch_size=8, pad="pow2")          # no host synchronisation
+    dems = result.rasters()                                                   # {scene id: (H, W) fp32 metres}
+
+`prepare` gathers the raw HWC bytes of the store through two index maps (`frame_maps`) and applies ToTensor's per-kind
+arithmetic -- K9's, bit for bit (csrc/totensor.h).  The maps carry `add_padding`'s mirror border index for index (its
+bottom strip sits one row above a true mirror), the extension of the frame to a multiple of the model's `size_multiple`,
+and nothing else: all policy is host code.  `finish` reads the window back and, for metres, applies clamp ->
+`metrics.descale_data` -> `+ base`, the bits of `summary.compose_scene` on a single uncropped tile.  `upscale_dem` keeps
+the reference's own contract on top of the two.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import tiles as T
+from .data import CONCAT_ORDER, DeviceScenes, ctypes_arrays
+
+Frame = namedtuple("Frame", "Hp Wp top left H W")     # the padded frame and the scene's window in it
+
+_CACHE_LIMIT = 256                                    # entries of a cache of uploads; a full cache is emptied
+_MAPS = {}                                            # (H, W, pad, multiple, device) -> _Uploaded((rows, cols)), Frame
+
+
+def frame_maps(H: int, W: int, pad: int = 0, multiple: int = 1):
+    """-> (rows, cols, top, left): int32 numpy maps with frame[Y][X] = scene[rows[Y]][cols[X]], and the scene's corner.
+
+    With n = pad the frame is (H + 2n + eh) x (W + 2n + ew), eh = -(H + 2n) mod multiple, ew likewise: `add_padding`'s
+    border (utils/utils.py:1501-1520) and, past it, its bottom / right rule continued until the side is a multiple.
+      rows: Y < n -> n-1-Y;  Y < H+n -> Y-n;  else 2H+n-2-Y    (the reference's bottom strip, one row above a mirror)
+      cols: X < n -> n-1-X;  X < W+n -> X-n;  else 2W+n-1-X
+    ValueError unless n <= H, n + eh <= H - 1 and n + ew <= W: the conditions under which every entry is inside the scene."""
+    H, W, n, m = int(H), int(W), int(pad), int(multiple)
+    if H < 1 or W < 1 or n < 0 or m < 1:
+        raise ValueError(f"frame_maps: H {H}, W {W}, pad {n}, multiple {m}")
+    eh, ew = (-(H + 2 * n)) % m, (-(W + 2 * n)) % m
+    if not (n <= H and n + eh <= H - 1 and n + ew <= W):
+        raise ValueError(f"frame_maps: a {H} x {W} scene cannot fill a border of {n} and an extension of {eh} rows, {ew} "
+                         f"columns (needs pad <= H, pad + rows <= H - 1, pad + columns <= W)")
+    Y = np.arange(H + 2 * n + eh, dtype=np.int64)
+    X = np.arange(W + 2 * n + ew, dtype=np.int64)
+    rows = np.where(Y < n, n - 1 - Y, np.where(Y < H + n, Y - n, 2 * H + n - 2 - Y)).astype(np.int32)
+    cols = np.where(X < n, n - 1 - X, np.where(X < W + n, X - n, 2 * W + n - 1 - X)).astype(np.int32)
+    return rows, cols, n, n
+
+
+class _Uploaded:
+    """Small int32 arrays copied to the device once and kept: one stream-ordered copy each from a pinned buffer that is
+    never written again (as data._Batches._upload), on the stream that is current at the first use.  A later use may be on
+    another stream, which nothing orders behind that copy, so the copies are followed by an event: `on_current_stream`
+    makes the current stream wait for it on the device (no host synchronisation) until the copies are seen to be
+    complete, and tells the allocator about a stream other than the first, so that the memory of an evicted entry is not
+    handed out again under a kernel that still reads it."""
+
+    def __init__(self, hosts, device):
+        self.device = device
+        self.stream = torch.cuda.current_stream(device)
+        self.tensors = []
+        for host in hosts:
+            pinned = torch.empty(host.shape, dtype=torch.int32, pin_memory=True)
+            pinned.numpy()[...] = host
+            self.tensors.append(pinned.to(device, non_blocking=True))
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+
+    def on_current_stream(self):
+        stream = torch.cuda.current_stream(self.device)
+        if self.event is not None:
+            if self.event.query():
+                self.event = None
+            elif stream != self.stream:
+                stream.wait_event(self.event)
+        if stream != self.stream:
+            for t in self.tensors:
+                t.record_stream(stream)
+        return self.tensors
+
+
+def _device_maps(H, W, pad, multiple, device):
+    """-> (rows, cols, frame): the device copies of `frame_maps`, cached per geometry and device, ordered for the current
+    stream."""
+    key = (H, W, pad, multiple, str(device))
+    if key not in _MAPS:
+        rows, cols, top, left = frame_maps(H, W, pad, multiple)
+        if len(_MAPS) >= _CACHE_LIMIT:
+            _MAPS.clear()
+        _MAPS[key] = (_Uploaded((rows, cols), torch.device(device)), Frame(len(rows), len(cols), top, left, H, W))
+    maps, frame = _MAPS[key]
+    rows, cols = maps.on_current_stream()
+    return rows, cols, frame
+
+
+class InferenceScenes(DeviceScenes):
+    """`data.DeviceScenes` without a ground truth: decoded scenes, uploaded once, in the same flat HWC layout with the same
+    members (`store`, `scene_table`, `base`, `flags`, `channels`, `shapes`, `ids`) and the same whole-scene range checks.
+    base: per-scene base elevations to use instead of `np.min(lr_dem)` (upscale_dem's `meta["base"]`)."""
+
+    def __init__(self, lr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *, relative: bool = False,
+                 elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
+                 mask_channel: Sequence[int] | None = None, image_range: str | None = None, ids: Sequence[str] | None = None,
+                 device="cuda", base: Sequence | None = None):
+        self._setup({"lr_dem": lr_dem, "hr_dem": None, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
+                    elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
+                    image_range=image_range, label_range=None, normalize=None, ids=ids, device=device, base=base)
+
+
+def _input_kinds(scenes):
+    return [k for k in CONCAT_ORDER if k in scenes.channels]
+
+
+def _rows_of(scenes, indices) -> np.ndarray:
+    """The sample table of jspsr_scene_prepare / _finish: (B, 2) int32 {scene, base as fp32 bits}."""
+    rows = np.zeros((len(indices), 2), dtype=np.int32)
+    for j, s in enumerate(indices):
+        if not 0 <= int(s) < len(scenes):
+            raise IndexError(f"scene {s} of {len(scenes)}")
+        rows[j] = (int(s), np.float32(scenes.base[int(s)]).view(np.int32))
+    return rows
+
+
+def _table(scenes, indices) -> torch.Tensor:
+    """The device copy of `_rows_of`, kept with the store per index list and ordered for the current stream: a repeated call
+    uploads nothing."""
+    cache = scenes.__dict__.setdefault("_infer_tables", {})
+    key = tuple(int(s) for s in indices)
+    if key not in cache:
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        cache[key] = _Uploaded((_rows_of(scenes, key),), scenes.device)
+    return cache[key].on_current_stream()[0]
+
+
+def _one_shape(scenes, indices):
+    if len(indices) == 0:
+        raise ValueError("no scenes named")
+    shapes = {tuple(scenes.shapes[int(s)]) for s in indices}
+    if len(shapes) != 1:
+        raise ValueError(f"scenes of shapes {sorted(shapes)} cannot share a frame")
+    return shapes.pop()
+
+
+def _prepare(scenes, table, H, W, pad, multiple, concat):
+    rows, cols, frame = _device_maps(H, W, int(pad), int(multiple), scenes.device)
+    B = table.shape[0]
+    kinds = _input_kinds(scenes)
+    kw = dict(dtype=torch.float32, device=scenes.device)
+    outs = {}
+    if concat:
+        images = torch.empty((B, sum(scenes.channels[k] for k in kinds), frame.Hp, frame.Wp), **kw)
+        c0 = 0
+        for k in kinds:
+            outs[k] = (images, c0)
+            c0 += scenes.channels[k]
+        inputs = [images]
+    else:
+        for k in kinds:
+            outs[k] = (torch.empty((B, scenes.channels[k], frame.Hp, frame.Wp), **kw), 0)
+        inputs = [outs[k][0] for k in kinds]
+    launch_prepare(scenes, table, rows, cols, frame.Hp, frame.Wp, outs)
+    return inputs, frame
+
+
+def launch_prepare(scenes, table, rows, cols, Hp, Wp, outs: dict):
+    """The raw call: table (B, 2) int32, rows (Hp,) and cols (Wp,) int32 on the device; outs kind -> (tensor of
+    (B, cpitch, Hp, Wp) fp32, first channel), as `DeviceScenes.make` takes them."""
+    P = ctypes_arrays(scenes, outs)
+    _lib.check(_lib.load().jspsr_scene_prepare(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
+                                               table.data_ptr(), table.shape[0], rows.data_ptr(), cols.data_ptr(), Hp, Wp,
+                                               scenes.flags, float(scenes.elev_min), float(scenes.elev_max),
+                                               len(scenes.mask_channel) + 1, torch.cuda.current_stream(scenes.device).cuda_stream),
+               "jspsr_scene_prepare")
+
+
+def prepare(scenes, indices: Sequence[int], pad: int = 0, multiple: int = 8, concat: bool = False):
+    """One launch: the scenes `indices` of the store (all of one shape) -> (inputs, frame).  inputs: the model's fp32
+    (B, C, Hp, Wp) tensors in `data.batch_pair`'s order [lr_dem, image, mask, canopy, coord], the kinds the store holds;
+    concat=True: one tensor [lr_dem | image | ...] (EDSR's input).  frame: `Frame(Hp, Wp, top, left, H, W)`."""
+    H, W = _one_shape(scenes, indices)
+    return _prepare(scenes, _table(scenes, indices), H, W, pad, multiple, concat)
+
+
+def _finish(pred, table, scenes, frame, metres, out):
+    B = table.shape[0]
+    if pred.dim() == 3:
+        pred = pred[:, None]
+    if tuple(pred.shape) != (B, 1, frame.Hp, frame.Wp):
+        raise ValueError(f"finish: predictions {tuple(pred.shape)}, expected {(B, 1, frame.Hp, frame.Wp)}")
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"finish: fp32 or bf16 predictions, got {pred.dtype}")
+    if pred.device != scenes.device:
+        raise ValueError(f"finish: predictions on {pred.device}, the scenes on {scenes.device}")
+    pred = pred.detach().contiguous()
+    _lib.check(_lib.load().jspsr_scene_finish(int(pred.dtype == torch.bfloat16), pred.data_ptr(), out.data_ptr(), table.data_ptr(),
+                                              B, frame.Hp, frame.Wp, frame.top, frame.left, frame.H, frame.W, int(bool(metres)),
+                                              int(bool(scenes.elev_log)), float(scenes.elev_min), float(scenes.elev_max),
+                                              torch.cuda.current_stream(scenes.device).cuda_stream), "jspsr_scene_finish")
+    return out
+
+
+def finish(pred: torch.Tensor, scenes, indices: Sequence[int], frame: Frame, metres: bool = True) -> torch.Tensor:
+    """One launch: predictions (B, 1, Hp, Wp) in the network's range (fp32 or bf16) -> (B, H, W) fp32, the scenes' window
+    of the frame.  metres=True: clamp to [0, 1] -> `metrics.descale_data` -> + the scene's base elevation (NaN stays NaN);
+    metres=False: the window as it is (what upscale_dem returns)."""
+    _one_shape(scenes, indices)
+    out = torch.empty((len(indices), frame.H, frame.W), dtype=torch.float32, device=scenes.device)
+    return _finish(pred, _table(scenes, indices), scenes, frame, metres, out)
+
+
+def _model_name(model, model_name):
+    return str(model_name or getattr(model, "name", None) or type(model).__module__.rsplit(".", 1)[-1]).lower()
+
+
+def _model_inputs(name, scenes, input_data):
+    """(concat, positions of prepare's outputs to pass on), as `data.batch_pair` chooses a model's inputs."""
+    kinds = _input_kinds(scenes)
+    if name == "completionformer":
+        raise NotImplementedError("the completionformer split input is not built")
+    want = kinds if input_data is None else ["lr_dem"] + [k for k in CONCAT_ORDER[1:] if k in input_data]
+    missing = [k for k in want if k not in kinds]
+    if missing:
+        raise ValueError(f"input_data asks for {missing}, the store holds {kinds}")
+    if name in {"jspsr", "lrru"}:
+        return False, [kinds.index(k) for k in want]
+    if want != kinds:
+        raise ValueError(f"input_data asks for {want}, the store holds {kinds}: a concatenated input takes every kind")
+    return True, [0]
+
+
+class SceneRasters:
+    """What `predict_scenes` returns: `buffer` flat fp32 on the device, and per scene, in the order the scenes were named,
+    `offsets` (elements into the buffer), `shapes` and `ids`."""
+
+    def __init__(self, buffer, offsets, shapes, ids):
+        self.buffer, self.offsets, self.shapes, self.ids = buffer, offsets, shapes, ids
+
+    def rasters(self) -> dict:
+        """{scene id: (H, W) float32 numpy array}: one device-to-host copy.  `list(rasters().values())` over a whole store
+        is what `summary.summarise` takes as `predictions`."""
+        host = self.buffer.cpu().numpy()
+        return {sid: host[o:o + h * w].reshape(h, w).copy() for sid, o, (h, w) in zip(self.ids, self.offsets, self.shapes)}
+
+
+@torch.no_grad()
+def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch_size: int = 1, pad=0,
+                   model_name: str | None = None, input_data: dict | None = None, metres: bool = True) -> SceneRasters:
+    """Whole scenes through the model: `model.eval()`, no gradients; the scenes are grouped by shape in index order and,
+    per group, each batch runs prepare -> forward -> finish (two launches around the forward, written straight into the
+    result's buffer).  No host synchronisation anywhere in the pass.
+
+    scenes: an `InferenceScenes`, or a `data.DeviceScenes` (its hr_dem is not read).  pad: the mirror border in pixels, or
+    "pow2" for `tiles.cal_pad` (the reference's rule; it asserts that both sides get the same border).  The frame is
+    extended to a multiple of `model.size_multiple` (JSPSR 8, LRRU 16, EDSR 1).  model_name / input_data choose the inputs
+    as `data.batch_pair` does: JSPSR / LRRU get [lr_dem, image, mask, canopy, coord] as far as input_data names them (None:
+    every kind of the store), any other model the concatenated tensor.  metres=False leaves the network's range."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    indices = list(range(len(scenes))) if indices is None else [int(i) for i in indices]
+    if not indices:
+        raise ValueError("predict_scenes: no scenes")
+    concat, take = _model_inputs(_model_name(model, model_name), scenes, input_data)
+    multiple = int(getattr(model, "size_multiple", 1))
+    groups = {}
+    for pos, s in enumerate(indices):
+        groups.setdefault(tuple(scenes.shapes[s]), []).append(pos)
+    order, offsets, total = [], [0] * len(indices), 0
+    for (h, w), members in groups.items():
+        total = (total + 3) // 4 * 4                          # a group starts 16-byte aligned
+        for pos in members:
+            offsets[pos] = total
+            total += h * w
+        order += members
+    table = _table(scenes, [indices[pos] for pos in order])
+    buffer = torch.empty(total, dtype=torch.float32, device=scenes.device)
+    model.eval()
+    at = 0
+    for (h, w), members in groups.items():
+        n = T.cal_pad(h, w) if pad == "pow2" else int(pad)
+        for lo in range(0, len(members), batch_size):
+            B = min(batch_size, len(members) - lo)
+            rows = table[at + lo:at + lo + B]
+            inputs, frame = _prepare(scenes, rows, h, w, n, multiple, concat)
+            pred = model(*[inputs[i] for i in take])
+            o = offsets[members[lo]]
+            _finish(pred, rows, scenes, frame, metres, buffer[o:o + B * h * w])
+        at += len(members)
+    return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+
+
+def _get(p, name, default=None):
+    return p.get(name, default) if isinstance(p, dict) else getattr(p, name, default)
+
+
+def _as_u8(a, name):
+    a = np.asarray(a)
+    if a.dtype == np.uint8:
+        return a
+    b = a.astype(np.uint8)
+    if not np.array_equal(b, a):
+        raise ValueError(f"upscale_dem: {name} holds values that are not whole numbers 0..255")
+    return b
+
+
+def upscale_dem(model, sample: dict, p):
+    """The reference's `upscale_dem(model, sample, p)` (utils/utils.py:1556-1654) -> (y, t_infer_ms, m_infer_MB).
+
+    sample: HWC numpy arrays "lr_dem" and, optionally, "image" and "mask" (the mask_channel selection applied), plus
+    `sample["meta"]["base"]` when `p.relative` (KeyError without it, as in the reference).  p (attributes or keys):
+    mask_channel, relative, tensor_kwargs {min, max, log, scale_mask, image_range}, model_name, input_data.  The elevation
+    range tensor_kwargs min / max is required (ValueError without it).  As in the reference, the inputs are the rasters
+    the SAMPLE holds; `input_data` does not choose them.  The reference reads it only for the channel counts of the
+    concatenated tensor, so here, for a model with a concatenated input, an input_data whose image / mask channels differ
+    from the sample's is a ValueError; for JSPSR / LRRU it is not read.
+    The border is `cal_pad` of the DEM, with the reference's assertion that both sides get the same one.  The padded
+    frame must be a multiple of `model.size_multiple`, otherwise ValueError -- the reference would fail inside the model's
+    concat; `predict_scenes` extends such frames.  The model runs as it is handed over (the reference does not call
+    `eval()` either) under no_grad.
+    y: (H, W, 1) float32 in the network's range, unclamped, the padding removed.  t_infer: the forward alone, between two
+    events and followed by a synchronisation, in ms.  m_infer: `torch.cuda.max_memory_allocated` after a reset of the
+    peak, in MB.
+    Models other than JSPSR / LRRU get the concatenated input [lr_dem | image | mask], as `data.batch_pair` builds it; the
+    reference's own `else` branch fills that tensor and then passes the list [dem, img, msk] instead (:1628), which no
+    such model accepts."""
+    dem = np.asarray(sample["lr_dem"])
+    if dem.ndim != 3 or dem.shape[2] != 1:
+        raise ValueError(f"upscale_dem: lr_dem must be (H, W, 1), got {dem.shape}")
+    H, W = dem.shape[:2]
+    pad = T.cal_pad(H, W)
+    multiple = int(getattr(model, "size_multiple", 1))
+    if (H + 2 * pad) % multiple or (W + 2 * pad) % multiple:
+        raise ValueError(f"upscale_dem: a {H} x {W} scene pads to {H + 2 * pad} x {W + 2 * pad}, not a multiple of {multiple}; "
+                         f"predict_scenes extends the frame to one")
+    relative = bool(_get(p, "relative", False))
+    base = sample["meta"]["base"] if relative else 0.0
+    kw = _get(p, "tensor_kwargs") or {}
+    if kw.get("min") is None or kw.get("max") is None:
+        raise ValueError("upscale_dem: p.tensor_kwargs must give the elevation range, min and max")
+    name = _model_name(model, _get(p, "model_name"))
+    input_data = _get(p, "input_data")
+    if name not in {"jspsr", "lrru"} and input_data is not None:
+        for k in ("image", "mask"):
+            have = np.asarray(sample[k]).shape[2] if k in sample else 0
+            if int(input_data.get(k, 0)) != have:
+                raise ValueError(f"upscale_dem: input_data gives {k} {input_data.get(k, 0)} channels, the sample holds {have}")
+    device = next(model.parameters()).device
+    scenes = InferenceScenes([np.ascontiguousarray(dem, dtype=np.float32)],
+                             image=[np.ascontiguousarray(_as_u8(sample["image"], "image"))]
+                             if "image" in sample else None,
+                             mask=[np.ascontiguousarray(_as_u8(sample["mask"], "mask"))] if "mask" in sample else None,
+                             relative=relative, elev_min=kw.get("min"), elev_max=kw.get("max"), elev_log=kw.get("log", False),
+                             scale_mask=kw.get("scale_mask", False), mask_channel=_get(p, "mask_channel"),
+                             image_range=kw.get("image_range"), device=device, base=[base] if relative else None)
+    concat = name not in {"jspsr", "lrru"}
+    with torch.no_grad():
+        inputs, frame = prepare(scenes, [0], pad, 1, concat)
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.reset_peak_memory_stats(device)
+        start.record()
+        y = model(*inputs)
+        stop.record()
+        torch.cuda.current_stream(device).synchronize()
+        t_infer = start.elapsed_time(stop)
+        m_infer = torch.cuda.max_memory_allocated(device) / 1024 / 1024
+        y = finish(y, scenes, [0], frame, metres=False)
+    return y[0].cpu().numpy()[..., None], t_infer, m_infer

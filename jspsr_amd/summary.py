@@ -13,8 +13,9 @@ both for the prediction and for every baseline DEM against the ground truth.
 
 The pooled numbers differ from the per-tile meters of `metrics.batch_scores` (K10) by definition: numpy's median is the
 mean of the two middle elements (torch.median: the lower one) and numpy's percentile interpolates (kthvalue: one element).
-Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K12.  GeoTIFF output, plotting,
-`upscale_dem` and the richdem slope stay out.
+Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K12.  GeoTIFF output, plotting and the
+richdem slope stay out; `upscale_dem` and whole-scene inference are in jspsr_amd/infer.py (K13), whose
+`predict_scenes(...).rasters()` gives the per-scene metre rasters `summarise` takes as `predictions`.
 
 Device fp32 tensors go through the HIP kernels; host tensors through the same formulas as numpy / torch operators.
 """
