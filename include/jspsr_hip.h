@@ -569,6 +569,50 @@ int jspsr_scene_prepare(const void* const* src, const long long* src_bytes, floa
 int jspsr_scene_finish(int dtype, const void* pred, float* out, const int* samples, int B, int Hp, int Wp, int top, int left,
                        int H, int W, int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
 
+/* ---- K14 (ABI v24): whole-scene self-ensemble over the flips and quarter turns (csrc/scene_tta.hip) --------
+ * The reference has no self-ensemble.  What these two replace is the host work a user of K13 needs for one: np.rot90 /
+ * fliplr / flipud of every decoded raster (the order of RandomFlipRotate90, data/data_utils.py:26-28), a store and a
+ * jspsr_scene_prepare + jspsr_scene_finish pair per orientation, and the inverse transforms and the mean in numpy.
+ * A D4 element is K9's code = rot90 * 4 + flip_lr * 2 + flip_ud, the transformed raster flipud?(fliplr?(rot90(a, rot90))),
+ * W x H for an odd rot90.  Codes c and c' with flip_ud set / clear, the other flip inverted and rot90 two apart denote the
+ * same element (16 codes, 8 elements).
+ *
+ * jspsr_scene_prepare_d4: replaces the host transform + jspsr_scene_prepare.  As jspsr_scene_prepare, except
+ *   samples device int32 [B][3] = {scene, base elevation (fp32 bit pattern), code};
+ *   codes   HOST int32 [B], the same codes: every rot90 of a launch has one parity (JSPSR_EINVAL otherwise), so that one
+ *     frame serves it;
+ *   rows [Hp] / cols [Wp] index the TRANSFORMED scene (padding comes after the transform: the reference's mirror border is
+ *     not symmetric): out[b][c][Y][X] = ToTensor_kind(T_b[rows[Y]][cols[X]][c]), T_b the transformed raster of sample b.
+ *     coord is transformed with the rest: it holds the local coordinates of the SOURCE pixel.  NaN where
+ *     jspsr_scene_prepare writes it (the entries are checked against the transformed shape) and for a sample whose device
+ *     code is outside 0..15 or of the other parity.
+ *   Even rot90: jspsr_scene_prepare's gather with reversed indices.  Odd rot90: 32 x 32 frame tiles, the source window
+ *   staged in LDS (a frame row walks a source column); B <= 65535.  The bits of jspsr_scene_prepare on a store of the
+ *   transformed rasters.
+ *
+ * jspsr_scene_finish_mean: replaces K jspsr_scene_finish launches, the inverse transforms and the mean.  variants HOST
+ *   array of K = 1..JSPSR_TTA_MAX_VARIANTS entries, copied into the kernel's arguments (no upload): prediction
+ *   [B][1][Hp][Wp] of dtype JSPSR_F32 / JSPSR_BF16 for element `code`, whose h x w window -- the transformed shape of the
+ *   H x W scene, JSPSR_EINVAL otherwise -- has its corner at (top, left).  out [B][H][W] fp32 =
+ *     post((((y'_0 + y'_1) + y'_2) + ...) / (float)K),  y'_k = the window of variant k carried back by the inverse of its
+ *   element, widened to fp32; fp32 additions in the order given, one fp32 division (K = 1: the bits of
+ *   jspsr_scene_finish); a NaN in any variant makes the pixel NaN.  post: with metres != 0 the expressions of
+ *   jspsr_scene_finish, bit for bit; nothing otherwise.  samples device int32 [B][2] as for jspsr_scene_finish.
+ *   JSPSR_EINVAL: K outside 1..8, two variants of the same element, a window that leaves its frame or does not have the
+ *   transformed shape, B outside 1..65535.  JSPSR_EALIGN: a pointer not aligned to its element size.  16-byte stores when
+ *   W % 4 == 0 and out is 16-byte aligned.  No host synchronisation. */
+#define JSPSR_TTA_MAX_VARIANTS 8
+typedef struct jspsr_tta_variant {
+  const void* pred;
+  int dtype, code, Hp, Wp, top, left, h, w;
+} jspsr_tta_variant;
+int jspsr_scene_prepare_d4(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
+                           const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples,
+                           const int* codes, int B, const int* rows, const int* cols, int Hp, int Wp, int flags,
+                           double elev_min, double elev_max, int mask_div, jspsr_stream_t stream);
+int jspsr_scene_finish_mean(const jspsr_tta_variant* variants, int K, float* out, const int* samples, int B, int H, int W,
+                            int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

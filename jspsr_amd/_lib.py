@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lock = threading.Lock()
 _lib = None
@@ -102,8 +102,16 @@ SIGNATURES = {
     "jspsr_batch_make": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_prepare": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_finish": (c_i, [c_i, c_p, c_p, c_p] + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
+    "jspsr_scene_prepare_d4": (c_i, [c_p] * 7 + [c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_scene_finish_mean": (c_i, [c_p, c_i, c_p, c_p] + [c_i] * 5 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_nchw_to_nhwc": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
 }
+
+
+class TtaVariant(ctypes.Structure):
+    """jspsr_tta_variant of include/jspsr_hip.h: one prediction of jspsr_scene_finish_mean."""
+    _fields_ = [("pred", c_p), ("dtype", c_i), ("code", c_i), ("Hp", c_i), ("Wp", c_i), ("top", c_i), ("left", c_i),
+                ("h", c_i), ("w", c_i)]
 
 
 class JspsrHipError(RuntimeError):

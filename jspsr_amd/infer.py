@@ -15,6 +15,11 @@ bottom strip sits one row above a true mirror), the extension of the frame to a 
 and nothing else: all policy is host code.  `finish` reads the window back and, for metres, applies clamp ->
 `metrics.descale_data` -> `+ base`, the bits of `summary.compose_scene` on a single uncropped tile.  `upscale_dem` keeps
 the reference's own contract on top of the two.
+
+Self-ensemble (K14, csrc/scene_tta.hip): `predict_scenes(..., tta="d4")` averages the predictions over the four quarter
+turns and their mirror images.  `prepare_d4` transforms every raster of a sample on the device BEFORE the padding (the
+mirror border is not symmetric), one launch per rot90 parity; `finish_mean` carries up to eight predictions back, averages
+them in fp32 in a fixed order and converts to metres, one launch.
 """
 from __future__ import annotations
 
@@ -218,6 +223,236 @@ def finish(pred: torch.Tensor, scenes, indices: Sequence[int], frame: Frame, met
     return _finish(pred, _table(scenes, indices), scenes, frame, metres, out)
 
 
+# ---- K14 (csrc/scene_tta.hip): the self-ensemble over the flips and quarter turns ----------------------------------------------
+def _element(e):
+    """-> (rot90, flip_lr, flip_ud) from a triple or from K9's code rot90 * 4 + flip_lr * 2 + flip_ud."""
+    if isinstance(e, (int, np.integer)) and not isinstance(e, (bool, np.bool_)):
+        if not 0 <= int(e) < 16:
+            raise ValueError(f"D4 code {e} outside 0..15")
+        return int(e) >> 2, bool(int(e) & 2), bool(int(e) & 1)
+    try:
+        r, lr, ud = e
+    except (TypeError, ValueError):
+        raise ValueError(f"a D4 element is (rot90, flip_lr, flip_ud) or a code 0..15, got {e!r}") from None
+    if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) < 4:
+        raise ValueError(f"D4 element {e!r}: rot90 must be 0..3")
+    for f in (lr, ud):
+        if not isinstance(f, (bool, np.bool_)) and f not in (0, 1):
+            raise ValueError(f"D4 element {e!r}: the flips must be booleans")
+    return int(r), bool(lr), bool(ud)
+
+
+def d4_code(element) -> int:
+    r, lr, ud = _element(element)
+    return r * 4 + lr * 2 + ud
+
+
+def d4_canonical(element):
+    """The same element with flip_ud clear: flipud = fliplr after a half turn, so the 16 codes are 8 elements."""
+    r, lr, ud = _element(element)
+    return ((r + 2) % 4, not lr, False) if ud else (r, lr, False)
+
+
+def d4_elements(spec="d4") -> list:
+    """"d4": the eight elements (r, lr, False), r = 0..3, lr = False, True, in that order; None: the identity alone; a
+    sequence of triples (rot90, flip_lr, flip_ud) or codes: those, as triples, in the order given.  ValueError on a bad
+    value, on an empty sequence and on two entries that denote the same element."""
+    if spec is None:
+        return [(0, False, False)]
+    if isinstance(spec, str):
+        if spec.lower() != "d4":
+            raise ValueError(f"tta: 'd4', None or a sequence of elements, got {spec!r}")
+        return [(r, lr, False) for r in range(4) for lr in (False, True)]
+    out, seen = [], {}
+    for e in spec:
+        t = _element(e)
+        c = d4_canonical(t)
+        if c in seen:
+            raise ValueError(f"tta: {seen[c]} and {t} are the same element")
+        seen[c] = t
+        out.append(t)
+    if not out:
+        raise ValueError("tta: no elements")
+    return out
+
+
+def d4_apply(a, element, axes=(0, 1)):
+    """flipud?(fliplr?(rot90(a, rot90))) over `axes` of a numpy array: the reference's RandomFlipRotate90 order
+    (data/data_utils.py:26-28)."""
+    r, lr, ud = _element(element)
+    a = np.rot90(a, r, axes)
+    a = np.flip(a, axes[1]) if lr else a
+    return np.flip(a, axes[0]) if ud else a
+
+
+def d4_invert(a, element, axes=(0, 1)):
+    """The inverse of `d4_apply`: d4_invert(d4_apply(a, e), e) is a."""
+    r, lr, ud = _element(element)
+    a = np.flip(a, axes[0]) if ud else a
+    a = np.flip(a, axes[1]) if lr else a
+    return np.rot90(a, -r, axes)
+
+
+def _frame_d4(scenes, H, W, parity, pad, multiple, element):
+    """The frame of the transformed shape: (W, H) for an odd rot90; pad after the transform."""
+    h, w = (W, H) if parity else (H, W)
+    n = T.cal_pad(h, w) if pad == "pow2" else int(pad)
+    try:
+        return _device_maps(h, w, n, int(multiple), scenes.device)
+    except ValueError as err:
+        raise ValueError(f"frame_maps: element {element} turns the {H} x {W} scene into {h} x {w}: {err}") from None
+
+
+def _table_d4(scenes, indices, codes):
+    """(device table (len(codes) * B, 3) int32 {scene, base as fp32 bits, code}, element-major; the host codes), kept with
+    the store per (index list, codes) as `_table` keeps its tables."""
+    import ctypes
+    cache = scenes.__dict__.setdefault("_infer_tables", {})
+    key = ("d4", tuple(int(s) for s in indices), tuple(int(c) for c in codes))
+    if key not in cache:
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        base = _rows_of(scenes, key[1])
+        rows = np.concatenate([np.concatenate([base, np.full((len(base), 1), c, dtype=np.int32)], axis=1) for c in key[2]])
+        cache[key] = (_Uploaded((rows,), scenes.device), (ctypes.c_int * len(rows))(*rows[:, 2].tolist()))
+    uploaded, host = cache[key]
+    return uploaded.on_current_stream()[0], host
+
+
+def launch_prepare_d4(scenes, table, codes, rows, cols, Hp, Wp, outs: dict):
+    """The raw call: table (B, 3) int32 on the device, codes its third column on the host (a ctypes int array or a
+    sequence); the rest as `launch_prepare`, the maps those of the transformed shape."""
+    import ctypes
+    if not isinstance(codes, ctypes.Array):
+        codes = (ctypes.c_int * len(codes))(*[int(c) for c in codes])
+    if len(codes) != table.shape[0]:
+        raise ValueError(f"prepare_d4: {len(codes)} codes for {table.shape[0]} samples")
+    P = ctypes_arrays(scenes, outs)
+    _lib.check(_lib.load().jspsr_scene_prepare_d4(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
+                                                  table.data_ptr(), codes, table.shape[0], rows.data_ptr(), cols.data_ptr(), Hp,
+                                                  Wp, scenes.flags, float(scenes.elev_min), float(scenes.elev_max),
+                                                  len(scenes.mask_channel) + 1,
+                                                  torch.cuda.current_stream(scenes.device).cuda_stream), "jspsr_scene_prepare_d4")
+
+
+def _prepare_run(scenes, idx, elements, H, W, pad, multiple, concat):
+    """The samples (element, scene), element-major, of one forward: `elements` must share a frame shape (one rot90 parity,
+    or a square scene).  One launch per parity into batch slices of the same tensors, the even elements first.
+    -> (inputs, {parity: Frame}, the elements in batch order)."""
+    order = [e for e in elements if e[0] % 2 == 0] + [e for e in elements if e[0] % 2 == 1]
+    maps = {p: _frame_d4(scenes, H, W, p, pad, multiple, next(e for e in order if e[0] % 2 == p)) for p in {e[0] % 2 for e in order}}
+    shapes = {(f.Hp, f.Wp) for _, _, f in maps.values()}
+    if len(shapes) != 1:
+        raise ValueError(f"elements {order} of a {H} x {W} scene have frames {sorted(shapes)}: one rot90 parity per forward")
+    Hp, Wp = shapes.pop()
+    nb = len(idx)
+    kinds = _input_kinds(scenes)
+    kw = dict(dtype=torch.float32, device=scenes.device)
+    if concat:
+        inputs = [torch.empty((len(order) * nb, sum(scenes.channels[k] for k in kinds), Hp, Wp), **kw)]
+    else:
+        inputs = [torch.empty((len(order) * nb, scenes.channels[k], Hp, Wp), **kw) for k in kinds]
+    at = 0
+    for p in sorted(maps):
+        rows, cols, _ = maps[p]
+        codes = [d4_code(e) for e in order if e[0] % 2 == p]
+        table, host = _table_d4(scenes, idx, codes)
+        n = len(codes) * nb
+        outs, c0 = {}, 0
+        for j, k in enumerate(kinds):
+            outs[k] = (inputs[0][at:at + n], c0) if concat else (inputs[j][at:at + n], 0)
+            c0 += scenes.channels[k] if concat else 0
+        launch_prepare_d4(scenes, table, host, rows, cols, Hp, Wp, outs)
+        at += n
+    return inputs, {p: f for p, (_, _, f) in maps.items()}, order
+
+
+def prepare_d4(scenes, indices: Sequence[int], elements="d4", pad=0, multiple: int = 8, concat: bool = False) -> dict:
+    """One launch per rot90 parity: the D4 elements `elements` (`d4_elements`) of the scenes `indices` (all of one shape),
+    transformed, THEN padded and brought to ToTensor's range -> {parity: (inputs, frame, order)}.  inputs as `prepare`
+    gives them, the samples element-major: order[j] = (position in `indices`, element) of sample j.  frame: the frame of
+    the transformed shape, (W, H) for parity 1, with the same border and multiple.  The bits of `prepare` on a store of
+    the host-transformed rasters; coord holds the local coordinates of the source pixel."""
+    H, W = _one_shape(scenes, indices)
+    elements = d4_elements(elements)
+    idx = [int(s) for s in indices]
+    out = {}
+    for p in (0, 1):
+        es = [e for e in elements if e[0] % 2 == p]
+        if es:
+            inputs, frames, order = _prepare_run(scenes, idx, es, H, W, pad, multiple, concat)
+            out[p] = (inputs, frames[p], [(j, e) for e in order for j in range(len(idx))])
+    return out
+
+
+def _finish_mean(preds, table, scenes, frames, elements, H, W, metres, out):
+    B = table.shape[0]
+    variants = (_lib.TtaVariant * max(len(preds), 1))()
+    keep = []
+    for k, (pred, frame, e) in enumerate(zip(preds, frames, elements)):
+        if pred.dim() == 3:
+            pred = pred[:, None]
+        if tuple(pred.shape) != (B, 1, frame.Hp, frame.Wp):
+            raise ValueError(f"finish_mean: predictions {tuple(pred.shape)} of element {e}, expected {(B, 1, frame.Hp, frame.Wp)}")
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"finish_mean: fp32 or bf16 predictions, got {pred.dtype}")
+        if pred.device != scenes.device:
+            raise ValueError(f"finish_mean: predictions on {pred.device}, the scenes on {scenes.device}")
+        pred = pred.detach().contiguous()
+        keep.append(pred)
+        if k < len(variants):
+            variants[k] = _lib.TtaVariant(pred.data_ptr(), int(pred.dtype == torch.bfloat16), d4_code(e), frame.Hp, frame.Wp,
+                                          frame.top, frame.left, frame.H, frame.W)
+    _lib.check(_lib.load().jspsr_scene_finish_mean(variants, len(preds), out.data_ptr(), table.data_ptr(), B, H, W,
+                                                   int(bool(metres)), int(bool(scenes.elev_log)), float(scenes.elev_min),
+                                                   float(scenes.elev_max), torch.cuda.current_stream(scenes.device).cuda_stream),
+               "jspsr_scene_finish_mean")
+    return out
+
+
+def finish_mean(preds: Sequence[torch.Tensor], scenes, indices: Sequence[int], frames, elements, metres: bool = True) -> torch.Tensor:
+    """One launch: preds[k] (B, 1, Hp_k, Wp_k), fp32 or bf16, the model's output for element elements[k] of the scenes
+    `indices` -> (B, H, W) fp32: every window carried back by the inverse of its element, (((y'_0 + y'_1) + y'_2) + ...) / K
+    in fp32 in the order given, then `finish`'s metres (or nothing).  frames: {parity: Frame} as `prepare_d4` returns them,
+    or one Frame per prediction.  One element alone, the identity: the bits of `finish`.  A NaN anywhere makes the pixel NaN."""
+    H, W = _one_shape(scenes, indices)
+    elements = [_element(e) for e in elements]
+    if len(preds) != len(elements):
+        raise ValueError(f"finish_mean: {len(preds)} predictions for {len(elements)} elements")
+    if isinstance(frames, dict):
+        frames = [frames[e[0] % 2] for e in elements]
+    if len(frames) != len(elements):
+        raise ValueError(f"finish_mean: {len(frames)} frames for {len(elements)} elements")
+    out = torch.empty((len(indices), H, W), dtype=torch.float32, device=scenes.device)
+    return _finish_mean(list(preds), _table(scenes, indices), scenes, frames, elements, H, W, metres, out)
+
+
+def _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batch_size, pad, multiple, concat, take, metres):
+    """predict_scenes' pass with a self-ensemble: per group of equally shaped scenes, chunks of scenes whose variants ride
+    the batch dimension, at most `batch_size` samples per forward; a square scene's elements share one frame shape, a
+    rectangular scene's rot90 parities have one each."""
+    for (h, w), members in groups.items():
+        even, odd = [e for e in elements if e[0] % 2 == 0], [e for e in elements if e[0] % 2 == 1]
+        sets = [even + odd] if h == w else [s for s in (even, odd) if s]
+        nb = max(1, batch_size // max(len(s) for s in sets))               # scenes per chunk
+        per = max(1, batch_size // nb)                                     # elements per forward
+        for lo in range(0, len(members), nb):
+            idx = [indices[pos] for pos in members[lo:lo + nb]]
+            preds, frames = {}, {}
+            for s in sets:
+                for e0 in range(0, len(s), per):
+                    inputs, fr, order = _prepare_run(scenes, idx, s[e0:e0 + per], h, w, pad, multiple, concat)
+                    pred = model(*[inputs[i] for i in take])
+                    if pred.shape[0] != len(order) * len(idx):
+                        raise ValueError(f"predict_scenes: {len(order) * len(idx)} samples in, {pred.shape[0]} predictions out")
+                    pred = pred.detach().contiguous()
+                    for j, e in enumerate(order):
+                        preds[e], frames[e] = pred[j * len(idx):(j + 1) * len(idx)], fr[e[0] % 2]
+            o = offsets[members[lo]]
+            _finish_mean([preds[e] for e in elements], _table(scenes, idx), scenes, [frames[e] for e in elements], elements, h, w,
+                         metres, buffer[o:o + len(idx) * h * w])
+
+
 def _model_name(model, model_name):
     return str(model_name or getattr(model, "name", None) or type(model).__module__.rsplit(".", 1)[-1]).lower()
 
@@ -254,7 +489,8 @@ class SceneRasters:
 
 @torch.no_grad()
 def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch_size: int = 1, pad=0,
-                   model_name: str | None = None, input_data: dict | None = None, metres: bool = True) -> SceneRasters:
+                   model_name: str | None = None, input_data: dict | None = None, metres: bool = True,
+                   tta=None) -> SceneRasters:
     """Whole scenes through the model: `model.eval()`, no gradients; the scenes are grouped by shape in index order and,
     per group, each batch runs prepare -> forward -> finish (two launches around the forward, written straight into the
     result's buffer).  No host synchronisation anywhere in the pass.
@@ -263,7 +499,14 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     "pow2" for `tiles.cal_pad` (the reference's rule; it asserts that both sides get the same border).  The frame is
     extended to a multiple of `model.size_multiple` (JSPSR 8, LRRU 16, EDSR 1).  model_name / input_data choose the inputs
     as `data.batch_pair` does: JSPSR / LRRU get [lr_dem, image, mask, canopy, coord] as far as input_data names them (None:
-    every kind of the store), any other model the concatenated tensor.  metres=False leaves the network's range."""
+    every kind of the store), any other model the concatenated tensor.  metres=False leaves the network's range.
+
+    tta: None, or the self-ensemble (K14): "d4" or a sequence of D4 elements (`d4_elements`).  Every scene is run in each of
+    the orientations -- transformed, then padded -- and the predictions, carried back, are averaged in fp32 in the order
+    of the elements before the metre conversion (`prepare_d4`, `finish_mean`).  The variants ride the batch dimension:
+    `batch_size` bounds the SAMPLES of a forward.  A square scene's elements share one frame shape; a rectangular scene's
+    quarter turns have the transposed one, so its two rot90 parities are separate forwards."""
+    elements = None if tta is None else d4_elements(tta)
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     indices = list(range(len(scenes))) if indices is None else [int(i) for i in indices]
@@ -284,6 +527,9 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     table = _table(scenes, [indices[pos] for pos in order])
     buffer = torch.empty(total, dtype=torch.float32, device=scenes.device)
     model.eval()
+    if elements is not None:
+        _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batch_size, pad, multiple, concat, take, metres)
+        return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
     at = 0
     for (h, w), members in groups.items():
         n = T.cal_pad(h, w) if pad == "pow2" else int(pad)
