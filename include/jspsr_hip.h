@@ -613,6 +613,49 @@ int jspsr_scene_prepare_d4(const void* const* src, const long long* src_bytes, f
 int jspsr_scene_finish_mean(const jspsr_tta_variant* variants, int K, float* out, const int* samples, int B, int H, int W,
                             int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
 
+/* ---- K15 (ABI v25): tiled whole-scene inference, scenes of any size (csrc/scene_tiles.hip) ------------------
+ * The reference's evaluation protocol -- tiles of the training size, linear ramps in the overlaps (TileCrop,
+ * data/data_utils.py:87-194; gen_weight_row / col + merge_dem, utils/utils.py:802-967) -- for a cover of any H x W scene by
+ * n_y x n_x tiles of kh x kw (jspsr_amd/infer.py: plan_cover makes the origins and the weights).  What these two replace
+ * is host slicing of the decoded rasters per tile, a store of tiles, a jspsr_scene_prepare + jspsr_scene_finish pair, and
+ * the feather merge in numpy.
+ *
+ * jspsr_scene_prepare_windows: as jspsr_scene_prepare without the rows / cols maps; the windows of a batch may come from
+ *   any scenes of the store, of any shapes.
+ *   samples device int32 [B][4] = {scene, base elevation (fp32 bit pattern), y0, x0}.
+ *   out[kind] is (B, cpitch, kh, kw): out[b][c][y][x] = ToTensor_kind(scene[y0 + y][x0 + x][c]), the arithmetic of
+ *   csrc/totensor.h unchanged: the bits of jspsr_scene_prepare's unpadded frame at (y0 + y, x0 + x).  The base is the
+ *   scene's, and coord holds the local coordinates of the source pixel over the WHOLE scene, (y0 + y) / (H - 1) and
+ *   (x0 + x) / (W - 1).  A window pixel outside its scene, and every pixel of a sample whose scene index or store extent
+ *   is bad, is NaN; nothing is read there.  Element offsets are 64-bit (a 37 000 x 37 000 scene's image passes 2^31 bytes).
+ *   16-byte stores when kw % 4 == 0 and out[kind] is 16-byte aligned; otherwise any 4-byte aligned output.
+ *
+ * jspsr_scene_merge_windows: S scenes of one shape H x W and one cover.
+ *   tiles   [S][n_y * n_x][kh][kw], dtype JSPSR_F32 or JSPSR_BF16, the tiles of a scene row-major over the cover;
+ *   oy [n_y], ox [n_x]   device int32, the tile origins;
+ *   wy [n_y][kh], wx [n_x][kw]   device fp32, the weight of tile row ty at its row j (scene row oy[ty] + j), likewise wx;
+ *   lo_y [H], lo_x [W]   device int32, the lowest tile index whose weight at that coordinate is not zero;
+ *   samples device int32 [S][2] as for jspsr_scene_finish (only the base is read).
+ *   out [S][H][W] fp32.  Per pixel (y, x): acc = 0; for ty in {lo_y[y], lo_y[y] + 1}, for tx in {lo_x[x], lo_x[x] + 1}, in
+ *   that (row-major) order, where the tile exists, holds the pixel and wy[ty][y - oy[ty]] != 0 and wx[tx][x - ox[tx]] != 0:
+ *     acc = acc + (m * wx) * wy,   every operation rounded on its own in fp32,
+ *   m = the tile's value after jspsr_scene_finish's expressions (clamp, de-scale, + base) with metres != 0 -- K12's order,
+ *   conversion first and feathering in metres -- and the value widened to fp32 otherwise.  A tile whose weight at a pixel
+ *   is zero is NOT read: a NaN in a trimmed margin does not reach the output.  A gather without atomics: every run gives
+ *   the same bits.  On the reference's own covers (2 x 2, 3 x 3 of a square scene) with border 0: the bits of
+ *   jspsr_scenes_assemble_f32.  16-byte stores when W % 4 == 0 and out is 16-byte aligned.
+ *
+ * Both: JSPSR_EINVAL on a null pointer, a non-positive size (B, S, kh, kw, ...), tiles that cannot cover the scene;
+ * JSPSR_EALIGN on a pointer not aligned to its element size; both decided before any launch.  No host synchronisation. */
+int jspsr_scene_prepare_windows(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
+                                const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples,
+                                int B, int kh, int kw, int flags, double elev_min, double elev_max, int mask_div,
+                                jspsr_stream_t stream);
+int jspsr_scene_merge_windows(int dtype, const void* tiles, const float* wy, const float* wx, const int* lo_y, const int* lo_x,
+                              const int* oy, const int* ox, const int* samples, float* out, int S, int n_y, int n_x, int kh,
+                              int kw, int H, int W, int metres, int elev_log, double elev_min, double elev_max,
+                              jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("JSPSR_LAB_LIB") or os.path.join(_HERE, "lib", "libjspsr_hip.so")  # JSPSR_LAB_LIB: kernel-lab builds only
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _lock = threading.Lock()
 _lib = None
@@ -104,6 +104,8 @@ SIGNATURES = {
     "jspsr_scene_finish": (c_i, [c_i, c_p, c_p, c_p] + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_scene_prepare_d4": (c_i, [c_p] * 7 + [c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_finish_mean": (c_i, [c_p, c_i, c_p, c_p] + [c_i] * 5 + [ctypes.c_double, ctypes.c_double, c_p]),
+    "jspsr_scene_prepare_windows": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_scene_merge_windows": (c_i, [c_i] + [c_p] * 9 + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_nchw_to_nhwc": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
 }
 

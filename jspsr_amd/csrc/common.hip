@@ -55,7 +55,7 @@ std::atomic<int> g_conv_dynq{-1};
 int conv_dynq_override() { return g_conv_dynq.load(std::memory_order_relaxed); }
 }  // namespace jspsr
 
-extern "C" int jspsr_abi_version(void) { return 24; }
+extern "C" int jspsr_abi_version(void) { return 25; }
 extern "C" int jspsr_conv_dynamic_queue(int on) { return jspsr::g_conv_dynq.exchange(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }
 extern "C" long long jspsr_launch_count(const char* what) {
   if (!what) return -1;

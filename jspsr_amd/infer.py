@@ -20,6 +20,14 @@ Self-ensemble (K14, csrc/scene_tta.hip): `predict_scenes(..., tta="d4")` average
 turns and their mirror images.  `prepare_d4` transforms every raster of a sample on the device BEFORE the padding (the
 mirror border is not symmetric), one launch per rot90 parity; `finish_mean` carries up to eight predictions back, averages
 them in fp32 in a fixed order and converts to metres, one launch.
+
+Tiled inference (K15, csrc/scene_tiles.hip): `predict_scenes(..., tile=512, overlap=64, trim=16)` covers every scene that
+is larger than the tile with equal windows (`cover.plan_cover`), gathers them straight from the store (`prepare_windows`,
+windows of different scenes share a batch), and merges the predictions with the cover's ramp weights in metres
+(`merge_windows`, one launch per group of equally shaped scenes).  Activation memory then follows batch_size x tile^2, not
+the scene.  This is the reference's validation protocol -- per-tile channel-gate statistics, zero padding at tile edges,
+linear ramps over the overlaps -- continued to any scene; it is not an exact decomposition of the monolithic forward
+(`tiling.py` is).
 """
 from __future__ import annotations
 
@@ -31,6 +39,7 @@ import torch
 
 from . import _lib
 from . import tiles as T
+from .cover import Cover, plan_cover  # noqa: F401  (part of this module's surface)
 from .data import CONCAT_ORDER, DeviceScenes, ctypes_arrays
 
 Frame = namedtuple("Frame", "Hp Wp top left H W")     # the padded frame and the scene's window in it
@@ -453,6 +462,171 @@ def _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batc
                          metres, buffer[o:o + len(idx) * h * w])
 
 
+# ---- K15 (csrc/scene_tiles.hip): scenes of any size through tiles of one size ------------------------------------------------
+_COVERS = {}                                          # (Cover.key, device) -> _Uploaded((oy, ox, lo_y, lo_x, wy bits, wx bits))
+
+
+def _tile_sides(tile):
+    if isinstance(tile, (int, np.integer)) and not isinstance(tile, (bool, np.bool_)):
+        kh = kw = int(tile)
+    else:
+        try:
+            kh, kw = (int(t) for t in tile)
+        except (TypeError, ValueError):
+            raise ValueError(f"tile: an int or (kh, kw), got {tile!r}") from None
+    if kh < 1 or kw < 1:
+        raise ValueError(f"tile: positive sides, got {(kh, kw)}")
+    return kh, kw
+
+
+def _device_cover(cover: Cover, device):
+    """-> (oy, ox, lo_y, lo_x, wy, wx) on the device (the weights as their int32 bit patterns), cached per cover and device
+    and ordered for the current stream, as `_device_maps`."""
+    key = (cover.key, str(device))
+    if key not in _COVERS:
+        if len(_COVERS) >= _CACHE_LIMIT:
+            _COVERS.clear()
+        hosts = (cover.oy, cover.ox, cover.lo_y, cover.lo_x, np.ascontiguousarray(cover.wy, np.float32).view(np.int32),
+                 np.ascontiguousarray(cover.wx, np.float32).view(np.int32))
+        _COVERS[key] = _Uploaded(hosts, torch.device(device))
+    return _COVERS[key].on_current_stream()
+
+
+def _window_rows(scenes, windows) -> np.ndarray:
+    """The sample table of jspsr_scene_prepare_windows: (B, 4) int32 {scene, base as fp32 bits, y0, x0}."""
+    rows = np.zeros((len(windows), 4), dtype=np.int32)
+    for j, (s, y0, x0) in enumerate(windows):
+        if not 0 <= int(s) < len(scenes):
+            raise IndexError(f"scene {s} of {len(scenes)}")
+        rows[j] = (int(s), np.float32(scenes.base[int(s)]).view(np.int32), int(y0), int(x0))
+    return rows
+
+
+def _window_table(scenes, windows) -> torch.Tensor:
+    """The device copy of `_window_rows`, kept with the store per window list as `_table` keeps its tables."""
+    cache = scenes.__dict__.setdefault("_infer_tables", {})
+    key = ("windows", tuple((int(s), int(y), int(x)) for s, y, x in windows))
+    if key not in cache:
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        cache[key] = _Uploaded((_window_rows(scenes, key[1]),), scenes.device)
+    return cache[key].on_current_stream()[0]
+
+
+def launch_prepare_windows(scenes, table, kh, kw, outs: dict):
+    """The raw call: table (B, 4) int32 on the device; outs kind -> (tensor of (B, cpitch, kh, kw) fp32, first channel)."""
+    P = ctypes_arrays(scenes, outs)
+    _lib.check(_lib.load().jspsr_scene_prepare_windows(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
+                                                       table.data_ptr(), table.shape[0], kh, kw, scenes.flags,
+                                                       float(scenes.elev_min), float(scenes.elev_max), len(scenes.mask_channel) + 1,
+                                                       torch.cuda.current_stream(scenes.device).cuda_stream),
+               "jspsr_scene_prepare_windows")
+
+
+def _prepare_windows(scenes, table, kh, kw, concat):
+    B = table.shape[0]
+    kinds = _input_kinds(scenes)
+    kw_ = dict(dtype=torch.float32, device=scenes.device)
+    outs = {}
+    if concat:
+        images = torch.empty((B, sum(scenes.channels[k] for k in kinds), kh, kw), **kw_)
+        c0 = 0
+        for k in kinds:
+            outs[k] = (images, c0)
+            c0 += scenes.channels[k]
+        inputs = [images]
+    else:
+        for k in kinds:
+            outs[k] = (torch.empty((B, scenes.channels[k], kh, kw), **kw_), 0)
+        inputs = [outs[k][0] for k in kinds]
+    launch_prepare_windows(scenes, table, kh, kw, outs)
+    return inputs
+
+
+def prepare_windows(scenes, windows: Sequence, tile, concat: bool = False):
+    """One launch: the windows (scene, y0, x0) of the store, each `tile` = k or (kh, kw) pixels, of any scenes and shapes ->
+    the model's fp32 (B, C, kh, kw) inputs in `prepare`'s order (concat=True: one tensor).  The bits of `prepare(scenes,
+    [scene], 0, 1)` at [y0:y0 + kh, x0:x0 + kw] -- the base and the local coordinates are the whole scene's; a window
+    pixel outside its scene is NaN."""
+    kh, kw = _tile_sides(tile)
+    if len(windows) == 0:
+        raise ValueError("no windows named")
+    return _prepare_windows(scenes, _window_table(scenes, windows), kh, kw, concat)
+
+
+def _merge_windows(tiles, table, scenes, cover, metres, out):
+    S = table.shape[0]
+    if tiles.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"merge_windows: fp32 or bf16 predictions, got {tiles.dtype}")
+    if tiles.device != scenes.device:
+        raise ValueError(f"merge_windows: predictions on {tiles.device}, the scenes on {scenes.device}")
+    if tiles.numel() != S * cover.n * cover.kh * cover.kw or tuple(tiles.shape[-2:]) != (cover.kh, cover.kw):
+        raise ValueError(f"merge_windows: predictions {tuple(tiles.shape)}, expected {S} x {cover.n} tiles of {cover.kh} x {cover.kw}")
+    tiles = tiles.detach().contiguous()
+    oy, ox, lo_y, lo_x, wy, wx = _device_cover(cover, scenes.device)
+    _lib.check(_lib.load().jspsr_scene_merge_windows(int(tiles.dtype == torch.bfloat16), tiles.data_ptr(), wy.data_ptr(), wx.data_ptr(),
+                                                     lo_y.data_ptr(), lo_x.data_ptr(), oy.data_ptr(), ox.data_ptr(), table.data_ptr(),
+                                                     out.data_ptr(), S, cover.n_y, cover.n_x, cover.kh, cover.kw, cover.H, cover.W,
+                                                     int(bool(metres)), int(bool(scenes.elev_log)), float(scenes.elev_min),
+                                                     float(scenes.elev_max), torch.cuda.current_stream(scenes.device).cuda_stream),
+               "jspsr_scene_merge_windows")
+    return out
+
+
+def merge_windows(pred_tiles: torch.Tensor, scenes, indices: Sequence[int], cover: Cover, metres: bool = True) -> torch.Tensor:
+    """One launch: the predictions (S * n, 1, kh, kw) -- or (S, n, kh, kw) -- of the cover's n tiles, row-major, of the scenes
+    `indices` (all of the cover's shape), fp32 or bf16 -> (S, H, W) fp32.  Every tile goes to metres first as `finish`
+    does (clamp, de-scale, + base; metres=False: as it is), then acc += (m * wx) * wy over the tiles whose weights at the
+    pixel are not zero, row-major.  A tile is not read where its weight is zero."""
+    if _one_shape(scenes, indices) != (cover.H, cover.W):
+        raise ValueError(f"merge_windows: scenes of {tuple(scenes.shapes[int(indices[0])])}, a cover of {(cover.H, cover.W)}")
+    out = torch.empty((len(indices), cover.H, cover.W), dtype=torch.float32, device=scenes.device)
+    return _merge_windows(pred_tiles, _table(scenes, indices), scenes, cover, metres, out)
+
+
+def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffer, batch_size, concat, take, metres):
+    """predict_scenes' pass over the scenes larger than the tile (`tiled`: their positions in `indices`, ascending; `covers`:
+    shape -> Cover, all of one tile).  The windows are listed in scene order, row-major, and cut into forwards of
+    `batch_size`; the predictions land in one tile buffer laid out group by group, so that one merge launch per shape group
+    writes the result."""
+    kh, kw = next((c.kh, c.kw) for c in covers.values())
+    slot, at = {}, 0                                              # position -> first tile of the scene in the tile buffer
+    for shape, members in groups.items():
+        for pos in members:
+            slot[pos] = at
+            at += covers[shape].n
+    windows, slots = [], []
+    for pos in tiled:
+        cover = covers[tuple(scenes.shapes[indices[pos]])]
+        windows += [(indices[pos], y0, x0) for y0, x0 in cover.windows()]
+        slots += range(slot[pos], slot[pos] + cover.n)
+    table = _window_table(scenes, windows)
+    tiles = None
+    for lo in range(0, len(windows), batch_size):
+        B = min(batch_size, len(windows) - lo)
+        inputs = _prepare_windows(scenes, table[lo:lo + B], kh, kw, concat)
+        pred = model(*[inputs[i] for i in take])
+        if pred.dim() == 3:
+            pred = pred[:, None]
+        if tuple(pred.shape) != (B, 1, kh, kw):
+            raise ValueError(f"predict_scenes: {B} windows of {kh} x {kw} in, predictions {tuple(pred.shape)} out")
+        if tiles is None:
+            tiles = torch.empty((len(windows), 1, kh, kw), dtype=pred.dtype, device=scenes.device)
+        j = 0
+        while j < B:                                              # runs of consecutive slots: the windows of one scene
+            e = j + 1
+            while e < B and slots[lo + e] == slots[lo + e - 1] + 1:
+                e += 1
+            tiles[slots[lo + j]:slots[lo + j] + e - j].copy_(pred[j:e])
+            j = e
+    for shape, members in groups.items():
+        idx = [indices[pos] for pos in members]
+        h, w = shape
+        o, t0 = offsets[members[0]], slot[members[0]]
+        _merge_windows(tiles[t0:t0 + len(idx) * covers[shape].n], _table(scenes, idx), scenes, covers[shape], metres,
+                       buffer[o:o + len(idx) * h * w])
+
+
 def _model_name(model, model_name):
     return str(model_name or getattr(model, "name", None) or type(model).__module__.rsplit(".", 1)[-1]).lower()
 
@@ -490,7 +664,7 @@ class SceneRasters:
 @torch.no_grad()
 def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch_size: int = 1, pad=0,
                    model_name: str | None = None, input_data: dict | None = None, metres: bool = True,
-                   tta=None) -> SceneRasters:
+                   tta=None, tile=None, overlap: int | None = None, trim: int = 0) -> SceneRasters:
     """Whole scenes through the model: `model.eval()`, no gradients; the scenes are grouped by shape in index order and,
     per group, each batch runs prepare -> forward -> finish (two launches around the forward, written straight into the
     result's buffer).  No host synchronisation anywhere in the pass.
@@ -505,8 +679,20 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     the orientations -- transformed, then padded -- and the predictions, carried back, are averaged in fp32 in the order
     of the elements before the metre conversion (`prepare_d4`, `finish_mean`).  The variants ride the batch dimension:
     `batch_size` bounds the SAMPLES of a forward.  A square scene's elements share one frame shape; a rectangular scene's
-    quarter turns have the transposed one, so its two rot90 parities are separate forwards."""
+    quarter turns have the transposed one, so its two rot90 parities are separate forwards.
+
+    tile: None, or the tiled pass (K15): k or (kh, kw), a multiple of `model.size_multiple`.  A scene with both sides within
+    the tile runs as above, untiled.  Every other scene is covered by `plan_cover(H, W, tile, overlap, trim)` -- overlap
+    defaults to a quarter of the smaller tile side -- and its windows, listed in scene order and row-major, run in forwards
+    of `batch_size` windows (windows of different scenes and shapes share a batch); the predictions are merged in metres
+    with the cover's ramp weights, one launch per group of equally shaped scenes.  pad must be 0 for such a scene.  Each
+    tile is a forward of its own: channel-gate statistics are per tile and the convolutions see zeros past a tile's edge,
+    as in the reference's tiled validation; `trim` drops that many pixels on the tile sides that face another tile.
+    ValueError for a scene with exactly one side below its tile side (pass a rectangular tile); NotImplementedError
+    together with `tta`."""
     elements = None if tta is None else d4_elements(tta)
+    if tile is not None and elements is not None:
+        raise NotImplementedError("predict_scenes: tile together with tta (a windowed prepare_d4) is not built")
     if batch_size < 1:
         raise ValueError("batch_size must be positive")
     indices = list(range(len(scenes))) if indices is None else [int(i) for i in indices]
@@ -514,9 +700,25 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
         raise ValueError("predict_scenes: no scenes")
     concat, take = _model_inputs(_model_name(model, model_name), scenes, input_data)
     multiple = int(getattr(model, "size_multiple", 1))
+    tiled_groups = {}
+    if tile is not None:
+        kh, kw = _tile_sides(tile)
+        if kh % multiple or kw % multiple:
+            raise ValueError(f"predict_scenes: a tile of {kh} x {kw} is not a multiple of the model's {multiple}")
+        overlap = min(kh, kw) // 4 if overlap is None else int(overlap)
     groups = {}
     for pos, s in enumerate(indices):
         groups.setdefault(tuple(scenes.shapes[s]), []).append(pos)
+    if tile is not None:
+        for (h, w) in groups:
+            if (h < kh) != (w < kw) and not (h <= kh and w <= kw):
+                raise ValueError(f"predict_scenes: a {h} x {w} scene has one side below the {kh} x {kw} tile; pass a rectangular "
+                                 f"tile=(kh, kw) that fits")
+        tiled_groups = {shape: m for shape, m in groups.items() if not (shape[0] <= kh and shape[1] <= kw)}
+        if tiled_groups:
+            if pad != 0:
+                raise ValueError(f"predict_scenes: pad must be 0 for a tiled scene, got {pad!r}")
+            covers = {shape: plan_cover(shape[0], shape[1], (kh, kw), overlap, trim) for shape in tiled_groups}  # raises here
     order, offsets, total = [], [0] * len(indices), 0
     for (h, w), members in groups.items():
         total = (total + 3) // 4 * 4                          # a group starts 16-byte aligned
@@ -530,8 +732,14 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     if elements is not None:
         _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batch_size, pad, multiple, concat, take, metres)
         return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+    if tiled_groups:
+        tiled = sorted(pos for members in tiled_groups.values() for pos in members)
+        _predict_tiled(model, scenes, indices, tiled, tiled_groups, covers, offsets, buffer, batch_size, concat, take, metres)
     at = 0
     for (h, w), members in groups.items():
+        if (h, w) in tiled_groups:
+            at += len(members)
+            continue
         n = T.cal_pad(h, w) if pad == "pow2" else int(pad)
         for lo in range(0, len(members), batch_size):
             B = min(batch_size, len(members) - lo)
