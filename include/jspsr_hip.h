@@ -292,6 +292,16 @@ int jspsr_conv2d_forward(int dtype, const void* in, const void* wpack, const flo
                          int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
                          float* stats, const float* scale, const void* addend, int add_cstride,
                          const float* in_affine, int in_relu, jspsr_stream_t stream);
+/* The same conv reading its input through a PER-IMAGE per-channel scale (ChannelAttention in front of a conv,
+ * basics.py:57-58): in_scale [B][in_scale_bstride] fp32 (16-byte aligned, the stride a multiple of 4 and >= Cin) -- the s
+ * of jspsr_gate_mlp_forward as it stands.  A tile lies inside one image b and reads in[b,..,c] * in_scale[b][c] while it
+ * stages its patch: a plain fp32 multiply rounded once to `dtype`, the bits jspsr_gate_scale would have stored; zero
+ * padding stays zero.  Available where jspsr_conv2d_in_affine_ok(...) != 0; JSPSR_EINVAL otherwise. */
+int jspsr_conv2d_forward_scaled(int dtype, const void* in, const void* wpack, const float* bias, void* out,
+                                int B, int IH, int IW, int Cin, int in_cstride, int in_coff, int Cout,
+                                int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
+                                float* stats, const float* scale, const void* addend, int add_cstride,
+                                const float* in_scale, int in_scale_bstride, jspsr_stream_t stream);
 
 /* gin[b,y,x,c] = bias[c] + sum_{ky,kx,n} gout[b,(y+pad-ky)/stride,(x+pad-kx)/stride,n] * W[n,c,ky,kx]
  * over the taps where the division is exact: the data gradient of the conv above, and equally
@@ -334,6 +344,12 @@ int jspsr_conv2d_wgrad(int dtype, const void* G, int Cg, int g_cstride, int g_co
                        int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
                        int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
                        const float* x_affine, int x_relu, void* workspace, jspsr_stream_t stream);
+/* The weight gradient of jspsr_conv2d_forward_scaled: X is read as X[b,..,c] * x_scale[b][c] (x_scale [B][x_scale_bstride]
+ * fp32, as in_scale there) while it is staged.  Available where jspsr_conv2d_wgrad_x_affine_ok(...) != 0. */
+int jspsr_conv2d_wgrad_scaled(int dtype, const void* G, int Cg, int g_cstride, int g_coff, const void* X, int Cx,
+                              int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
+                              int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
+                              const float* x_scale, int x_scale_bstride, void* workspace, jspsr_stream_t stream);
 
 /* ---- K4/K5: per-channel operators around the convolutions (HBM-bound, NHWC) -----------------
  * Tensors are (pointer, channel pitch, channel offset) slices of NHWC buffers, `npix` pixels,
@@ -714,6 +730,11 @@ size_t jspsr_gate_mlp_backward_workspace_bytes(int B, int C, int Ch);
 int jspsr_gate_mlp_backward(const float* ds, const float* s, const float* hid, const float* avg, const float* mx,
                             const float* w1, const float* w2, int B, int C, int Ch, float* davg, float* dmax, float* dw1,
                             float* dw2, void* workspace, jspsr_stream_t stream);
+/* The two calls above run chip-wide kernels (a wave per hidden unit, a thread per channel).  The earlier kernels -- one
+ * workgroup per image, the same sums in the same order, the same bits -- stay behind this switch for comparison:
+ * on = 1 / 0 selects them / the wide ones, on < 0 only asks; returns the previous setting.  Initial value: the
+ * environment's JSPSR_GATE_MLP_LEGACY (default 0). */
+int jspsr_gate_mlp_legacy(int on);
 
 /* The models' first step with every input (the reference hands them contiguous planar fp32 tensors, utils/utils.py:156-179;
  * models/JSPSR.py:208-222 then feeds the stems): src (B,C,H,W) fp32 -> dst (B,H,W,c_pad) in `dtype`, channels last and

@@ -53,12 +53,14 @@ SIGNATURES = {
     "jspsr_conv2d_stats_rows": (c_i, [c_i, c_i, c_i]),
     "jspsr_conv2d_in_affine_ok": (c_i, [c_i] * 5),
     "jspsr_conv2d_forward": (c_i, [c_i] + [c_p] * 4 + [c_i] * 14 + [c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
+    "jspsr_conv2d_forward_scaled": (c_i, [c_i] + [c_p] * 4 + [c_i] * 14 + [c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
     "jspsr_bn_fold": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_p]),
     "jspsr_conv2d_dgrad_reduce_ok": (c_i, [c_i] * 10),
     "jspsr_conv2d_dgrad": (c_i, [c_i] + [c_p] * 4 + [c_i] * 16 + [c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "jspsr_conv2d_wgrad_workspace_bytes": (ctypes.c_size_t, [c_i] * 8),
     "jspsr_conv2d_wgrad_x_affine_ok": (c_i, [c_i] * 10),
     "jspsr_conv2d_wgrad": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p] + [c_i] * 12 + [c_p, c_i, c_p, c_p]),
+    "jspsr_conv2d_wgrad_scaled": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p] + [c_i] * 12 + [c_p, c_i, c_p, c_p]),
     "jspsr_reduce_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_bn_forward": (c_i, [c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_i,
                                c_i, c_f, c_p, c_p, c_ll, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
@@ -99,6 +101,7 @@ SIGNATURES = {
     "jspsr_gate_mlp_forward": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "jspsr_gate_mlp_backward_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_gate_mlp_backward": (c_i, [c_p] * 7 + [c_i, c_i, c_i] + [c_p] * 6),
+    "jspsr_gate_mlp_legacy": (c_i, [c_i]),
     "jspsr_batch_make": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_prepare": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_finish": (c_i, [c_i, c_p, c_p, c_p] + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),

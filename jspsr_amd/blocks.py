@@ -71,9 +71,12 @@ class ConvUnit(nn.Module):
         self.relu = relu
 
     def forward(self, x, dest=None):
+        c = self.conv[0]
+        if hasattr(self, "camb") and hasattr(self.conv, "bn"):
+            fc = self.camb.fc
+            return E.gated_conv_bn(x, fc[0].weight, fc[1].weight, c.weight, self.conv.bn, self.k // 2, relu=self.relu, dest=dest)
         if hasattr(self, "camb"):
             x = self.camb(x)
-        c = self.conv[0]
         if hasattr(self.conv, "bn"):
             return E.conv_bn(x, c.weight, self.conv.bn, 1, self.k // 2, relu=self.relu, dest=dest)
         return E.conv2d(x, c.weight, c.bias, 1, self.k // 2, relu=self.relu, dest=dest)  # bias + ReLU in the epilogue

@@ -635,16 +635,30 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_p
       preg[i] = make_uint4(v[0], v[1], v[2], v[3]);
     }
     if (g.in_affine) {
-      const float* ap = g.in_affine + chunk * BK + ch * EPC;
+      // (a tile lies inside one image: with in_bstride the table is that image's -- the channel gate's s[b][c])
+      const float* ap = g.in_affine + (size_t)bimg * g.in_bstride + chunk * BK + ch * EPC;
 #pragma unroll
       for (int e = 0; e < EPC; e += 4) {
-        const float4 a = *reinterpret_cast<const float4*>(ap + e), b = *reinterpret_cast<const float4*>(ap + g.Cin + e);
+        const float4 a = *reinterpret_cast<const float4*>(ap + e);
         asc[e] = a.x; asc[e + 1] = a.y; asc[e + 2] = a.z; asc[e + 3] = a.w;
-        ash[e] = b.x; ash[e + 1] = b.y; ash[e + 2] = b.z; ash[e + 3] = b.w;
+      }
+      if (!g.in_scale_only) {
+#pragma unroll
+        for (int e = 0; e < EPC; e += 4) {
+          const float4 b = *reinterpret_cast<const float4*>(ap + g.Cin + e);
+          ash[e] = b.x; ash[e + 1] = b.y; ash[e + 2] = b.z; ash[e + 3] = b.w;
+        }
       }
     }
   };
   auto store_patch = [&]() __attribute__((always_inline)) {
+    if (g.in_affine && g.in_scale_only) {
+#pragma unroll
+      for (int i = 0; i < P_IT; ++i)
+        if (plds[i] >= 0)
+          *reinterpret_cast<uint4*>(Ps + plds[i]) = poff[i] != OOB ? scale16<T>(preg[i], asc) : make_uint4(0u, 0u, 0u, 0u);
+      return;
+    }
     if (g.in_affine) {
       const bool rl = g.in_relu != 0;
 #pragma unroll
@@ -1235,11 +1249,11 @@ extern "C" int jspsr_conv2d_stats_rows(int B, int OH, int OW) {
   return B * ((OH + 7) / 8) * ((OW + 15) / 16);   // one partial row per 8x16-pixel M-tile
 }
 
-extern "C" int jspsr_conv2d_forward(int dtype, const void* in, const void* wpack, const float* bias, void* out,
-                                    int B, int IH, int IW, int Cin, int in_cstride, int in_coff, int Cout,
-                                    int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
-                                    float* stats, const float* scale, const void* addend, int add_cstride,
-                                    const float* in_affine, int in_relu, jspsr_stream_t stream) {
+static int conv2d_forward_impl(int dtype, const void* in, const void* wpack, const float* bias, void* out,
+                               int B, int IH, int IW, int Cin, int in_cstride, int in_coff, int Cout,
+                               int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
+                               float* stats, const float* scale, const void* addend, int add_cstride,
+                               const float* in_affine, int in_relu, int in_bstride, int in_scale_only, jspsr_stream_t stream) {
   if (int e = check_common(dtype, in, wpack, out, Cin, in_cstride, in_coff, out_cstride, out_coff, Cout, "conv2d_forward")) return e;
   if (in_affine && !aligned16(in_affine)) return fail(JSPSR_EALIGN, "conv2d_forward: in_affine must be 16-byte aligned");
   if (addend && add_cstride < Cout) return fail(JSPSR_EINVAL, "conv2d_forward: addend pitch %d < %d channels", add_cstride, Cout);
@@ -1260,8 +1274,28 @@ extern "C" int jspsr_conv2d_forward(int dtype, const void* in, const void* wpack
   if (stats && (bias || relu || scale || addend))
     return fail(JSPSR_EINVAL, "conv2d_forward: statistics are taken from the raw accumulators (no bias / scale / addend / ReLU)");
   g.scale = scale; g.addend = addend; g.add_cstride = add_cstride;
-  g.in_affine = in_affine; g.in_relu = in_relu;
+  g.in_affine = in_affine; g.in_relu = in_relu; g.in_bstride = in_bstride; g.in_scale_only = in_scale_only;
   return dtype == JSPSR_F32 ? launch<float>(in, wpack, bias, out, stats, g, s) : launch<__bf16>(in, wpack, bias, out, stats, g, s);
+}
+
+extern "C" int jspsr_conv2d_forward(int dtype, const void* in, const void* wpack, const float* bias, void* out,
+                                    int B, int IH, int IW, int Cin, int in_cstride, int in_coff, int Cout,
+                                    int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
+                                    float* stats, const float* scale, const void* addend, int add_cstride,
+                                    const float* in_affine, int in_relu, jspsr_stream_t stream) {
+  return conv2d_forward_impl(dtype, in, wpack, bias, out, B, IH, IW, Cin, in_cstride, in_coff, Cout, out_cstride, out_coff, KH, KW,
+                             stride, pad, relu, stats, scale, addend, add_cstride, in_affine, in_relu, 0, 0, stream);
+}
+
+extern "C" int jspsr_conv2d_forward_scaled(int dtype, const void* in, const void* wpack, const float* bias, void* out,
+                                           int B, int IH, int IW, int Cin, int in_cstride, int in_coff, int Cout,
+                                           int out_cstride, int out_coff, int KH, int KW, int stride, int pad, int relu,
+                                           float* stats, const float* scale, const void* addend, int add_cstride,
+                                           const float* in_scale, int in_scale_bstride, jspsr_stream_t stream) {
+  if (!in_scale || in_scale_bstride < Cin || in_scale_bstride % 4)
+    return fail(JSPSR_EINVAL, "conv2d_forward_scaled: in_scale must be [B][in_scale_bstride >= Cin] floats, the stride a multiple of 4");
+  return conv2d_forward_impl(dtype, in, wpack, bias, out, B, IH, IW, Cin, in_cstride, in_coff, Cout, out_cstride, out_coff, KH, KW,
+                             stride, pad, relu, stats, scale, addend, add_cstride, in_scale, 0, in_scale_bstride, 1, stream);
 }
 
 extern "C" int jspsr_conv2d_in_affine_ok(int dtype, int Cin, int KH, int KW, int stride) {

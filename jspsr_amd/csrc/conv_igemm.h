@@ -50,6 +50,8 @@ struct ConvGeom {
   const float* scale;     // optional per-output-channel factor (inference: BatchNorm folded into the epilogue)
   const float* in_affine; // optional [2][Cin] (scale | shift): the gathered tensor is read as [relu](x * scale + shift),
   int in_relu;            // applied while the patch is staged (patch kernel only); zero padding stays zero
+  int in_bstride;         // floats between the tables of consecutive images (0: one table for the batch)
+  int in_scale_only;      // the table is [Cin] scales alone: x * scale, a plain multiply (the channel gate: s[b][c])
   FastDiv fd_ntn, fd_ttx, fd_tty;   // patch kernel: division by its N-tile / tile-column / tile-row counts (set by its launcher)
   // Round 4 -- the reduce pass of a BatchNorm backward in the epilogue of the data gradient that PRODUCES its input gradient
   // (patch kernel, 16-byte epilogue path): red_x = the BatchNorm's saved pre-normalisation tensor on the written grid (channel
@@ -102,7 +104,9 @@ int launch_conv128_resident(const void* in, const void* wgt, const float* bias, 
 
 }  // namespace jspsr
 
-// [relu](x * sc + sh) on 16 bytes of T (4 fp32 / 8 bf16 channels), fp32 arithmetic, one rounding to the storage type
+// [relu](x * sc + sh) on 16 bytes of T (4 fp32 / 8 bf16 channels), fp32 arithmetic, one rounding to the storage type.
+// The fused multiply-add is spelled out: left to contraction, a caller that also forms x * sc for another use (scale16 on
+// the other arm of a select) gets a separate multiply and add here, and other bits.
 template <typename T, int N>
 __device__ __forceinline__ uint4 affine_relu16(const uint4& v, const float (&sc)[N], const float (&sh)[N], bool relu) {
   static_assert(N * sizeof(T) == 16, "one 16-byte chunk of channels");
@@ -111,7 +115,7 @@ __device__ __forceinline__ uint4 affine_relu16(const uint4& v, const float (&sc)
     float f[4] = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f[i] = f[i] * sc[i] + sh[i];
+      f[i] = __builtin_fmaf(f[i], sc[i], sh[i]);
       if (relu) f[i] = fmaxf(f[i], 0.f);
     }
     r = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
@@ -120,9 +124,33 @@ __device__ __forceinline__ uint4 affine_relu16(const uint4& v, const float (&sc)
     unsigned o[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float lo = __uint_as_float(w[i] << 16) * sc[2 * i] + sh[2 * i];
-      float hi = __uint_as_float(w[i] & 0xffff0000u) * sc[2 * i + 1] + sh[2 * i + 1];
+      float lo = __builtin_fmaf(__uint_as_float(w[i] << 16), sc[2 * i], sh[2 * i]);
+      float hi = __builtin_fmaf(__uint_as_float(w[i] & 0xffff0000u), sc[2 * i + 1], sh[2 * i + 1]);
       if (relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
+      const __bf16 bl = (__bf16)lo, bh = (__bf16)hi;
+      o[i] = (unsigned)__builtin_bit_cast(unsigned short, bl) | ((unsigned)__builtin_bit_cast(unsigned short, bh) << 16);
+    }
+    r = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+  return r;
+}
+
+// x * sc on 16 bytes of T, fp32 multiply, one rounding to the storage type: the bits gate_scale_kernel stores
+// (a multiply, not affine_relu16 with a zero shift: -0 + 0 would lose the sign of a zero)
+template <typename T, int N>
+__device__ __forceinline__ uint4 scale16(const uint4& v, const float (&sc)[N]) {
+  static_assert(N * sizeof(T) == 16, "one 16-byte chunk of channels");
+  uint4 r;
+  if constexpr (sizeof(T) == 4) {
+    r = make_uint4(__float_as_uint(__uint_as_float(v.x) * sc[0]), __float_as_uint(__uint_as_float(v.y) * sc[1]),
+                   __float_as_uint(__uint_as_float(v.z) * sc[2]), __float_as_uint(__uint_as_float(v.w) * sc[3]));
+  } else {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    unsigned o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float lo = __uint_as_float(w[i] << 16) * sc[2 * i];
+      const float hi = __uint_as_float(w[i] & 0xffff0000u) * sc[2 * i + 1];
       const __bf16 bl = (__bf16)lo, bh = (__bf16)hi;
       o[i] = (unsigned)__builtin_bit_cast(unsigned short, bl) | ((unsigned)__builtin_bit_cast(unsigned short, bh) << 16);
     }

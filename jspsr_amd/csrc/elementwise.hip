@@ -12,6 +12,7 @@
 // -> bit-reproducible statistics, no atomics.
 #include "common.h"
 
+#include <atomic>
 #include <cstdlib>
 
 namespace {
@@ -1104,6 +1105,179 @@ __global__ __launch_bounds__(GM_T) void gate_mlp_bwd_kernel(const float* __restr
   }
 }
 
+// ---- the same MLP spread over the chip.  The kernels above run one workgroup per image -- 8 of 256 CUs at the training
+// shape -- and walk the hidden units one after the other behind loads a cache line apart per lane: microseconds of
+// arithmetic, up to 241 us of latency on the step's dependency chain.  Below, every (image, hidden unit) and every
+// (image, channel) is a wave / a thread of its own, w2 is read a cache line per instruction or 16 bytes per lane, and
+// every lane keeps a batch of loads in flight.  Every scalar keeps the order of
+// operations of the kernels above (lane l over c = l, l + 64, ... then the xor butterfly; j ascending in the output
+// sums), so the results are theirs bit for bit: JSPSR_GATE_MLP_LEGACY=1 / jspsr_gate_mlp_legacy(1) selects the old
+// kernels for the comparison.
+constexpr int GM_JT = 128;                // hidden units per staged slab of w2 (output kernel)
+constexpr int GM_U = 8;                   // loads of one operand a lane issues back to back before it uses the first: left to
+                                          // the compiler these loops wait for every load in turn (0.5 us each from HBM)
+// Every multiply-add below is the fused one the compiler makes of `z += w * h` in the kernels above, spelled out: in a batch
+// of independent products it would pair the multiplies (v_pk_mul_f32) and add separately -- other bits.
+
+// hid[b][0|1][j] = relu(W1 avg[b]), relu(W1 mx[b]): one wave per (image, hidden unit).  grid (ceil(Ch / 4), B)
+__global__ __launch_bounds__(GM_T) void gate_mlp_hidden_kernel(const float* __restrict__ avg, const float* __restrict__ mx,
+                                                              const float* __restrict__ w1, int C, int Ch, float* __restrict__ hid) {
+  const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int j = blockIdx.x * (GM_T / 64) + wave;
+  if (j >= Ch) return;
+  const float* a = avg + (size_t)b * C;
+  const float* m = mx + (size_t)b * C;
+  const float* w = w1 + (size_t)j * C;
+  float da = 0.f, dm = 0.f;
+  for (int c0 = lane; c0 < C; c0 += 64 * GM_U) {
+    float wv[GM_U], av[GM_U], mv[GM_U];
+#pragma unroll
+    for (int u = 0; u < GM_U; ++u) {
+      const int c = c0 + 64 * u;
+      const bool ok = c < C;
+      wv[u] = ok ? w[c] : 0.f; av[u] = ok ? a[c] : 0.f; mv[u] = ok ? m[c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < GM_U; ++u)
+      if (c0 + 64 * u < C) { da = __builtin_fmaf(wv[u], av[u], da); dm = __builtin_fmaf(wv[u], mv[u], dm); }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) { da += __shfl_xor(da, d, 64); dm += __shfl_xor(dm, d, 64); }
+  if (lane == 0) {
+    hid[((size_t)b * 2 + 0) * Ch + j] = fmaxf(da, 0.f);
+    hid[((size_t)b * 2 + 1) * Ch + j] = fmaxf(dm, 0.f);
+  }
+}
+
+// s[b][c] = sigmoid(sum_j w2[c][j] (ha + hm)[j]): one thread per (image, channel), one wave per 64 channels.  The wave's
+// 64 rows of w2 are one contiguous block of memory: it goes through LDS -- consecutive lanes load consecutive floats, whole
+// cache lines per instruction, in slabs of GM_JT hidden units kept at an odd pitch -- and each lane then walks its own row
+// (the parameters live in a flat buffer at 4-byte alignment, so the loads are 4-byte ones).  grid (ceil(C / 64), B)
+__global__ __launch_bounds__(64) void gate_mlp_out_kernel(const float* __restrict__ hid, const float* __restrict__ w2, int C, int Ch,
+                                                         float* __restrict__ s) {
+  extern __shared__ float gm_lds[];       // [Ch] h_avg + h_max, then [64][pitch] rows of w2
+  constexpr int U = 2 * GM_U;
+  const int b = blockIdx.y, c0 = blockIdx.x * 64, lane = threadIdx.x;
+  const int rows = C - c0 < 64 ? C - c0 : 64;
+  const int jt = Ch < GM_JT ? Ch : GM_JT, pitch = jt | 1;
+  float* h = gm_lds;
+  float* wt = gm_lds + Ch;
+  for (int j = lane; j < Ch; j += 64) h[j] = hid[((size_t)b * 2 + 0) * Ch + j] + hid[((size_t)b * 2 + 1) * Ch + j];
+  float z = 0.f;
+  for (int j0 = 0; j0 < Ch; j0 += jt) {
+    const int n = Ch - j0 < jt ? Ch - j0 : jt, total = rows * n;
+    __syncthreads();                      // the previous slab has been consumed (first pass: h is written)
+    const float* src = w2 + (size_t)c0 * Ch + j0;
+    // element i = r * n + q of the slab, i = lane, lane + 64, ...: (r, q) advance by (64 / n, 64 % n) without a division
+    const int dr = 64 / n, dq = 64 - dr * n;
+    int r = lane / n, q = lane - r * n;
+    for (int i0 = lane; i0 < total; i0 += 64 * U) {
+      int off[U], dst[U];
+      float v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        off[u] = r * Ch + q; dst[u] = r * pitch + q;
+        r += dr; q += dq;
+        if (q >= n) { q -= n; ++r; }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = i0 + 64 * u < total ? src[off[u]] : 0.f;
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (i0 + 64 * u < total) wt[dst[u]] = v[u];
+    }
+    __syncthreads();
+    if (lane < rows) {
+      const float* w = wt + lane * pitch;
+      const float* hj = h + j0;
+      int j = 0;
+      for (; j + GM_U <= n; j += GM_U) {
+        float wv[GM_U], hv[GM_U];
+#pragma unroll
+        for (int u = 0; u < GM_U; ++u) { wv[u] = w[j + u]; hv[u] = hj[j + u]; }
+#pragma unroll
+        for (int u = 0; u < GM_U; ++u) z = __builtin_fmaf(wv[u], hv[u], z);
+      }
+      for (; j < n; ++j) z = __builtin_fmaf(w[j], hj[j], z);
+    }
+  }
+  if (lane < rows) s[(size_t)b * C + c0 + lane] = 1.f / (1.f + expf(-z));
+}
+
+// dz = ds s (1 - s) (kept in dzs by the first workgroup of each image); dh[j] = sum_c w2[c][j] dz[c], masked by the two
+// ReLUs (kept in dhs).  One wave per (image, four consecutive hidden units): lane l takes c = l, l + 64, ... as above and
+// reads the four weights of its row side by side (16 bytes) -- four independent sums per lane, then four butterflies.
+// grid (ceil(Ch / 16), B)
+__global__ __launch_bounds__(GM_T) void gate_mlp_bwd_hidden_kernel(const float* __restrict__ ds, const float* __restrict__ s,
+                                                                  const float* __restrict__ hid, const float* __restrict__ w2, int C,
+                                                                  int Ch, float* __restrict__ dzs, float* __restrict__ dhs) {
+  const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const float* sb = s + (size_t)b * C;
+  const float* dsb = ds + (size_t)b * C;
+  if (blockIdx.x == 0)
+    for (int c = tid; c < C; c += GM_T) { const float sv = sb[c]; dzs[(size_t)b * C + c] = dsb[c] * sv * (1.f - sv); }
+  const int j0 = (blockIdx.x * (GM_T / 64) + wave) * 4;
+  if (j0 >= Ch) return;
+  const int nj = Ch - j0 < 4 ? Ch - j0 : 4;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int c0 = lane; c0 < C; c0 += 64 * GM_U) {
+    float sv[GM_U], dv[GM_U], wv[GM_U][4];
+#pragma unroll
+    for (int u = 0; u < GM_U; ++u) {
+      const int c = c0 + 64 * u;
+      const bool ok = c < C;
+      sv[u] = ok ? sb[c] : 0.f; dv[u] = ok ? dsb[c] : 0.f;
+      const float* w = w2 + (size_t)c * Ch + j0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) wv[u][k] = ok && k < nj ? w[k] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < GM_U; ++u)
+      if (c0 + 64 * u < C) {
+        const float v = dv[u] * sv[u] * (1.f - sv[u]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < nj) acc[k] = __builtin_fmaf(wv[u][k], v, acc[k]);
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float a = acc[k];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) a += __shfl_xor(a, d, 64);
+    const int j = j0 + k;
+    if (lane == 0 && j < Ch) {
+      dhs[((size_t)b * 2 + 0) * Ch + j] = hid[((size_t)b * 2 + 0) * Ch + j] > 0.f ? a : 0.f;
+      dhs[((size_t)b * 2 + 1) * Ch + j] = hid[((size_t)b * 2 + 1) * Ch + j] > 0.f ? a : 0.f;
+    }
+  }
+}
+
+// davg = W1^T dh_a, dmax = W1^T dh_m: one thread per (image, channel); the reads of w1 are coalesced over c as they stand.
+// grid (ceil(C / 64), B)
+__global__ __launch_bounds__(64) void gate_mlp_bwd_in_kernel(const float* __restrict__ dhs, const float* __restrict__ w1, int C, int Ch,
+                                                            float* __restrict__ davg, float* __restrict__ dmax) {
+  extern __shared__ float gm_lds[];       // [2][Ch] dh
+  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
+  for (int j = threadIdx.x; j < 2 * Ch; j += 64) gm_lds[j] = dhs[(size_t)b * 2 * Ch + j];
+  __syncthreads();
+  if (c >= C) return;
+  const float* dh = gm_lds;
+  const float* w = w1 + c;
+  float ga = 0.f, gm = 0.f;
+  int j = 0;
+  for (; j + 2 * GM_U <= Ch; j += 2 * GM_U) {
+    float wv[2 * GM_U];
+#pragma unroll
+    for (int u = 0; u < 2 * GM_U; ++u) wv[u] = w[(size_t)(j + u) * C];
+#pragma unroll
+    for (int u = 0; u < 2 * GM_U; ++u) { ga = __builtin_fmaf(wv[u], dh[j + u], ga); gm = __builtin_fmaf(wv[u], dh[Ch + j + u], gm); }
+  }
+  for (; j < Ch; ++j) { const float wv = w[(size_t)j * C]; ga = __builtin_fmaf(wv, dh[j], ga); gm = __builtin_fmaf(wv, dh[Ch + j], gm); }
+  davg[(size_t)b * C + c] = ga;
+  dmax[(size_t)b * C + c] = gm;
+}
+
 // dw2[c][j] = sum_b dz[b][c] (ha + hm)[b][j];  dw1[j][c] = sum_b dh_a[b][j] avg[b][c] + dh_m[b][j] mx[b][c]  (b in order)
 __global__ __launch_bounds__(GM_T) void gate_mlp_wgrad_kernel(const float* __restrict__ dzs, const float* __restrict__ dhs,
                                                              const float* __restrict__ hid, const float* __restrict__ avg,
@@ -1127,13 +1301,40 @@ __global__ __launch_bounds__(GM_T) void gate_mlp_wgrad_kernel(const float* __res
   }
 }
 
+// -1: not decided yet (JSPSR_GATE_MLP_LEGACY is read at the first call); 0 / 1 once set
+static std::atomic<int> g_gate_mlp_legacy{-1};
+static bool gate_mlp_legacy() {
+  int v = g_gate_mlp_legacy.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("JSPSR_GATE_MLP_LEGACY");
+    v = e && atoi(e) != 0;
+    g_gate_mlp_legacy.store(v, std::memory_order_relaxed);
+  }
+  return v != 0;
+}
+
+extern "C" int jspsr_gate_mlp_legacy(int on) {
+  const int prev = gate_mlp_legacy();
+  if (on >= 0) g_gate_mlp_legacy.store(on != 0, std::memory_order_relaxed);
+  return prev;
+}
+
 extern "C" int jspsr_gate_mlp_forward(const float* avg, const float* mx, const float* w1, const float* w2, int B, int C, int Ch,
                                       float* s, float* hid, jspsr_stream_t stream) {
   if (!avg || !mx || !w1 || !w2 || !s || !hid || B <= 0 || C <= 0 || Ch <= 0 || Ch > 4096)
     return fail(JSPSR_EINVAL, "gate_mlp_forward: bad arguments");
-  hipLaunchKernelGGL(gate_mlp_fwd_kernel, dim3(B), dim3(GM_T), Ch * sizeof(float), static_cast<hipStream_t>(stream), avg, mx, w1, w2,
-                     C, Ch, s, hid);
-  return check_launch("gate_mlp_forward");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (gate_mlp_legacy()) {
+    hipLaunchKernelGGL(gate_mlp_fwd_kernel, dim3(B), dim3(GM_T), Ch * sizeof(float), st, avg, mx, w1, w2, C, Ch, s, hid);
+    return check_launch("gate_mlp_forward");
+  }
+  hipLaunchKernelGGL(gate_mlp_hidden_kernel, dim3((Ch + GM_T / 64 - 1) / (GM_T / 64), B), dim3(GM_T), 0, st, avg, mx, w1, C, Ch, hid);
+  if (int e = check_launch("gate_mlp_hidden")) return e;
+  const int jt = Ch < GM_JT ? Ch : GM_JT;
+  const size_t lds = ((size_t)Ch + 64 * (size_t)(jt | 1)) * sizeof(float);     // <= 49 KiB at Ch = 4096
+  const dim3 grid((C + 63) / 64, B);
+  hipLaunchKernelGGL(gate_mlp_out_kernel, grid, dim3(64), lds, st, hid, w2, C, Ch, s);
+  return check_launch("gate_mlp_out");
 }
 
 extern "C" size_t jspsr_gate_mlp_backward_workspace_bytes(int B, int C, int Ch) {
@@ -1150,9 +1351,17 @@ extern "C" int jspsr_gate_mlp_backward(const float* ds, const float* s, const fl
   float* dzs = static_cast<float*>(workspace);
   float* dhs = dzs + (size_t)B * C;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(gate_mlp_bwd_kernel, dim3(B), dim3(GM_T), (C + 2 * Ch) * sizeof(float), st, ds, s, hid, w1, w2, C, Ch, davg, dmax,
-                     dzs, dhs);
-  if (int e = check_launch("gate_mlp_backward")) return e;
+  if (gate_mlp_legacy()) {
+    hipLaunchKernelGGL(gate_mlp_bwd_kernel, dim3(B), dim3(GM_T), (C + 2 * Ch) * sizeof(float), st, ds, s, hid, w1, w2, C, Ch, davg, dmax,
+                       dzs, dhs);
+    if (int e = check_launch("gate_mlp_backward")) return e;
+  } else {
+    const dim3 grid_h((Ch + 4 * (GM_T / 64) - 1) / (4 * (GM_T / 64)), B);
+    hipLaunchKernelGGL(gate_mlp_bwd_hidden_kernel, grid_h, dim3(GM_T), 0, st, ds, s, hid, w2, C, Ch, dzs, dhs);
+    if (int e = check_launch("gate_mlp_bwd_hidden")) return e;
+    hipLaunchKernelGGL(gate_mlp_bwd_in_kernel, dim3((C + 63) / 64, B), dim3(64), 2 * Ch * sizeof(float), st, dhs, w1, C, Ch, davg, dmax);
+    if (int e = check_launch("gate_mlp_bwd_in")) return e;
+  }
   const long long n2 = 2LL * C * Ch;
   const int blocks = (int)((n2 + GM_T - 1) / GM_T > 2048 ? 2048 : (n2 + GM_T - 1) / GM_T);
   hipLaunchKernelGGL(gate_mlp_wgrad_kernel, dim3(blocks), dim3(GM_T), 0, st, dzs, dhs, hid, avg, mx, B, C, Ch, dw1, dw2);

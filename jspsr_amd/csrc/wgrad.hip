@@ -303,16 +303,19 @@ struct PatchGeom {
   int pairs_g, pairs_x;     // tiles of G channels / chunks of X channels
   const float* x_affine;    // optional [2][Cx] (scale | shift): X is read as [relu](x * scale + shift) while it is staged
   int x_relu;               // (the conv's input was never materialised: see conv.hip, in_affine); padding stays zero
+  int x_bstride;            // floats between the tables of consecutive images (0: one table for the batch)
+  int x_scale_only;         // the table is [Cx] scales alone: X * scale, a plain multiply (the channel gate's s[b][c]; XAFF = 2)
 };
 
 template <typename T> struct WP;
 template <> struct WP<float> { static constexpr int U = 32; };
 template <> struct WP<__bf16> { static constexpr int U = 64; };
 
-// XAFF: X is read through x_affine (+ ReLU) while it is staged -- a separate instantiation, so the plain kernel keeps
-// its register allocation (with the transform compiled in, the bf16 kernel sits at the 256-VGPR limit: every launch
-// measured 13 % slower, transform used or not)
-template <typename T, bool XAFF>
+// XAFF: X is read through x_affine while it is staged (1: scale | shift + ReLU, 2: the per-image scale alone) -- separate
+// instantiations, so the plain kernel keeps its register allocation (with the transform compiled in, the bf16 kernel
+// sits at the 256-VGPR limit: every launch measured 13 % slower, transform used or not) and the scale-only form does
+// not carry the shift's registers
+template <typename T, int XAFF>
 __global__ __launch_bounds__(NT, 2) void wgrad_patch_kernel(const T* __restrict__ G, const T* __restrict__ X,
                                                            float* __restrict__ ws, PatchGeom g) {
   constexpr int EPC = WT<T>::EPC, U = WP<T>::U, TC = 64;      // 64-channel tiles on both sides
@@ -361,12 +364,19 @@ __global__ __launch_bounds__(NT, 2) void wgrad_patch_kernel(const T* __restrict_
   uint4 greg[2][G_IT], xreg[2][X_IT];
   float xsc[EPC], xsh[EPC];                                    // this thread's channel chunk never changes
   if (XAFF && x_ok) {
-    const float* ap = g.x_affine + cx0 + ch * EPC;
+    // (a workgroup's strip lies inside image b: with x_bstride the table is that image's)
+    const float* ap = g.x_affine + (size_t)b * g.x_bstride + cx0 + ch * EPC;
 #pragma unroll
     for (int e = 0; e < EPC; e += 4) {
-      const float4 a = *reinterpret_cast<const float4*>(ap + e), b2 = *reinterpret_cast<const float4*>(ap + g.Cx + e);
+      const float4 a = *reinterpret_cast<const float4*>(ap + e);
       xsc[e] = a.x; xsc[e + 1] = a.y; xsc[e + 2] = a.z; xsc[e + 3] = a.w;
-      xsh[e] = b2.x; xsh[e + 1] = b2.y; xsh[e + 2] = b2.z; xsh[e + 3] = b2.w;
+    }
+    if (XAFF == 1) {
+#pragma unroll
+      for (int e = 0; e < EPC; e += 4) {
+        const float4 b2 = *reinterpret_cast<const float4*>(ap + g.Cx + e);
+        xsh[e] = b2.x; xsh[e + 1] = b2.y; xsh[e + 2] = b2.z; xsh[e + 3] = b2.w;
+      }
     }
   }
   auto load_g = [&](auto SET, int oy) {
@@ -403,7 +413,8 @@ __global__ __launch_bounds__(NT, 2) void wgrad_patch_kernel(const T* __restrict_
     for (int i = 0; i < X_IT; ++i)
       if ((X_IT * RSTEP <= U + 2) || r0 + i * RSTEP < U + 2) {
         uint4 v = xreg[set][i];
-        if (XAFF) v = (rowok && xcol[i] != OOB) ? affine_relu16<T>(v, xsc, xsh, rl) : make_uint4(0u, 0u, 0u, 0u);
+        if (XAFF == 1) v = (rowok && xcol[i] != OOB) ? affine_relu16<T>(v, xsc, xsh, rl) : make_uint4(0u, 0u, 0u, 0u);
+        if (XAFF == 2) v = (rowok && xcol[i] != OOB) ? scale16<T>(v, xsc) : make_uint4(0u, 0u, 0u, 0u);
         *reinterpret_cast<uint4*>(x_st + slot * XS_BYTES + i * RSTEP * P) = v;
       }
   };
@@ -640,7 +651,7 @@ int launch_w(const void* G, const void* X, float* ws, const WgradGeom& g, int sp
 
 template <typename T>
 int run(const void* G, const void* X, float* dW, int R, int C, float* ws, WgradGeom& g, int accumulate, hipStream_t s,
-        const float* x_affine, int x_relu) {
+        const float* x_affine, int x_relu, int x_bstride, int x_scale_only) {
   if (g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad == 1 && g.IH == g.OH && g.IW == g.OW && wgrad_patch_enabled()) {
     const PatchPlan pp = make_patch_plan<T>(g.B, g.OH, g.OW, g.Cg, g.Cx);
     const long long img_g = (long long)g.OH * g.OW * g.g_cs * (long long)sizeof(T);
@@ -653,13 +664,16 @@ int run(const void* G, const void* X, float* dW, int R, int C, float* ws, WgradG
       q.Ktot = g.Ktot; q.strips_x = g.OW / WP<T>::U;
       q.rows_per_blk = pp.rows_per_blk; q.row_blks = pp.row_blks;
       q.pairs_g = (g.Cg + 63) / 64; q.pairs_x = (g.Cx + 63) / 64;
-      q.x_affine = x_affine; q.x_relu = x_relu;
+      q.x_affine = x_affine; q.x_relu = x_relu; q.x_bstride = x_bstride; q.x_scale_only = x_scale_only;
       const long long nblk = (long long)pp.units * q.pairs_g * q.pairs_x;
-      if (x_affine)
-        hipLaunchKernelGGL((wgrad_patch_kernel<T, true>), dim3((unsigned)nblk), dim3(NT), 0, s, static_cast<const T*>(G),
+      if (x_affine && x_scale_only)
+        hipLaunchKernelGGL((wgrad_patch_kernel<T, 2>), dim3((unsigned)nblk), dim3(NT), 0, s, static_cast<const T*>(G),
+                           static_cast<const T*>(X), ws, q);
+      else if (x_affine)
+        hipLaunchKernelGGL((wgrad_patch_kernel<T, 1>), dim3((unsigned)nblk), dim3(NT), 0, s, static_cast<const T*>(G),
                            static_cast<const T*>(X), ws, q);
       else
-        hipLaunchKernelGGL((wgrad_patch_kernel<T, false>), dim3((unsigned)nblk), dim3(NT), 0, s, static_cast<const T*>(G),
+        hipLaunchKernelGGL((wgrad_patch_kernel<T, 0>), dim3((unsigned)nblk), dim3(NT), 0, s, static_cast<const T*>(G),
                            static_cast<const T*>(X), ws, q);
       if (int e = check_launch("conv2d_wgrad_patch")) return e;
       const long long total = (long long)R * g.Ktot;
@@ -705,10 +719,11 @@ extern "C" size_t jspsr_conv2d_wgrad_workspace_bytes(int dtype, int B, int OH, i
   return splits * Cg * Ktot * sizeof(float);
 }
 
-extern "C" int jspsr_conv2d_wgrad(int dtype, const void* G, int Cg, int g_cstride, int g_coff, const void* X, int Cx,
-                                  int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
-                                  int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
-                                  const float* x_affine, int x_relu, void* workspace, jspsr_stream_t stream) {
+static int conv2d_wgrad_impl(int dtype, const void* G, int Cg, int g_cstride, int g_coff, const void* X, int Cx,
+                             int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
+                             int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
+                             const float* x_affine, int x_relu, int x_bstride, int x_scale_only, void* workspace,
+                             jspsr_stream_t stream) {
   if (dtype != JSPSR_F32 && dtype != JSPSR_BF16) return fail(JSPSR_EINVAL, "conv2d_wgrad: bad dtype");
   if (x_affine && !aligned16(x_affine)) return fail(JSPSR_EALIGN, "conv2d_wgrad: x_affine must be 16-byte aligned");
   if (!G || !X || !dW || !workspace) return fail(JSPSR_EINVAL, "conv2d_wgrad: null pointer");
@@ -727,8 +742,26 @@ extern "C" int jspsr_conv2d_wgrad(int dtype, const void* G, int Cg, int g_cstrid
   g.M = (long long)B * OH * OW;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
-  return dtype == JSPSR_F32 ? run<float>(G, X, dW, R, C, ws, g, accumulate, s, x_affine, x_relu)
-                            : run<__bf16>(G, X, dW, R, C, ws, g, accumulate, s, x_affine, x_relu);
+  return dtype == JSPSR_F32 ? run<float>(G, X, dW, R, C, ws, g, accumulate, s, x_affine, x_relu, x_bstride, x_scale_only)
+                            : run<__bf16>(G, X, dW, R, C, ws, g, accumulate, s, x_affine, x_relu, x_bstride, x_scale_only);
+}
+
+extern "C" int jspsr_conv2d_wgrad(int dtype, const void* G, int Cg, int g_cstride, int g_coff, const void* X, int Cx,
+                                  int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
+                                  int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
+                                  const float* x_affine, int x_relu, void* workspace, jspsr_stream_t stream) {
+  return conv2d_wgrad_impl(dtype, G, Cg, g_cstride, g_coff, X, Cx, x_cstride, x_coff, dW, R, C, B, OH, OW, IH, IW, KH, KW, stride, pad,
+                           accumulate, x_affine, x_relu, 0, 0, workspace, stream);
+}
+
+extern "C" int jspsr_conv2d_wgrad_scaled(int dtype, const void* G, int Cg, int g_cstride, int g_coff, const void* X, int Cx,
+                                         int x_cstride, int x_coff, float* dW, int R, int C, int B, int OH, int OW,
+                                         int IH, int IW, int KH, int KW, int stride, int pad, int accumulate,
+                                         const float* x_scale, int x_scale_bstride, void* workspace, jspsr_stream_t stream) {
+  if (!x_scale || x_scale_bstride < Cx || x_scale_bstride % 4)
+    return fail(JSPSR_EINVAL, "conv2d_wgrad_scaled: x_scale must be [B][x_scale_bstride >= Cx] floats, the stride a multiple of 4");
+  return conv2d_wgrad_impl(dtype, G, Cg, g_cstride, g_coff, X, Cx, x_cstride, x_coff, dW, R, C, B, OH, OW, IH, IW, KH, KW, stride, pad,
+                           accumulate, x_scale, 0, x_scale_bstride, 1, workspace, stream);
 }
 
 extern "C" int jspsr_conv2d_wgrad_x_affine_ok(int dtype, int B, int OH, int OW, int Cg, int Cx, int KH, int KW, int stride, int pad) {

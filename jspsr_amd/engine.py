@@ -158,6 +158,16 @@ def channel_gate(x, w1, w2):
     return ops.channel_gate(x, w1, w2)
 
 
+def gated_conv_bn(x, gw1, gw2, weight, bn: torch.nn.BatchNorm2d, padding=1, relu=False, dest=None):
+    """Channel gate -> bias-free conv -> BatchNorm (+ReLU) of a gated Basic2d (basics.py:49-58).  A training step takes
+    one autograd node whose conv reads x through the gate's scale (ops._GatedConvBN); inference, sharded inference and
+    shapes the patch kernels refuse compose the separate operators."""
+    training = bn.training or bn.running_mean is None
+    if _gate_sync is None and training and torch.is_grad_enabled() and ops.gated_conv_ok(x, weight, padding):
+        return ops.gated_conv_bn(x, gw1, gw2, weight, bn.weight, bn.bias, _bn_state(bn), padding, relu, dest)
+    return conv_bn(channel_gate(x, gw1, gw2), weight, bn, 1, padding, relu=relu, dest=dest)
+
+
 def propagate_head(dem, head, w, b, scale=1.0):
     """K1h: sigmoid + propagation straight from the merged 1x1 head's NHWC output (ops.propagate_head)."""
     return ops.propagate_head(dem.contiguous(), head, w, b, scale)

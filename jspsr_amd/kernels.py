@@ -86,12 +86,29 @@ def fused_input_ok(dtype, B, OH, OW, Cin, Cout, KH, KW, stride, pad) -> bool:
         bool(lib.jspsr_conv2d_wgrad_x_affine_ok(dt, B, OH, OW, Cout, Cin, KH, KW, stride, pad))
 
 
+def _chk_scale(t, B, C, name):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (B, C):
+        raise ValueError(f"{name}: expected a contiguous fp32 ({B}, {C}) tensor on the GPU, got {tuple(t.shape)} {t.dtype}")
+
+
+def in_scale_ok(dtype, Cin, KH, KW, stride) -> bool:
+    """Can the forward conv apply a per-channel input transform while staging (in_affine / in_scale: the patch kernels)?"""
+    return bool(_lib.load().jspsr_conv2d_in_affine_ok(F32 if dtype == torch.float32 else BF16, Cin, KH, KW, stride))
+
+
+def x_scale_ok(dtype, B, OH, OW, Cout, Cin, KH, KW, stride, pad) -> bool:
+    """... and the weight gradient (x_affine / x_scale: the nine-tap kernel)?"""
+    return bool(_lib.load().jspsr_conv2d_wgrad_x_affine_ok(F32 if dtype == torch.float32 else BF16, B, OH, OW, Cout, Cin, KH, KW,
+                                                           stride, pad))
+
+
 def conv2d_forward(x, wpack, bias, stride, pad, relu=False, out=None, out_coff=0, cin=None, in_coff=0, stats=False,
-                   scale=None, addend=None, in_affine=None, in_relu=False):
+                   scale=None, addend=None, in_affine=None, in_relu=False, in_scale=None):
     """x (B,IH,IW,Cs) NHWC, wpack [Cout][KH][KW][Cin] -> (B,OH,OW,Cout) (or a slice of `out`).
     stats=True (no bias / ReLU): also returns the BatchNorm partial statistics (rows, 2, Cout) fp32 taken from
     the accumulators in the epilogue.  scale (Cout,) fp32 / addend (B,OH,OW,Cout): inference epilogue
-    out = [relu](acc * scale + bias + addend)."""
+    out = [relu](acc * scale + bias + addend).  in_scale (B, Cin) fp32: the input is read as x[b,..,c] * in_scale[b,c]
+    while it is staged (the channel gate in front of a conv; needs in_scale_ok)."""
     _chk_s(x, "conv2d_forward")
     B, IH, IW, _ = x.shape
     Cs = pitch(x)
@@ -110,15 +127,19 @@ def conv2d_forward(x, wpack, bias, stride, pad, relu=False, out=None, out_coff=0
         _chk_s(addend, "conv2d_forward addend")
         if tuple(addend.shape) != (B, OH, OW, Cout) or addend.dtype != x.dtype:
             raise ValueError(f"conv2d_forward: addend {tuple(addend.shape)} {addend.dtype} does not match the result")
-    _lib.check(lib.jspsr_conv2d_forward(_dt(x), x.data_ptr(), wpack.data_ptr(),
-                                        bias.data_ptr() if bias is not None else None, out.data_ptr(),
-                                        B, IH, IW, Cin, Cs, in_coff, Cout, pitch(out), out_coff,
-                                        KH, KW, stride, pad, int(relu), st.data_ptr() if st is not None else None,
-                                        scale.data_ptr() if scale is not None else None,
-                                        addend.data_ptr() if addend is not None else None,
-                                        pitch(addend) if addend is not None else 0,
-                                        in_affine.data_ptr() if in_affine is not None else None, int(in_relu),
-                                        _stream()), "jspsr_conv2d_forward")
+    head = (_dt(x), x.data_ptr(), wpack.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+            B, IH, IW, Cin, Cs, in_coff, Cout, pitch(out), out_coff, KH, KW, stride, pad, int(relu),
+            st.data_ptr() if st is not None else None, scale.data_ptr() if scale is not None else None,
+            addend.data_ptr() if addend is not None else None, pitch(addend) if addend is not None else 0)
+    if in_scale is not None:
+        if in_affine is not None:
+            raise ValueError("conv2d_forward: in_scale and in_affine exclude each other")
+        _chk_scale(in_scale, B, Cin, "conv2d_forward in_scale")
+        _lib.check(lib.jspsr_conv2d_forward_scaled(*head, in_scale.data_ptr(), in_scale.shape[1], _stream()),
+                   "jspsr_conv2d_forward_scaled")
+    else:
+        _lib.check(lib.jspsr_conv2d_forward(*head, in_affine.data_ptr() if in_affine is not None else None, int(in_relu),
+                                            _stream()), "jspsr_conv2d_forward")
     return (out, st) if stats else out
 
 
@@ -182,8 +203,9 @@ def conv2d_dgrad(g, wpack_t, in_hw, stride, pad, bias=None, relu=False, out=None
 
 
 def conv2d_wgrad(G, X, R, C, KH, KW, stride, pad, out=None, accumulate=False, g_coff=0, cg=None, x_coff=0, cx=None,
-                 x_affine=None, x_relu=False):
-    """dW (R,C,KH,KW) fp32 = sum_pixels G[.., r] * X[shifted.., c].  G (B,OH,OW,Cgs), X (B,IH,IW,Cxs) NHWC."""
+                 x_affine=None, x_relu=False, x_scale=None):
+    """dW (R,C,KH,KW) fp32 = sum_pixels G[.., r] * X[shifted.., c].  G (B,OH,OW,Cgs), X (B,IH,IW,Cxs) NHWC.
+    x_scale (B, cx) fp32: X is read as X[b,..,c] * x_scale[b,c] (the counterpart of conv2d_forward's in_scale)."""
     _chk_s(G, "conv2d_wgrad")
     _chk_s(X, "conv2d_wgrad")
     B, OH, OW, Cg_ = G.shape
@@ -197,10 +219,17 @@ def conv2d_wgrad(G, X, R, C, KH, KW, stride, pad, out=None, accumulate=False, g_
     dt = _dt(G)
     nbytes = lib.jspsr_conv2d_wgrad_workspace_bytes(dt, B, OH, OW, cg, cx, KH, KW)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=G.device)
-    _lib.check(lib.jspsr_conv2d_wgrad(dt, G.data_ptr(), cg, Cgs, g_coff, X.data_ptr(), cx, Cxs, x_coff,
-                                      out.data_ptr(), R, C, B, OH, OW, IH, IW, KH, KW, stride, pad,
-                                      int(accumulate), x_affine.data_ptr() if x_affine is not None else None, int(x_relu),
-                                      ws.data_ptr(), _stream()), "jspsr_conv2d_wgrad")
+    head = (dt, G.data_ptr(), cg, Cgs, g_coff, X.data_ptr(), cx, Cxs, x_coff, out.data_ptr(), R, C, B, OH, OW, IH, IW, KH, KW,
+            stride, pad, int(accumulate))
+    if x_scale is not None:
+        if x_affine is not None:
+            raise ValueError("conv2d_wgrad: x_scale and x_affine exclude each other")
+        _chk_scale(x_scale, B, cx, "conv2d_wgrad x_scale")
+        _lib.check(lib.jspsr_conv2d_wgrad_scaled(*head, x_scale.data_ptr(), x_scale.shape[1], ws.data_ptr(), _stream()),
+                   "jspsr_conv2d_wgrad_scaled")
+    else:
+        _lib.check(lib.jspsr_conv2d_wgrad(*head, x_affine.data_ptr() if x_affine is not None else None, int(x_relu),
+                                          ws.data_ptr(), _stream()), "jspsr_conv2d_wgrad")
     return out
 
 
@@ -399,6 +428,12 @@ def gate_mlp_forward(avg, mx, w1, w2):
     _lib.check(lib.jspsr_gate_mlp_forward(avg.data_ptr(), mx.data_ptr(), w1.data_ptr(), w2.data_ptr(), B, C, Ch, s.data_ptr(),
                                           hid.data_ptr(), _stream()), "jspsr_gate_mlp_forward")
     return s, hid
+
+
+def gate_mlp_legacy(on: int = -1) -> bool:
+    """Select (1) / deselect (0) the one-workgroup-per-image gate MLP kernels, which the chip-wide ones replaced and
+    reproduce bit for bit; on < 0 only asks.  Returns the previous setting."""
+    return bool(_lib.load().jspsr_gate_mlp_legacy(int(on)))
 
 
 def gate_mlp_backward(ds, s, hid, avg, mx, w1, w2):

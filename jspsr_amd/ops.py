@@ -1140,3 +1140,84 @@ class _ChannelGate(torch.autograd.Function):
 
 def channel_gate(x, w1, w2):
     return _ChannelGate.apply(x, w1, w2)
+
+
+# ChannelAttention -> conv3x3 -> BatchNorm of a gated ConvUnit without the scaled tensor: the conv (and its weight gradient)
+# read x through the gate's per-image scale s[b][c] while they stage their operand (jspsr_conv2d_forward_scaled,
+# jspsr_conv2d_wgrad_scaled), so gate_scale's pass over the tensor and the saved x * s disappear.  Where the patch kernels
+# do not apply the unit keeps the separate pass; where only the nine-tap weight-gradient kernel does not (image width not a
+# multiple of its strip), the backward re-forms x * s for the weight gradient alone.  JSPSR_GATE_FUSE=0: the separate pass
+# everywhere (Switches).
+gate_fuse = os.environ.get("JSPSR_GATE_FUSE", "1") != "0"
+
+
+def gated_conv_ok(x, weight, pad) -> bool:
+    """Can _GatedConvBN take this unit?  (3x3, stride 1, pad 1 on the patch kernels, no channel padding.)"""
+    if not gate_fuse or x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+        return False
+    B, H, W, Cp = x.shape
+    O, I, KH, KW = weight.shape
+    return Cp == I and O % K.epc(x.dtype) == 0 and KH == 3 and KW == 3 and pad == 1 and K.in_scale_ok(x.dtype, I, 3, 3, 1)
+
+
+class _GatedConvBN(torch.autograd.Function):
+    """[relu](bn(conv3x3(x * s))), s = sigmoid(MLP(avgpool x) + MLP(maxpool x)) (basics.py:49-58), training mode, as one
+    autograd node.  The kernels and their results are those of _ChannelGate -> _Conv -> _BatchNorm, bit for bit, minus
+    gate_scale: y = x * s is formed inside the conv's and the weight gradient's staging and never stored."""
+
+    @staticmethod
+    def forward(ctx, x, gw1, gw2, weight, gamma, beta, bn, pad, relu, dest):
+        x = x.contiguous()
+        cdt = x.dtype
+        B, H, W, Cp = x.shape
+        O, I, KH, KW = weight.shape
+        rm, rv, mom, eps, training = bn
+        avg, mx, amax = K.gate_pool(x)
+        w1f, w2f = gw1.detach().float().flatten(1).contiguous(), gw2.detach().float().flatten(1).contiguous()
+        s, hid = K.gate_mlp_forward(avg, mx, w1f, w2f)
+        wd = weight.detach().contiguous()
+        ctx.wparam = weight if isinstance(weight, torch.nn.Parameter) else None
+        z, st = K.conv2d_forward(x, _packed(weight, wd, 0, Cp, cdt), None, 1, pad, False, stats=True, in_scale=s)
+        out_v = dest[0].slice(dest[1], O, z.shape[:3]) if dest is not None else None
+        gd, bd = gamma.detach(), beta.detach()
+        out, mean, invstd = K.bn_forward(z, gd, bd, rm, rv, mom, eps, training, relu, None, 1.0, partial=st, out=out_v)
+        ctx.gb = tuple(p if isinstance(p, torch.nn.Parameter) else None for p in (gamma, beta))
+        ctx.cfg = (pad, 2 if relu else 0, training)    # the ReLU mask is a function of z alone: recomputed (bn_backward relu=2)
+        ctx.wshapes = (gw1.shape, gw2.shape, gw1.dtype, gw2.dtype)
+        ctx.save_for_backward(x, avg, mx, amax, s, hid, w1f, w2f, wd, z, gd, bd, mean, invstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        pad, mode, training = ctx.cfg
+        x, avg, mx, amax, s, hid, w1f, w2f, wd, z, gamma, beta, mean, invstd = ctx.saved_tensors
+        cdt = x.dtype
+        B, H, W, I = x.shape
+        O = wd.shape[0]
+        sink = _bn_sink(*ctx.gb)
+        dz, _, dg, db = K.bn_backward(K.nhwc(dout), None, z, gamma, mean, invstd, training, mode, 1.0, beta=beta, grads_into=sink)
+        if sink is not None:
+            _bn_ready(*ctx.gb)
+        pw = ctx.wparam
+
+        def wgrad():   # the conv's input x * s was never materialised: its weight gradient re-forms it while staging
+            if K.x_scale_ok(cdt, B, H, W, O, I, 3, 3, 1, pad):
+                return _wgrad_async(pw, dz, x, O, I, 3, 3, 1, pad, x_scale=s)
+            return _wgrad_async(pw, dz, K.gate_scale(x, s), O, I, 3, 3, 1, pad)
+
+        if not wgrad_after_dgrad:
+            dW = wgrad()
+        dy = K.conv2d_dgrad(dz, _packed(pw, wd, 1, O, cdt), (H, W), 1, pad)
+        if wgrad_after_dgrad:
+            dW = wgrad()
+        del dz
+        ds = K.gate_backward_reduce(dy, x)
+        davg, dmax, dw1, dw2 = K.gate_mlp_backward(ds, s, hid, avg, mx, w1f, w2f)
+        dx = K.gate_backward_apply(dy, s, davg, dmax, amax)
+        s1, s2, t1, t2 = ctx.wshapes
+        return dx, dw1.reshape(s1).to(t1), dw2.reshape(s2).to(t2), dW, dg, db, None, None, None, None
+
+
+def gated_conv_bn(x, gw1, gw2, weight, gamma, beta, bn, pad, relu=False, dest=None):
+    """bn: (running_mean, running_var, momentum, eps, training).  Ask gated_conv_ok first."""
+    return _GatedConvBN.apply(x, gw1, gw2, weight, gamma, beta, bn, pad, relu, dest)
