@@ -672,6 +672,33 @@ int jspsr_scene_merge_windows(int dtype, const void* tiles, const float* wy, con
                               int kw, int H, int W, int metres, int elev_log, double elev_min, double elev_max,
                               jspsr_stream_t stream);
 
+/* ---- K16 (ABI v25, additive): the self-ensemble per window of a tiled scene (csrc/scene_tiles_tta.hip) --------
+ * jspsr_scene_prepare_windows_d4: jspsr_scene_prepare_windows composed with K14's D4 map, a window and a code per sample.
+ *   What it replaces is jspsr_scene_prepare_windows followed by a flip / rot90 of every input tensor of every sample.
+ *   samples device int32 [B][5] = {scene, base elevation (fp32 bit pattern), y0, x0, code}, code = rot90 * 4 + flip_lr * 2 +
+ *     flip_ud as for jspsr_scene_prepare_d4;
+ *   codes   HOST int32 [B], the same codes: every rot90 of a launch has one parity (JSPSR_EINVAL otherwise), so that one
+ *     output shape serves it -- (B, cpitch, kh, kw) for an even rot90, (B, cpitch, kw, kh) for an odd one.
+ *   out[b][c][i][j] = ToTensor_kind(scene[y0 + sy][x0 + sx][c]) with (sy, sx) the pixel of the kh x kw window that the
+ *   element flipud?(fliplr?(rot90(window, rot90))) puts at (i, j): the bits of jspsr_scene_prepare_windows' output moved
+ *   by the transform.  The base, H and W are the scene's own, so coord holds the local coordinates of the SOURCE pixel over
+ *   the whole scene; a source pixel outside its scene is NaN, and so is every pixel of a sample whose scene index or store
+ *   extent is bad or whose device code is outside 0..15 or of the other parity.  The windows of a launch may come from any
+ *   scenes and shapes of the store.  Element offsets are 64-bit.
+ *   Even rot90: jspsr_scene_prepare_windows' streaming kernel with rows and columns walked forwards or backwards.  Odd
+ *   rot90: 32 x 32 output tiles, the pre-image staged in LDS (an output row walks a source column); B <= 65535.
+ *   16-byte stores when the output row length (kw even, kh odd) is a multiple of 4 and out[kind] is 16-byte aligned;
+ *   otherwise any 4-byte aligned output.
+ *   JSPSR_EINVAL: a null pointer, B <= 0 or > 65535, kh <= 0, kw <= 0, a code outside 0..15, two parities, an hr_dem
+ *   output, bad channel counts, both image ranges; JSPSR_EALIGN: a pointer not aligned to its element size; all decided
+ *   before any launch.  No host synchronisation.
+ * The mean of a window's predictions is jspsr_scene_finish_mean with the tile as its scene (H = kh, W = kw, metres = 0), and
+ * the merge jspsr_scene_merge_windows on those fp32 tiles: no further entry point. */
+int jspsr_scene_prepare_windows_d4(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
+                                   const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples,
+                                   const int* codes, int B, int kh, int kw, int flags, double elev_min, double elev_max,
+                                   int mask_div, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

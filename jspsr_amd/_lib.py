@@ -109,6 +109,7 @@ SIGNATURES = {
     "jspsr_scene_finish_mean": (c_i, [c_p, c_i, c_p, c_p] + [c_i] * 5 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_scene_prepare_windows": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_merge_windows": (c_i, [c_i] + [c_p] * 9 + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
+    "jspsr_scene_prepare_windows_d4": (c_i, [c_p] * 7 + [c_i, c_p, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_nchw_to_nhwc": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
 }
 

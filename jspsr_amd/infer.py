@@ -28,6 +28,11 @@ windows of different scenes share a batch), and merges the predictions with the 
 the scene.  This is the reference's validation protocol -- per-tile channel-gate statistics, zero padding at tile edges,
 linear ramps over the overlaps -- continued to any scene; it is not an exact decomposition of the monolithic forward
 (`tiling.py` is).
+
+Tiled self-ensemble (K16, csrc/scene_tiles_tta.hip): `predict_scenes(..., tile=512, window_tta="d4")` keeps the upright cover
+and runs every WINDOW in each orientation: `prepare_windows_d4` gathers and transforms in one launch per rot90 parity,
+`mean_windows` (K14's finish_mean, the tile as its scene) carries the predictions back and averages them in fp32, and
+`merge_windows` feathers the mean tiles in metres.
 """
 from __future__ import annotations
 
@@ -627,6 +632,194 @@ def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffe
                        buffer[o:o + len(idx) * h * w])
 
 
+# ---- K16 (csrc/scene_tiles_tta.hip): the self-ensemble per window of a tiled scene -------------------------------------------
+def _window_table_d4(scenes, windows, codes):
+    """(device table (len(codes) * B, 5) int32 {scene, base as fp32 bits, y0, x0, code}, element-major; the host codes), kept
+    with the store per (window list, codes) as `_window_table` keeps its tables."""
+    import ctypes
+    cache = scenes.__dict__.setdefault("_infer_tables", {})
+    key = ("windows_d4", tuple((int(s), int(y), int(x)) for s, y, x in windows), tuple(int(c) for c in codes))
+    if key not in cache:
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        base = _window_rows(scenes, key[1])
+        rows = np.concatenate([np.concatenate([base, np.full((len(base), 1), c, dtype=np.int32)], axis=1) for c in key[2]])
+        cache[key] = (_Uploaded((rows,), scenes.device), (ctypes.c_int * len(rows))(*rows[:, 4].tolist()))
+    uploaded, host = cache[key]
+    return uploaded.on_current_stream()[0], host
+
+
+def launch_prepare_windows_d4(scenes, table, codes, kh, kw, outs: dict):
+    """The raw call: table (B, 5) int32 on the device, codes its fifth column on the host (a ctypes int array or a sequence),
+    all of one rot90 parity; outs kind -> (tensor of (B, cpitch, kh, kw) fp32 -- (B, cpitch, kw, kh) for an odd rot90 --,
+    first channel)."""
+    import ctypes
+    if not isinstance(codes, ctypes.Array):
+        codes = (ctypes.c_int * len(codes))(*[int(c) for c in codes])
+    if len(codes) != table.shape[0]:
+        raise ValueError(f"prepare_windows_d4: {len(codes)} codes for {table.shape[0]} samples")
+    P = ctypes_arrays(scenes, outs)
+    _lib.check(_lib.load().jspsr_scene_prepare_windows_d4(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(),
+                                                          len(scenes), table.data_ptr(), codes, table.shape[0], kh, kw, scenes.flags,
+                                                          float(scenes.elev_min), float(scenes.elev_max),
+                                                          len(scenes.mask_channel) + 1,
+                                                          torch.cuda.current_stream(scenes.device).cuda_stream),
+               "jspsr_scene_prepare_windows_d4")
+
+
+def _prepare_windows_run(scenes, windows, elements, kh, kw, concat):
+    """The samples (element, window), element-major, of one forward: `elements` must share an output shape (one rot90 parity,
+    or a square tile).  One launch per parity into batch slices of the same tensors, the even elements first.
+    -> (inputs, the elements in batch order)."""
+    order = [e for e in elements if e[0] % 2 == 0] + [e for e in elements if e[0] % 2 == 1]
+    shapes = {(kw, kh) if e[0] % 2 else (kh, kw) for e in order}
+    if len(shapes) != 1:
+        raise ValueError(f"elements {order} of a {kh} x {kw} window have shapes {sorted(shapes)}: one rot90 parity per forward")
+    oh, ow = shapes.pop()
+    nb = len(windows)
+    kinds = _input_kinds(scenes)
+    kw_ = dict(dtype=torch.float32, device=scenes.device)
+    if concat:
+        inputs = [torch.empty((len(order) * nb, sum(scenes.channels[k] for k in kinds), oh, ow), **kw_)]
+    else:
+        inputs = [torch.empty((len(order) * nb, scenes.channels[k], oh, ow), **kw_) for k in kinds]
+    at = 0
+    for p in (0, 1):
+        codes = [d4_code(e) for e in order if e[0] % 2 == p]
+        if not codes:
+            continue
+        table, host = _window_table_d4(scenes, windows, codes)
+        n = len(codes) * nb
+        outs, c0 = {}, 0
+        for j, k in enumerate(kinds):
+            outs[k] = (inputs[0][at:at + n], c0) if concat else (inputs[j][at:at + n], 0)
+            c0 += scenes.channels[k] if concat else 0
+        launch_prepare_windows_d4(scenes, table, host, kh, kw, outs)
+        at += n
+    return inputs, order
+
+
+def prepare_windows_d4(scenes, windows: Sequence, tile, elements="d4", concat: bool = False) -> dict:
+    """One launch per rot90 parity: the D4 elements `elements` (`d4_elements`) of the windows (scene, y0, x0) of the store,
+    each `tile` = k or (kh, kw) pixels, of any scenes and shapes -> {parity: (inputs, order)}.  inputs as `prepare_windows`
+    gives them -- (B, C, kh, kw) for parity 0, (B, C, kw, kh) for parity 1 --, the samples element-major: order[j] = (position
+    in `windows`, element) of sample j.  The bits of `prepare_windows` moved by flipud?(fliplr?(rot90(window, rot90))): the
+    base and the local coordinates are those of the source pixel in its whole scene, a source pixel outside its scene is
+    NaN."""
+    kh, kw = _tile_sides(tile)
+    if len(windows) == 0:
+        raise ValueError("no windows named")
+    elements = d4_elements(elements)
+    windows = [(int(s), int(y), int(x)) for s, y, x in windows]
+    out = {}
+    for p in (0, 1):
+        es = [e for e in elements if e[0] % 2 == p]
+        if es:
+            inputs, order = _prepare_windows_run(scenes, windows, es, kh, kw, concat)
+            out[p] = (inputs, [(j, e) for e in order for j in range(len(windows))])
+    return out
+
+
+def _mean_windows(preds, elements, kh, kw, table, out):
+    """jspsr_scene_finish_mean with the tile as its scene: preds[k] (N, 1, kh, kw) -- (N, 1, kw, kh) for an odd rot90 -- of
+    element elements[k]; table a device (N, 2) int32 table (read, not used: metres = 0); out (N, 1, kh, kw) fp32."""
+    N = table.shape[0]
+    variants = (_lib.TtaVariant * max(len(preds), 1))()
+    keep = []
+    for k, (pred, e) in enumerate(zip(preds, elements)):
+        oh, ow = (kw, kh) if e[0] % 2 else (kh, kw)
+        if pred.dim() == 3:
+            pred = pred[:, None]
+        if tuple(pred.shape) != (N, 1, oh, ow):
+            raise ValueError(f"mean_windows: predictions {tuple(pred.shape)} of element {e}, expected {(N, 1, oh, ow)}")
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"mean_windows: fp32 or bf16 predictions, got {pred.dtype}")
+        if pred.device != out.device:
+            raise ValueError(f"mean_windows: predictions on {pred.device} and on {out.device}")
+        pred = pred.detach().contiguous()
+        keep.append(pred)
+        if k < len(variants):
+            variants[k] = _lib.TtaVariant(pred.data_ptr(), int(pred.dtype == torch.bfloat16), d4_code(e), oh, ow, 0, 0, oh, ow)
+    _lib.check(_lib.load().jspsr_scene_finish_mean(variants, len(preds), out.data_ptr(), table.data_ptr(), N, kh, kw, 0, 0, 0.0, 1.0,
+                                                   torch.cuda.current_stream(out.device).cuda_stream), "jspsr_scene_finish_mean")
+    return out
+
+
+def mean_windows(preds: Sequence[torch.Tensor], elements, tile) -> torch.Tensor:
+    """One launch: preds[k] (N, 1, kh, kw) -- (N, 1, kw, kh) for an odd rot90 --, fp32 or bf16, the model's output for element
+    elements[k] of N windows of `tile` = k or (kh, kw) -> (N, 1, kh, kw) fp32 in the network's range: every tile carried back
+    by the inverse of its element, (((y'_0 + y'_1) + y'_2) + ...) / K in fp32 in the order given (`finish_mean` with the tile
+    as its scene and metres=False).  One element alone, the identity: the input widened to fp32.  `merge_windows` takes the
+    result."""
+    kh, kw = _tile_sides(tile)
+    elements = [_element(e) for e in elements]
+    preds = list(preds)
+    if len(preds) != len(elements):
+        raise ValueError(f"mean_windows: {len(preds)} predictions for {len(elements)} elements")
+    if not preds:
+        raise ValueError("mean_windows: no predictions")
+    N, device = preds[0].shape[0], preds[0].device
+    table = torch.zeros((N, 2), dtype=torch.int32, device=device)
+    out = torch.empty((N, 1, kh, kw), dtype=torch.float32, device=device)
+    return _mean_windows(preds, elements, kh, kw, table, out)
+
+
+def _predict_tiled_tta(model, scenes, indices, tiled, groups, covers, offsets, buffer, batch_size, concat, take, metres, elements):
+    """`_predict_tiled` with a self-ensemble per window: the windows, listed as there, go in chunks of nb windows whose
+    variants ride the batch dimension, at most `batch_size` samples per forward (`_predict_tta`'s rule, the tile in the place
+    of the scene: a square tile's elements share one shape, a rectangular tile's rot90 parities have one each).  Per chunk
+    one finish_mean launch writes the fp32 mean tiles into the tile buffer; then `_predict_tiled`'s merge."""
+    kh, kw = next((c.kh, c.kw) for c in covers.values())
+    slot, at = {}, 0                                              # position -> first tile of the scene in the tile buffer
+    for shape, members in groups.items():
+        for pos in members:
+            slot[pos] = at
+            at += covers[shape].n
+    windows, slots = [], []
+    for pos in tiled:
+        cover = covers[tuple(scenes.shapes[indices[pos]])]
+        windows += [(indices[pos], y0, x0) for y0, x0 in cover.windows()]
+        slots += range(slot[pos], slot[pos] + cover.n)
+    even, odd = [e for e in elements if e[0] % 2 == 0], [e for e in elements if e[0] % 2 == 1]
+    sets = [even + odd] if kh == kw else [s for s in (even, odd) if s]
+    nb = max(1, batch_size // max(len(s) for s in sets))              # windows per chunk
+    per = max(1, batch_size // nb)                                    # elements per forward
+    tiles = torch.empty((len(windows), 1, kh, kw), dtype=torch.float32, device=scenes.device)
+    for lo in range(0, len(windows), nb):
+        chunk = windows[lo:lo + nb]
+        B = len(chunk)
+        preds = {}
+        for s in sets:
+            for e0 in range(0, len(s), per):
+                inputs, order = _prepare_windows_run(scenes, chunk, s[e0:e0 + per], kh, kw, concat)
+                pred = model(*[inputs[i] for i in take])
+                if pred.dim() == 3:
+                    pred = pred[:, None]
+                if tuple(pred.shape) != (len(order) * B, 1) + tuple(inputs[0].shape[2:]):
+                    raise ValueError(f"predict_scenes: {len(order) * B} windows of {tuple(inputs[0].shape[2:])} in, predictions "
+                                     f"{tuple(pred.shape)} out")
+                pred = pred.detach().contiguous()
+                for j, e in enumerate(order):
+                    preds[e] = pred[j * B:(j + 1) * B]
+        table = _table(scenes, [w[0] for w in chunk])
+        one_run = all(slots[lo + j] == slots[lo] + j for j in range(B))
+        out = tiles[slots[lo]:slots[lo] + B] if one_run else torch.empty((B, 1, kh, kw), dtype=torch.float32, device=scenes.device)
+        _mean_windows([preds[e] for e in elements], elements, kh, kw, table, out)
+        j = 0
+        while not one_run and j < B:                                  # runs of consecutive slots: the windows of one scene
+            e = j + 1
+            while e < B and slots[lo + e] == slots[lo + e - 1] + 1:
+                e += 1
+            tiles[slots[lo + j]:slots[lo + j] + e - j].copy_(out[j:e])
+            j = e
+    for shape, members in groups.items():
+        idx = [indices[pos] for pos in members]
+        h, w = shape
+        o, t0 = offsets[members[0]], slot[members[0]]
+        _merge_windows(tiles[t0:t0 + len(idx) * covers[shape].n], _table(scenes, idx), scenes, covers[shape], metres,
+                       buffer[o:o + len(idx) * h * w])
+
+
 def _model_name(model, model_name):
     return str(model_name or getattr(model, "name", None) or type(model).__module__.rsplit(".", 1)[-1]).lower()
 
@@ -664,7 +857,7 @@ class SceneRasters:
 @torch.no_grad()
 def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch_size: int = 1, pad=0,
                    model_name: str | None = None, input_data: dict | None = None, metres: bool = True,
-                   tta=None, tile=None, overlap: int | None = None, trim: int = 0) -> SceneRasters:
+                   tta=None, tile=None, overlap: int | None = None, trim: int = 0, window_tta=None) -> SceneRasters:
     """Whole scenes through the model: `model.eval()`, no gradients; the scenes are grouped by shape in index order and,
     per group, each batch runs prepare -> forward -> finish (two launches around the forward, written straight into the
     result's buffer).  No host synchronisation anywhere in the pass.
@@ -689,7 +882,23 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     tile is a forward of its own: channel-gate statistics are per tile and the convolutions see zeros past a tile's edge,
     as in the reference's tiled validation; `trim` drops that many pixels on the tile sides that face another tile.
     ValueError for a scene with exactly one side below its tile side (pass a rectangular tile); NotImplementedError
-    together with `tta`."""
+    together with `tta`.
+
+    window_tta: None, or the self-ensemble per window (K16), with `tile`: what `tta` takes.  This is not a tiled `tta` --
+    that would cover the TRANSFORMED scene, and a cover's origins are not mirror-symmetric: the upright cover stays, and
+    every window is run in each orientation (`prepare_windows_d4`).  A scene within the tile runs as with tta=window_tta:
+    its one window is the scene.  The windows of the other scenes go in chunks of nb = max(1, batch_size // m) windows, m
+    the largest set of elements that share a shape -- all of them for a square tile, the larger rot90 parity for a
+    rectangular one -- and each set in forwards of max(1, batch_size // nb) elements, even rot90 before odd, element-major,
+    so that `batch_size` still bounds the samples of a forward.  Per chunk one launch carries the predictions back and
+    averages them in fp32 in the order of the elements (`mean_windows`); the fp32 mean tiles are then merged as above, the
+    mean before the metres as with `tta`.  window_tta=[(0, False, False)] gives the bits of the plain tiled pass.
+    ValueError without `tile` and together with `tta`."""
+    window_elements = None if window_tta is None else d4_elements(window_tta)
+    if window_elements is not None and tile is None:
+        raise ValueError("predict_scenes: window_tta transforms the windows of a tiled pass; give tile (or use tta)")
+    if window_elements is not None and tta is not None:
+        raise ValueError("predict_scenes: window_tta together with tta; the scene-level ensemble of a tiled pass is not built")
     elements = None if tta is None else d4_elements(tta)
     if tile is not None and elements is not None:
         raise NotImplementedError("predict_scenes: tile together with tta (a windowed prepare_d4) is not built")
@@ -734,7 +943,15 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
         return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
     if tiled_groups:
         tiled = sorted(pos for members in tiled_groups.values() for pos in members)
-        _predict_tiled(model, scenes, indices, tiled, tiled_groups, covers, offsets, buffer, batch_size, concat, take, metres)
+        if window_elements is not None:
+            _predict_tiled_tta(model, scenes, indices, tiled, tiled_groups, covers, offsets, buffer, batch_size, concat, take,
+                               metres, window_elements)
+        else:
+            _predict_tiled(model, scenes, indices, tiled, tiled_groups, covers, offsets, buffer, batch_size, concat, take, metres)
+    if window_elements is not None:                               # the scenes within the tile: their one window is the scene
+        whole = {shape: members for shape, members in groups.items() if shape not in tiled_groups}
+        _predict_tta(model, scenes, indices, window_elements, whole, offsets, buffer, batch_size, pad, multiple, concat, take, metres)
+        return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
     at = 0
     for (h, w), members in groups.items():
         if (h, w) in tiled_groups:
