@@ -699,6 +699,44 @@ int jspsr_scene_prepare_windows_d4(const void* const* src, const long long* src_
                                    const int* codes, int B, int kh, int kw, int flags, double elev_min, double elev_max,
                                    int mask_div, jspsr_stream_t stream);
 
+/* ---- K17 (ABI v25, additive): voids in whole-scene inference (csrc/scene_voids.hip) --------------------------
+ * Real DEM tiles have voids (sea, data gaps, no-data values).  What these entries replace is a Euclidean feature transform
+ * and a gather on the host, a second upload of the store, and a numpy np.where over the results.
+ *
+ * jspsr_scene_nearest_seed: for every pixel of every scene of a store, the nearest seed pixel of the SAME scene.
+ *   seed    device uint8 [pixels], flat, the scenes back to back in the store's pixel layout; non-zero = seed;
+ *   scenes  device int64 [n_scenes][3] = {pixel offset, H, W} (the store's scene table); scenes_host the same on the HOST
+ *     (the sizes are checked and the grids sized from it before any launch);
+ *   limit   0 = none, else a pixel whose nearest seed is farther than `limit` pixels (d2 > limit^2) finds none;
+ *   src, d2 device int32 [pixels]: src = y_s * W + x_s of the seed inside its scene, d2 = dy^2 + dx^2; a seed pixel has
+ *     src = itself and d2 = 0; both are -1 where the scene has no seed or none within the limit.
+ *   The rule: among the seeds of the scene the one that minimises (dy^2 + dx^2, |dx|, dx, dy) lexicographically, d = seed -
+ *   query.  Exact, integer, the same bits on every run.  Sides are at most 32767 (d2 < 2^31): a larger one is JSPSR_EINVAL,
+ *   not a launch.  A search never crosses a scene boundary.  On the device every scene is checked against `pixels` again; one
+ *   that does not fit is skipped.
+ *   Phase 1, per column: the vertical distance to the column's nearest seed, ties to the upper one, int16, in `workspace`
+ *   (jspsr_scene_nearest_seed_workspace_bytes, 2 B per pixel, 2-byte aligned); the columns are cut into bands of 64 rows,
+ *   a thread per (band, column), so that a tall narrow scene fills the chip.  Phase 2, per row: the row's column distances
+ *   staged in LDS; every pixel walks outwards x, x-1, x+1, x-2, ... over k^2 + g^2, strict improvements only, until
+ *   k^2 >= best or k > limit.  Cost O(distance to the nearest seed) per query.  Three kernels, one call; src and d2 double
+ *   as scratch between them.
+ * jspsr_scene_fill_voids: in place on the fp32 lr_dem store, dem[p] = void[p] ? (src[p] >= 0 ? dem[scene offset + src[p]] :
+ *   base[scene]) : dem[p].  src as jspsr_scene_nearest_seed gives it for seed = not void (NULL: every void gets the base);
+ *   base device fp32 [n_scenes].  A source that is itself a void, or outside its scene, counts as none: no value is both
+ *   read and written.
+ * jspsr_scene_mask_out: rows device int64 [n_rows][3] = {offset into out, offset into void_out, pixels};
+ *   out[row offset + i] = nodata where void_out[plane offset + i] is set, i < pixels; out has out_len elements and void_out
+ *   `pixels` bytes, a row that leaves either is skipped.  One launch for all scenes of a predict_scenes call.
+ * All: JSPSR_EINVAL on a null pointer, a non-positive size, a negative limit, a scene outside the plane; JSPSR_EALIGN on a
+ * pointer not aligned to its element size; decided before any launch.  No host synchronisation. */
+size_t jspsr_scene_nearest_seed_workspace_bytes(long long pixels);
+int jspsr_scene_nearest_seed(const unsigned char* seed, long long pixels, const long long* scenes, const long long* scenes_host,
+                             int n_scenes, int limit, int* src, int* d2, void* workspace, jspsr_stream_t stream);
+int jspsr_scene_fill_voids(float* dem, const unsigned char* void_plane, const int* src, long long pixels,
+                           const long long* scenes, int n_scenes, const float* base, jspsr_stream_t stream);
+int jspsr_scene_mask_out(float* out, long long out_len, const unsigned char* void_out, long long pixels,
+                         const long long* rows, int n_rows, float nodata, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -110,6 +110,10 @@ SIGNATURES = {
     "jspsr_scene_prepare_windows": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_merge_windows": (c_i, [c_i] + [c_p] * 9 + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_scene_prepare_windows_d4": (c_i, [c_p] * 7 + [c_i, c_p, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_scene_nearest_seed_workspace_bytes": (ctypes.c_size_t, [c_ll]),
+    "jspsr_scene_nearest_seed": (c_i, [c_p, c_ll, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "jspsr_scene_fill_voids": (c_i, [c_p, c_p, c_p, c_ll, c_p, c_i, c_p, c_p]),
+    "jspsr_scene_mask_out": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_i, c_f, c_p]),
     "jspsr_nchw_to_nhwc": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
 }
 

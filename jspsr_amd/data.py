@@ -44,6 +44,19 @@ def _as_hwc(a, kind: str, i: int) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def void_pixels(a: np.ndarray, nodata) -> np.ndarray:
+    """The voids of an fp32 raster: not finite, or -- unless `nodata` is NaN -- equal to np.float32(nodata)."""
+    v = ~np.isfinite(a)
+    nd = np.float32(nodata)
+    return v if np.isnan(nd) else v | (a == nd)
+
+
+def _whole(name: str, v) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+        raise ValueError(f"{name}: a whole number of pixels >= 0, got {v!r}")
+    return int(v)
+
+
 class DeviceScenes:
     """Decoded scenes, uploaded once, in the layout `DFC30.__getitem__` holds them: lr_dem / hr_dem fp32 (H,W,1), image
     uint8 (H,W,3), mask uint8 (H,W,C) (the `mask_channel` selection already applied), canopy uint8 (H,W,1); lists of numpy
@@ -54,23 +67,34 @@ class DeviceScenes:
     `min - base - elev_min >= 1` and every scaled value in [0, 1].  The scaling is monotone, so a scene that passes cannot
     give a crop that fails.  This is stricter than the reference: a scene whose only bad pixels no crop ever covers is
     refused here.  `elev_min` / `elev_max` are the config's Python numbers (tensor_kwargs min / max).
+
+    Voids (no-data pixels) are not taken here: `nodata` raises NotImplementedError together with `hr_dem`.  The store without
+    a ground truth, `infer.InferenceScenes(nodata=...)`, fills them on the device at construction (K17).
     """
 
     def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
                  relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
-                 normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda"):
+                 normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda", nodata=None):
         if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
             raise KeyError("hr_dem")
+        if nodata is not None:
+            raise NotImplementedError("nodata: voids in a store with hr_dem (training, scores over valid pixels) are not built; "
+                                      "`infer.InferenceScenes` takes them")
         self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device)
 
     def _setup(self, raw: dict, coord, *, relative, elev_min, elev_max, elev_log, scale_mask, mask_channel, image_range,
-               label_range, normalize, ids, device, base=None):
+               label_range, normalize, ids, device, base=None, nodata=None, void_margin=0, fill_limit=None):
         """Checks, layout and upload of a store holding the kinds of `raw` that are not None (`infer.InferenceScenes` is
-        the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`."""
+        the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`.  nodata, void_margin,
+        fill_limit: the voids of lr_dem (K17, `infer.InferenceScenes`); nodata=None changes nothing."""
         lr_dem = raw["lr_dem"]
+        void_margin = _whole("void_margin", void_margin)
+        fill_limit = None if fill_limit is None else _whole("fill_limit", fill_limit)
+        if nodata is not None and raw.get("hr_dem") is not None:
+            raise NotImplementedError("nodata: voids in a store with hr_dem are not built")
         if coord not in (None, "local"):
             if str(coord).lower() == "global":
                 raise NotImplementedError("coord='global' needs the scenes' georeferencing; only 'local' is built")
@@ -114,13 +138,24 @@ class DeviceScenes:
         if coord and any(h < 2 or w < 2 for h, w in self.shapes):
             raise ValueError("local coordinates need scenes of at least 2 x 2 pixels")
         self.ids = [str(i) for i in range(n)] if ids is None else [str(i) for i in ids]
-        self.base = [np.min(a) if relative else 0 for a in host["lr_dem"]]
+        voids = None
+        if nodata is not None:
+            voids = [void_pixels(a, nodata) for a in host["lr_dem"]]
+            for i, v in enumerate(voids):
+                if v.all():
+                    raise ValueError(f"scene {self.ids[i]}: no valid pixel, every lr_dem value is a void")
+            self.base = [np.min(a[~v]) if relative else 0 for a, v in zip(host["lr_dem"], voids)]
+        else:
+            self.base = [np.min(a) if relative else 0 for a in host["lr_dem"]]
         if base is not None:
             if len(base) != n:
                 raise ValueError(f"base: {len(base)} values, lr_dem has {n} scenes")
             self.base = list(base)
         for i in range(n):
-            self._check_scene(i, {k: v[i] for k, v in host.items()})
+            s = {k: v[i] for k, v in host.items()}
+            if voids is not None:
+                s["lr_dem"] = s["lr_dem"][~voids[i]]                 # the range checks read the valid pixels only
+            self._check_scene(i, s)
         offs = np.zeros(n + 1, dtype=np.int64)
         offs[1:] = np.cumsum([h * w for h, w in self.shapes])
         self.scene_table = torch.tensor([[int(offs[i]), h, w] for i, (h, w) in enumerate(self.shapes)], dtype=torch.int64,
@@ -129,6 +164,49 @@ class DeviceScenes:
         self.store = {k: torch.from_numpy(np.concatenate([a.reshape(-1) for a in v])).to(self.device) for k, v in host.items()}
         self.flags = ((LOG if elev_log else 0) | (SCALE_MASK if scale_mask else 0) | (IMAGE_11 if image_range == "[-1, 1]" else 0)
                       | (LABEL_11 if label_range == "[-1, 1]" else 0) | (IMAGE_255 if image_range == "[0, 255]" else 0))
+        if voids is not None:
+            self._fill_voids(voids, nodata, void_margin, fill_limit)
+
+    # K17: the members of a store built with `nodata`; None otherwise (and then absent from the instance)
+    nodata = void = void_out = void_counts = None
+    void_margin, fill_limit = 0, None
+
+    def _fill_voids(self, voids: list, nodata, void_margin: int, fill_limit):
+        """The device side of `nodata` (K17, csrc/scene_voids.hip), once, at construction: upload the void plane, replace
+        every void of store["lr_dem"] by its nearest valid pixel of the same scene (`infer.nearest_seed`'s rule; farther than
+        `fill_limit`: the scene's base) and make the output mask, void or within `void_margin` of one.  A store without a
+        single void launches nothing and keeps its bits."""
+        from . import infer                                          # infer imports this module
+        self.nodata, self.void_margin, self.fill_limit = nodata, void_margin, fill_limit
+        self.void_counts = [int(v.sum()) for v in voids]
+        plane = np.concatenate([v.reshape(-1) for v in voids]).astype(np.uint8)
+        self.void = torch.from_numpy(plane).to(self.device)
+        self.void_out = self.void
+        if sum(self.void_counts) == 0:
+            return
+        host_table = np.array([[0, h, w] for h, w in self.shapes], dtype=np.int64)
+        host_table[1:, 0] = np.cumsum([h * w for h, w in self.shapes])[:-1]
+        src = None
+        if fill_limit is None or fill_limit > 0:
+            src, _ = infer._nearest_seed(self.void ^ 1, self.scene_table, host_table, fill_limit or 0)
+        base = torch.tensor([float(np.float32(b)) for b in self.base], dtype=torch.float32, device=self.device)
+        infer.fill_voids(self.store["lr_dem"], self.void, src, self.scene_table, base)
+        del src
+        if void_margin > 0:
+            _, d2 = infer._nearest_seed(self.void, self.scene_table, host_table, void_margin)
+            self.void_out = (d2 >= 0).to(torch.uint8)
+
+    def void_mask(self, i: int, out: bool = False) -> torch.Tensor:
+        """(H, W) bool view on the device of scene i's voids; out=True: of its output mask (void or within `void_margin`
+        of one).  Only for a store built with `nodata`."""
+        plane = self.void_out if out else self.void
+        if plane is None:
+            raise ValueError("void_mask: the store was built without nodata")
+        if not 0 <= int(i) < len(self):
+            raise IndexError(f"scene {i} of {len(self)}")
+        h, w = self.shapes[int(i)]
+        o = sum(a * b for a, b in self.shapes[:int(i)])
+        return plane[o:o + h * w].view(h, w).view(torch.bool)
 
     def __len__(self):
         return len(self.shapes)

@@ -124,15 +124,27 @@ def _device_maps(H, W, pad, multiple, device):
 class InferenceScenes(DeviceScenes):
     """`data.DeviceScenes` without a ground truth: decoded scenes, uploaded once, in the same flat HWC layout with the same
     members (`store`, `scene_table`, `base`, `flags`, `channels`, `shapes`, `ids`) and the same whole-scene range checks.
-    base: per-scene base elevations to use instead of `np.min(lr_dem)` (upscale_dem's `meta["base"]`)."""
+    base: per-scene base elevations to use instead of `np.min(lr_dem)` (upscale_dem's `meta["base"]`).
+
+    Voids (K17, csrc/scene_voids.hip).  nodata=None: no scene may hold one (today's checks, nothing else happens).
+    Otherwise an lr_dem pixel is a void when it is not finite, or -- unless nodata is NaN -- equals np.float32(nodata).  The
+    base (`np.min` when `relative`) and the range checks then read the valid pixels only; a scene without one is a
+    ValueError that names it.  The void plane is uploaded (`void`: flat uint8 in the store's pixel layout; `void_counts` per
+    scene; `void_mask(i)`), and once, at construction, every void of store["lr_dem"] is replaced on the device by the value of
+    its nearest valid pixel of the same scene (`nearest_seed`'s rule) -- farther than `fill_limit` pixels from valid data:
+    by the scene's base; fill_limit=0: every void.  After that the store is read-only and finite: prepare, the ensembles and
+    the tiled passes read it unchanged.  `void_out` (`void_mask(i, out=True)`): void, or within the Euclidean distance
+    `void_margin` of one (0: `void` itself, the same tensor); `predict_scenes(mask_voids=True)` writes np.float32(nodata)
+    there.  Voids in image, mask or canopy, voids together with hr_dem, and scores over valid pixels are not built."""
 
     def __init__(self, lr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *, relative: bool = False,
                  elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, ids: Sequence[str] | None = None,
-                 device="cuda", base: Sequence | None = None):
+                 device="cuda", base: Sequence | None = None, nodata=None, void_margin: int = 0, fill_limit: int | None = None):
         self._setup({"lr_dem": lr_dem, "hr_dem": None, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
-                    image_range=image_range, label_range=None, normalize=None, ids=ids, device=device, base=base)
+                    image_range=image_range, label_range=None, normalize=None, ids=ids, device=device, base=base,
+                    nodata=nodata, void_margin=void_margin, fill_limit=fill_limit)
 
 
 def _input_kinds(scenes):
@@ -820,6 +832,129 @@ def _predict_tiled_tta(model, scenes, indices, tiled, groups, covers, offsets, b
                        buffer[o:o + len(idx) * h * w])
 
 
+# ---- K17 (csrc/scene_voids.hip): voids -- the nearest-seed transform, the fill and the output mask ------------------------------
+MAX_SIDE = 32767                                      # scene sides of the transform: d2 < 2^31
+
+
+def _host_table(shapes_or_table) -> np.ndarray:
+    """(n, 3) int64 {pixel offset, H, W} on the host from a list of (H, W) shapes (scenes back to back) or from such a
+    table, a numpy array or a tensor (a device tensor is copied back: a synchronisation)."""
+    a = shapes_or_table
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a, dtype=np.int64)
+    if a.ndim != 2 or a.shape[1] not in (2, 3) or a.shape[0] == 0:
+        raise ValueError(f"nearest_seed: a list of (H, W) shapes or an (n, 3) table {{offset, H, W}}, got shape {a.shape}")
+    if a.shape[1] == 3:
+        return np.ascontiguousarray(a)
+    table = np.zeros((len(a), 3), dtype=np.int64)
+    table[:, 1:] = a
+    table[1:, 0] = np.cumsum(a[:, 0] * a[:, 1])[:-1]
+    return table
+
+
+def _nearest_seed(seed, table, host_table, limit: int):
+    """The raw call: seed flat uint8 on the device, table (n, 3) int64 on the device and its host copy, limit >= 1 or 0 for
+    none -> (src, d2) int32.  The workspace (2 B per pixel) is freed on return; the allocator keeps it until the stream
+    has passed the launches."""
+    if seed.dtype != torch.uint8 or seed.dim() != 1 or not seed.is_contiguous() or not seed.is_cuda:
+        raise ValueError(f"nearest_seed: a flat contiguous uint8 plane on the device, got {seed.dtype} {tuple(seed.shape)} on {seed.device}")
+    n = seed.numel()
+    lib = _lib.load()
+    host_table = np.ascontiguousarray(host_table, dtype=np.int64)
+    src = torch.empty(n, dtype=torch.int32, device=seed.device)
+    d2 = torch.empty(n, dtype=torch.int32, device=seed.device)
+    work = torch.empty(max(1, lib.jspsr_scene_nearest_seed_workspace_bytes(n)), dtype=torch.uint8, device=seed.device)
+    _lib.check(lib.jspsr_scene_nearest_seed(seed.data_ptr(), n, table.data_ptr(), host_table.ctypes.data, len(host_table), int(limit),
+                                            src.data_ptr(), d2.data_ptr(), work.data_ptr(),
+                                            torch.cuda.current_stream(seed.device).cuda_stream), "jspsr_scene_nearest_seed")
+    return src, d2
+
+
+def nearest_seed(seed: torch.Tensor, shapes_or_scene_table, limit: int | None = None):
+    """Three kernels, one call: for every pixel of a flat uint8 device plane `seed` (non-zero = seed) that holds the scenes
+    `shapes_or_scene_table` -- a list of (H, W), back to back, or an (n, 3) int64 table {pixel offset, H, W} such as a
+    store's `scene_table` -- its nearest seed of the SAME scene -> (src, d2), flat int32 on the device.
+
+    The rule: of all seeds of the scene the one that minimises (dy^2 + dx^2, |dx|, dx, dy) lexicographically, d = seed -
+    query.  src = y_s * W + x_s inside the scene, d2 the squared distance; a seed has src = itself, d2 = 0.  Both are -1 where
+    the scene has no seed, or none within `limit` pixels (d2 > limit^2; None: no limit; 0: only the seeds themselves find
+    one).  Exact and integer: every run gives the same bits.  Sides are at most 32767."""
+    host = _host_table(shapes_or_scene_table)
+    if limit is not None and (isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) or int(limit) < 0):
+        raise ValueError(f"nearest_seed: limit is None or a whole number >= 0, got {limit!r}")
+    if isinstance(shapes_or_scene_table, torch.Tensor) and shapes_or_scene_table.device == seed.device \
+            and shapes_or_scene_table.dtype == torch.int64 and shapes_or_scene_table.is_contiguous():
+        table = shapes_or_scene_table
+    else:
+        table = torch.from_numpy(host).to(seed.device)
+    src, d2 = _nearest_seed(seed, table, host, 1 if limit == 0 else int(limit or 0))
+    if limit == 0:                                                    # the entry's 0 means none: run with 1, keep the seeds
+        far = d2 != 0
+        src, d2 = src.masked_fill_(far, -1), d2.masked_fill_(far, -1)
+    return src, d2
+
+
+def fill_voids(dem: torch.Tensor, void: torch.Tensor, src, scene_table: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """One launch, in place on a flat fp32 device buffer of scenes (a store's lr_dem): dem[p] = dem[scene offset + src[p]]
+    where void[p] is set -- the scene's base[scene] where src[p] is -1, or everywhere with src=None -- and dem[p] elsewhere.
+    src: `nearest_seed` of the plane `void ^ 1`; scene_table (n, 3) int64 and base (n,) fp32 on the device.  A source that
+    is itself a void counts as none, so no value is both read and written."""
+    n = dem.numel()
+    for name, t, dt in (("dem", dem, torch.float32), ("void", void, torch.uint8), ("src", src, torch.int32), ("base", base, torch.float32),
+                        ("scene_table", scene_table, torch.int64)):
+        if t is None and name == "src":
+            continue
+        if t.dtype != dt or not t.is_contiguous() or t.device != dem.device or not t.is_cuda:
+            raise ValueError(f"fill_voids: {name} must be a contiguous {dt} tensor on {dem.device}")
+        if name in ("void", "src") and t.numel() != n:
+            raise ValueError(f"fill_voids: {name} has {t.numel()} elements, dem {n}")
+    if scene_table.dim() != 2 or scene_table.shape[1] != 3 or base.numel() != scene_table.shape[0]:
+        raise ValueError(f"fill_voids: scene_table {tuple(scene_table.shape)}, base {tuple(base.shape)}")
+    _lib.check(_lib.load().jspsr_scene_fill_voids(dem.data_ptr(), void.data_ptr(), None if src is None else src.data_ptr(), n,
+                                                  scene_table.data_ptr(), scene_table.shape[0], base.data_ptr(),
+                                                  torch.cuda.current_stream(dem.device).cuda_stream), "jspsr_scene_fill_voids")
+    return dem
+
+
+def mask_out(out: torch.Tensor, void_out: torch.Tensor, rows: torch.Tensor, nodata) -> torch.Tensor:
+    """One launch, in place on a flat fp32 device buffer: out[rows[r][0] + i] = np.float32(nodata) where
+    void_out[rows[r][1] + i] is set, i < rows[r][2]; rows (m, 3) int64 on the device {offset into out, offset into the
+    plane, pixels}; a row that leaves either buffer is skipped."""
+    if out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("mask_out: out must be a contiguous fp32 tensor on the device")
+    if void_out.dtype != torch.uint8 or not void_out.is_contiguous() or void_out.device != out.device:
+        raise ValueError(f"mask_out: void_out must be a contiguous uint8 tensor on {out.device}")
+    if rows.dtype != torch.int64 or rows.dim() != 2 or rows.shape[1] != 3 or not rows.is_contiguous() or rows.device != out.device:
+        raise ValueError(f"mask_out: rows must be a contiguous (m, 3) int64 tensor on {out.device}")
+    _lib.check(_lib.load().jspsr_scene_mask_out(out.data_ptr(), out.numel(), void_out.data_ptr(), void_out.numel(), rows.data_ptr(),
+                                                rows.shape[0], float(np.float32(nodata)),
+                                                torch.cuda.current_stream(out.device).cuda_stream), "jspsr_scene_mask_out")
+    return out
+
+
+def _mask_rows(scenes, indices, offsets) -> torch.Tensor:
+    """The device table of `mask_out` for a predict_scenes call, kept with the store per index list (the offsets follow
+    from it) as `_table` keeps its tables: int64 rows uploaded as pairs of int32."""
+    cache = scenes.__dict__.setdefault("_infer_tables", {})
+    key = ("mask_out", tuple(int(s) for s in indices))
+    if key not in cache:
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        starts = np.concatenate([[0], np.cumsum([h * w for h, w in scenes.shapes])])
+        rows = np.array([[offsets[pos], starts[s], scenes.shapes[s][0] * scenes.shapes[s][1]] for pos, s in enumerate(key[1])],
+                        dtype=np.int64)
+        cache[key] = _Uploaded((rows.view(np.int32),), scenes.device)
+    return cache[key].on_current_stream()[0].view(torch.int64)
+
+
+def _result(scenes, indices, offsets, buffer, mask_voids) -> "SceneRasters":
+    """predict_scenes' end: for a store that holds voids one more launch writes its no-data value into the result."""
+    if mask_voids and getattr(scenes, "void_out", None) is not None and sum(scenes.void_counts) > 0:
+        mask_out(buffer, scenes.void_out, _mask_rows(scenes, indices, offsets), scenes.nodata)
+    return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+
+
 def _model_name(model, model_name):
     return str(model_name or getattr(model, "name", None) or type(model).__module__.rsplit(".", 1)[-1]).lower()
 
@@ -857,7 +992,8 @@ class SceneRasters:
 @torch.no_grad()
 def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch_size: int = 1, pad=0,
                    model_name: str | None = None, input_data: dict | None = None, metres: bool = True,
-                   tta=None, tile=None, overlap: int | None = None, trim: int = 0, window_tta=None) -> SceneRasters:
+                   tta=None, tile=None, overlap: int | None = None, trim: int = 0, window_tta=None,
+                   mask_voids: bool = True) -> SceneRasters:
     """Whole scenes through the model: `model.eval()`, no gradients; the scenes are grouped by shape in index order and,
     per group, each batch runs prepare -> forward -> finish (two launches around the forward, written straight into the
     result's buffer).  No host synchronisation anywhere in the pass.
@@ -893,7 +1029,12 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     so that `batch_size` still bounds the samples of a forward.  Per chunk one launch carries the predictions back and
     averages them in fp32 in the order of the elements (`mean_windows`); the fp32 mean tiles are then merged as above, the
     mean before the metres as with `tta`.  window_tta=[(0, False, False)] gives the bits of the plain tiled pass.
-    ValueError without `tile` and together with `tta`."""
+    ValueError without `tile` and together with `tta`.
+
+    mask_voids (K17): a store built with `nodata` was filled at construction, so every path above reads finite values.  With
+    mask_voids=True one more launch at the end, for all scenes of the call and either `metres`, writes np.float32(scenes.nodata)
+    into the result wherever `scenes.void_out` is set; False returns the filled prediction.  A store without `nodata`, or
+    with no void in it, launches nothing more."""
     window_elements = None if window_tta is None else d4_elements(window_tta)
     if window_elements is not None and tile is None:
         raise ValueError("predict_scenes: window_tta transforms the windows of a tiled pass; give tile (or use tta)")
@@ -940,7 +1081,7 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     model.eval()
     if elements is not None:
         _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batch_size, pad, multiple, concat, take, metres)
-        return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+        return _result(scenes, indices, offsets, buffer, mask_voids)
     if tiled_groups:
         tiled = sorted(pos for members in tiled_groups.values() for pos in members)
         if window_elements is not None:
@@ -951,7 +1092,7 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
     if window_elements is not None:                               # the scenes within the tile: their one window is the scene
         whole = {shape: members for shape, members in groups.items() if shape not in tiled_groups}
         _predict_tta(model, scenes, indices, window_elements, whole, offsets, buffer, batch_size, pad, multiple, concat, take, metres)
-        return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+        return _result(scenes, indices, offsets, buffer, mask_voids)
     at = 0
     for (h, w), members in groups.items():
         if (h, w) in tiled_groups:
@@ -966,7 +1107,7 @@ def predict_scenes(model, scenes, indices: Sequence[int] | None = None, *, batch
             o = offsets[members[lo]]
             _finish(pred, rows, scenes, frame, metres, buffer[o:o + B * h * w])
         at += len(members)
-    return SceneRasters(buffer, offsets, [tuple(scenes.shapes[s]) for s in indices], [scenes.ids[s] for s in indices])
+    return _result(scenes, indices, offsets, buffer, mask_voids)
 
 
 def _get(p, name, default=None):
