@@ -737,6 +737,45 @@ int jspsr_scene_fill_voids(float* dem, const unsigned char* void_plane, const in
 int jspsr_scene_mask_out(float* out, long long out_len, const unsigned char* void_out, long long pixels,
                          const long long* rows, int n_rows, float nodata, jspsr_stream_t stream);
 
+/* ---- K18 (ABI v25, additive): pooled scores over valid pixels -- the masked form of K12(b) (csrc/summary.hip)
+ * A K17 result carries the no-data value where the input had voids, and a real ground truth has holes of its own: one
+ * such pixel wrecks RMSE, LE95 and PSNR of a whole table.  What this entry replaces is a device-to-host copy of every raster,
+ * boolean indexing and np.median / np.percentile on the host.
+ *
+ * jspsr_summary_valid_forward: jspsr_summary_forward over the elements a validity plane keeps.  Arguments as K12's, plus
+ *   valid   device uint8 [valid_numel] in the GROUND TRUTH's layout: read at the gt offset and pitch of every window;
+ *     valid_numel must equal gt_numel.  A pixel counts iff its byte is non-zero.  One plane serves all candidates: every
+ *     row of a table is scored over the same pixels.
+ *   counts  device int64 [n_segments]: the number n_v of valid elements of every segment.
+ *   segments: K12's table; words 3..7 (ranks and weight) are IGNORED.  n stays the segment's element count before masking
+ *     and still fixes the chunking, total and total_chunks.
+ *   With a mask n_v is data on the device, so the ranks, the weight and the divisor are formed there, by the first scan:
+ *     n_v = the sum of the chunks' counts (exact, integer); median ranks (n_v - 1) / 2 and n_v / 2; v = 0.95 (n_v - 1) in
+ *     double, l = floor(v), LE95 ranks l and min(l + 1, n_v - 1), g = v - l (no contraction: -ffp-contract=off); RMSE =
+ *     sqrt(sum / n_v).  One __host__ __device__ inline forms them; jspsr_summary_ranks is its host twin, and the bits are
+ *     those of jspsr_amd/summary.py: segment_ranks(n_v).
+ *   A masked element's candidate and ground-truth values have no influence whatever they are (NaN, inf, -32767, 1e30): it
+ *     is left out of the fp64 sum and of every histogram.  An element that is valid and NaN makes the row's five scores
+ *     NaN, as in K12.  An element no window covers, or read outside a buffer, counts as valid and is NaN, as in K12.
+ *   A segment with n_v = 0: all 11 columns NaN, counts = 0; not an error (the host cannot know).
+ *   Departure from K12: none in the arithmetic.  A workgroup still owns one chunk of one segment and masked elements add
+ *     nothing, so a call with an all-ones plane has exactly the bits of jspsr_summary_forward, all 11 columns.
+ *   16 launches whatever the windows, segments, candidates and mask are (census labels summary_valid_prepare /
+ *   summary_valid_select; K12's labels do not move); a row has the same bits for every n_cand, whatever other segments the
+ *   call holds, on every run.  No host synchronisation.
+ *   JSPSR_EINVAL: K12's cases, a null valid or counts, valid_numel != gt_numel.  workspace:
+ *   jspsr_summary_valid_workspace_bytes(...) bytes (K12's plus one byte per pooled element and four per chunk; 0 = bad
+ *   arguments), 16-byte aligned (JSPSR_EALIGN); counts 8-byte aligned.
+ * jspsr_summary_ranks: out5 (HOST) = { (n - 1) / 2, n / 2, l, min(l + 1, n - 1), the bits of the double g }; JSPSR_EINVAL
+ *   for n < 1 or a null out5.  No device is touched. */
+size_t jspsr_summary_valid_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks);
+int jspsr_summary_valid_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                                long long gt_numel, const unsigned char* valid, long long valid_numel,
+                                const long long* windows, int n_windows, const long long* segments, int n_segments,
+                                long long total, long long total_chunks, double value_max, float* out, long long* counts,
+                                void* workspace, jspsr_stream_t stream);
+int jspsr_summary_ranks(long long n, long long* out5);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

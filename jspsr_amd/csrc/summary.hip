@@ -21,6 +21,17 @@
 //     order that depends on the segment's own size only: a row has the same bits for every n_cand, for every set of
 //     other segments in the call, on every run.  The workgroups of a row flush their LDS counts into one of up to 16
 //     replicas of the row's counters (hist_replicas): global adds to one address serialise.
+// (c) jspsr_summary_valid_forward (K18): (b) over the elements a validity plane in the ground truth's layout keeps.  The
+//     three kernels are templates on MASKED; the unmasked instances are (b) as it was.  prepare reads the plane through
+//     the window table, keeps a validity byte per pooled element (written once, by the workgroups of candidate 0, read
+//     by every select pass of every candidate), leaves masked elements out of the fp64 sum and of every histogram and
+//     writes its chunk's count of valid elements.  With a mask the number of valid elements n_v of a segment is data on
+//     the device: the first scan folds the chunk counts into n_v and forms the ranks, the LE95 weight (kept in the row
+//     state) and the divisor of the sum from it (segment_ranks_of: one __host__ __device__ inline, the bits of
+//     jspsr_amd/summary.py: segment_ranks).  Masked lanes arrive at hist_add with match = false, they do not branch
+//     around it.  A workgroup still owns one CHUNK of one segment of the UNMASKED numbering, and masked elements add
+//     nothing: an all-ones plane gives (b)'s bits.  n_v = 0: no lane of the scan finds the rank, the states stay
+//     where they are, and the row is written as NaN.
 // Departures from the reference (numpy on float32 arrays), see include/jspsr_hip.h: RMSE from an fp64 sum rounded once
 // (not numpy's fp32 pairwise mean); LE95's virtual index in double (numpy 2 forms it in float32 for float32 input); PSNR
 // without the 1e-8 the reference's online form adds for the baselines.
@@ -41,6 +52,25 @@ constexpr int MAXC = 8;
 constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // segment, h, w, e offset, {offset, pitch} of gt, cand 0..7
 constexpr int SEG_WORDS = 8;                  // e start, n, first chunk, 4 ranks, g (fp64 bits)
 static_assert(CHUNK % (MT * UNROLL) == 0, "a chunk is a whole number of unrolled steps");
+
+// The ranks and the weight every order statistic of n >= 1 elements is read at (jspsr_amd/summary.py: segment_ranks):
+// median (n - 1) / 2 and n / 2; v = 0.95 (n - 1) in double, l = floor(v), LE95 l and min(l + 1, n - 1), g = v - l.  No
+// contraction (this file is built with -ffp-contract=off): v is rounded before floor(v) is taken from it.
+struct Ranks {
+  long long m0, m1, l0, l1;
+  double g;
+};
+__host__ __device__ inline Ranks segment_ranks_of(long long n) {
+  Ranks r;
+  const double v = 0.95 * (double)(n - 1);
+  const double fl = floor(v);
+  r.m0 = (n - 1) / 2;
+  r.m1 = n / 2;
+  r.l0 = (long long)fl;
+  r.l1 = r.l0 + 1 < n - 1 ? r.l0 + 1 : n - 1;
+  r.g = v - fl;
+  return r;
+}
 
 __device__ __forceinline__ unsigned order_key(float f) {      // float -> unsigned key with the same ordering (NaNs last)
   const unsigned u = __float_as_uint(f);
@@ -131,8 +161,8 @@ struct RowState {            // one per (candidate, segment), in device memory; 
   unsigned prefix[NSTATE];   // key bits fixed so far (high bits)
   unsigned k[NSTATE];        // rank still to find inside the current prefix class (0-based)
   float center;              // the median, for |e - median|
-  unsigned has_nan;          // the fp64 sum is NaN: a NaN among the errors
-  unsigned pad[2];
+  unsigned has_nan;          // bit 0: the fp64 sum is NaN, a NaN among the errors; bit 1 (K18): no valid element
+  unsigned pad[2];           // K18: the bits of the LE95 weight g (the unmasked form reads it from the segment table)
 };
 static_assert(sizeof(RowState) == 64, "RowState layout");
 
@@ -141,6 +171,13 @@ struct Buffers {             // by value in the kernel arguments
   long long cand_numel[MAXC];
   const float* gt;
   long long gt_numel;
+};
+
+struct Mask {                // K18, by value in the kernel arguments; all null in the unmasked instances, never read there
+  const unsigned char* plane;  // the validity plane, the ground truth's layout and numel
+  unsigned char* keep;         // [total] a byte per pooled element, the layout of one candidate's e
+  unsigned* chunk_n;           // [total_chunks] valid elements per chunk
+  long long* counts;           // [n_seg] the output
 };
 
 // last row whose word `col` is <= v (rows ascending in that word; row 0 if none is)
@@ -168,12 +205,14 @@ __device__ __forceinline__ bool my_chunk(const long long* __restrict__ seg, int 
   return true;
 }
 
-__global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const long long* __restrict__ win, int n_win,
+template <bool MASKED>
+__global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, Mask K, const long long* __restrict__ win, int n_win,
                                                             const long long* __restrict__ seg, int n_seg, long long total,
                                                             long long total_chunks, int reps, float* __restrict__ e_all,
                                                             double* __restrict__ partial, unsigned* __restrict__ hist) {
   __shared__ unsigned lh[2][256];
   __shared__ double red[MT / 64];
+  __shared__ unsigned nred[MT / 64];
   const int tid = threadIdx.x, c = blockIdx.y;
   lh[0][tid] = 0u;
   lh[1][tid] = 0u;
@@ -188,6 +227,7 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const lo
   long long w_lo = 0, w_hi = 0, w_w = 1, goff = 0, gpitch = 0, coff = 0, cpitch = 0;   // the window of the last element
   bool w_ok = false;
   double sum = 0.0;
+  unsigned kept = 0u;                                           // MASKED: valid elements this thread has seen
   for (long long base = lo; base < hi; base += MT * UNROLL) {
     float err[UNROLL];
     bool valid[UNROLL];
@@ -208,6 +248,7 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const lo
         coff = wr[6 + 2 * c]; cpitch = wr[7 + 2 * c];
       }
       float v = __builtin_nanf("");                             // an element no window covers, or a read outside a buffer
+      bool keep = true;                                         // ... counts as valid: the row turns NaN, as without a mask
       if (w_ok && p >= w_lo && p < w_hi) {
         const long long local = p - w_lo;
         long long y;
@@ -215,11 +256,20 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const lo
         else y = local / w_w;
         const long long x = local - y * w_w;
         const long long jc = coff + y * cpitch + x, jg = goff + y * gpitch + x;
-        if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) v = __fsub_rn(cp[jc], gp[jg]);
+        if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) {
+          v = __fsub_rn(cp[jc], gp[jg]);
+          if constexpr (MASKED) keep = K.plane[jg] != 0;          // the plane has gt's numel (checked by the entry)
+        }
+      }
+      if constexpr (MASKED) {
+        if (!keep) v = 0.f;                                     // whatever cand and gt hold there: it is never looked at again
+        if (c == 0) K.keep[p] = keep ? 1 : 0;
+        valid[u] = keep;                                        // masked lanes still arrive at hist_add, with match = false
+        kept += keep ? 1u : 0u;
       }
       err[u] = v;
       e[p] = v;
-      sum += (double)v * (double)v;
+      if (keep) sum += (double)v * (double)v;
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -229,11 +279,23 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const lo
   }
   const double v = wave_sum(sum);
   if ((tid & 63) == 0) red[tid >> 6] = v;
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) kept += (unsigned)__shfl_xor((int)kept, d, 64);
+    if ((tid & 63) == 0) nred[tid >> 6] = kept;
+  }
   __syncthreads();
   if (tid == 0) {
     double t = 0.0;
     for (int q = 0; q < MT / 64; ++q) t += red[q];
     partial[(size_t)c * total_chunks + blockIdx.x] = t;
+    if constexpr (MASKED) {
+      if (c == 0) {
+        unsigned nk = 0u;
+        for (int q = 0; q < MT / 64; ++q) nk += nred[q];
+        K.chunk_n[blockIdx.x] = nk;
+      }
+    }
   }
   unsigned* hrow = hist + (((size_t)c * n_seg + s) * reps + rep) * NSTATE * 256;
   if (lh[0][tid]) atomicAdd(&hrow[0 * 256 + tid], lh[0][tid]);
@@ -243,7 +305,8 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, const lo
 // histograms of byte `pass` of the keys that carry their state's prefix.  group 0: states 0..3 (e and |e|, one read for
 // both); group 1: states 4, 5 (|e - median|).  While the two states of a pair agree on the higher bytes, only the lower
 // one is counted (the scan reads it for both).
-__global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restrict__ e_all, const long long* __restrict__ seg, int n_seg,
+template <bool MASKED>
+__global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restrict__ e_all, Mask K, const long long* __restrict__ seg, int n_seg,
                                                            long long total, int reps, int group, int pass, const RowState* __restrict__ st,
                                                            unsigned* __restrict__ hist) {
   __shared__ unsigned lh[4][256];
@@ -272,6 +335,7 @@ __global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restr
       const long long i = base + u * MT + tid;
       valid[u] = i < hi;
       x[u] = valid[u] ? e[i] : 0.f;
+      if constexpr (MASKED) valid[u] = valid[u] && K.keep[e_start + i] != 0;     // e_start + i < total (my_chunk)
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -297,12 +361,14 @@ __global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restr
 // One workgroup per (candidate, segment), a wave per state: find the bin holding the state's rank, fix its byte, reduce
 // the rank; clear the row's histograms.  init: the first scan of a call -- the states come from the segment table and
 // RMSE / PSNR from the chunk sums, folded in chunk order.  After byte 0 the keys are complete: the scores are written.
-__global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restrict__ partial, long long total_chunks,
+template <bool MASKED>
+__global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restrict__ partial, Mask K, long long total_chunks,
                                                          const long long* __restrict__ seg, int n_seg, int reps, int group,
                                                          int pass, int init, double value_max, RowState* __restrict__ st,
                                                          unsigned* __restrict__ hist, float* __restrict__ out) {
   __shared__ RowState cur;
   __shared__ double red[MT / 64];
+  __shared__ long long nred[MT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t row = blockIdx.x;
   const int c = (int)(row / n_seg), s = (int)(row % n_seg);
@@ -313,10 +379,12 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
   if (init) {
     if (tid == 0) {
       for (int q = 0; q < NSTATE; ++q) cur.prefix[q] = 0u;
-      cur.k[0] = cur.k[4] = (unsigned)sg[3];
-      cur.k[1] = cur.k[5] = (unsigned)sg[4];
-      cur.k[2] = (unsigned)sg[5];
-      cur.k[3] = (unsigned)sg[6];
+      if constexpr (!MASKED) {
+        cur.k[0] = cur.k[4] = (unsigned)sg[3];
+        cur.k[1] = cur.k[5] = (unsigned)sg[4];
+        cur.k[2] = (unsigned)sg[5];
+        cur.k[3] = (unsigned)sg[6];
+      }
       cur.center = 0.f;
       cur.has_nan = 0u;
       cur.pad[0] = cur.pad[1] = 0u;
@@ -328,6 +396,14 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
       for (long long j = tid; j < nchunks; j += MT) a += src[j];
     a = wave_sum(a);
     if (lane == 0) red[wave] = a;
+    if constexpr (MASKED) {                                      // n_v: integers, exact in any order
+      long long nk = 0;
+      if (sg[2] >= 0 && sg[2] + nchunks <= total_chunks)
+        for (long long j = tid; j < nchunks; j += MT) nk += (long long)K.chunk_n[sg[2] + j];
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) nk += __shfl_xor(nk, d, 64);
+      if (lane == 0) nred[wave] = nk;
+    }
   } else if (tid < (int)(sizeof(RowState) / 4)) {
     reinterpret_cast<unsigned*>(&cur)[tid] = reinterpret_cast<const unsigned*>(st + row)[tid];
   }
@@ -335,10 +411,31 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
   if (init && tid == 0) {
     double t = 0.0;
     for (int q = 0; q < MT / 64; ++q) t += red[q];
-    const double rm = sqrt(t / (double)n);
+    long long n_v = n;
+    if constexpr (MASKED) {
+      n_v = 0;
+      for (int q = 0; q < MT / 64; ++q) n_v += nred[q];
+      if (n_v < 0 || n_v > n) n_v = 0;                           // cannot happen with counts this call wrote
+      if (c == 0) K.counts[s] = n_v;
+      if (n_v >= 1) {
+        const Ranks r = segment_ranks_of(n_v);
+        cur.k[0] = cur.k[4] = (unsigned)r.m0;
+        cur.k[1] = cur.k[5] = (unsigned)r.m1;
+        cur.k[2] = (unsigned)r.l0;
+        cur.k[3] = (unsigned)r.l1;
+        __builtin_memcpy(cur.pad, &r.g, 8);
+      } else {                                                   // every histogram of the row stays empty: no lane finds a rank
+        for (int q = 0; q < NSTATE; ++q) cur.k[q] = 0u;
+      }
+    }
+    const double rm = sqrt(t / (double)n_v);
     o[0] = (float)rm;
     o[4] = (float)(20.0 * log10(value_max / rm));               // +inf at rm == 0; NaN stays NaN
     cur.has_nan = (t != t) ? 1u : 0u;
+    if constexpr (MASKED) cur.has_nan |= n_v < 1 ? 2u : 0u;
+  }
+  if constexpr (MASKED) {
+    if (init) __syncthreads();                                   // kernel-uniform: the ranks were written after the barrier above
   }
   // a wave per state
   const int q = (group ? 4 : 0) + wave, ql = q & ~1;
@@ -364,7 +461,7 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
       if (lane >= d) incl += up;
     }
     const unsigned excl = incl - own;
-    if (k >= excl && k < incl) {                                 // exactly one lane: the counts sum to more than k
+    if (k >= excl && k < incl) {                                 // exactly one lane: the counts sum to more than k (none: n_v = 0)
       unsigned run = excl;
       int b = 0;
       if (k >= run + c0) { run += c0; b = 1;
@@ -391,19 +488,29 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
       const float l0 = key_value(cur.prefix[2]), l1 = key_value(cur.prefix[3]);
       const float med = __fmul_rn(__fadd_rn(m0, m1), 0.5f);      // np.median of a float32 array: mean of the two middle elements
       double g;
-      const long long gb = sg[7];
-      __builtin_memcpy(&g, &gb, 8);
+      if constexpr (MASKED) {
+        __builtin_memcpy(&g, cur.pad, 8);
+      } else {
+        const long long gb = sg[7];
+        __builtin_memcpy(&g, &gb, 8);
+      }
       const float le = (float)((double)l0 + ((double)l1 - (double)l0) * g);
       cur.center = med;
       o[1] = bad ? nanv : med;
       o[3] = bad ? nanv : le;
       o[5] = m0; o[6] = m1; o[9] = l0; o[10] = l1;
       if (bad) { o[0] = nanv; o[4] = nanv; }
+      if constexpr (MASKED) {
+        if (cur.has_nan & 2u) { o[5] = nanv; o[6] = nanv; o[9] = nanv; o[10] = nanv; }
+      }
     } else {
       const float d0 = key_value(cur.prefix[4]), d1 = key_value(cur.prefix[5]);
       const float mad = __fmul_rn(__fadd_rn(d0, d1), 0.5f);
       o[2] = bad ? nanv : (float)(1.4826 * (double)mad);
       o[7] = d0; o[8] = d1;
+      if constexpr (MASKED) {
+        if (cur.has_nan & 2u) { o[7] = nanv; o[8] = nanv; }
+      }
     }
   }
   __syncthreads();
@@ -456,36 +563,47 @@ extern "C" int jspsr_scenes_assemble_f32(const float* tiles, const float* base, 
   return check_launch("scenes_assemble");
 }
 
-extern "C" size_t jspsr_summary_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks) {
+
+namespace {
+
+// The workspace: e, the chunk sums, the histograms, [K18: the chunk counts, cleared with the histograms], the row states,
+// [K18: the validity bytes].  The unmasked layout is K12's.
+size_t workspace_bytes(bool masked, int n_cand, int n_segments, long long total, long long total_chunks) {
   if (!sizes_ok(n_cand, n_segments, total, total_chunks)) return 0;
   const size_t rows = (size_t)n_cand * n_segments;
-  return up16((size_t)n_cand * total * sizeof(float)) + up16((size_t)n_cand * total_chunks * sizeof(double)) +
-         rows * hist_replicas(rows, total_chunks) * NSTATE * 256 * sizeof(unsigned) + rows * sizeof(RowState) + 64;
+  const size_t k12 = up16((size_t)n_cand * total * sizeof(float)) + up16((size_t)n_cand * total_chunks * sizeof(double)) +
+                     rows * hist_replicas(rows, total_chunks) * NSTATE * 256 * sizeof(unsigned) + rows * sizeof(RowState) + 64;
+  return masked ? k12 + up16((size_t)total_chunks * sizeof(unsigned)) + up16((size_t)total) : k12;
 }
 
-extern "C" int jspsr_summary_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
-                                     long long gt_numel, const long long* windows, int n_windows, const long long* segments,
-                                     int n_segments, long long total, long long total_chunks, double value_max, float* out,
-                                     void* workspace, jspsr_stream_t stream) {
-  if (n_cand < 1 || n_cand > MAXC) return fail(JSPSR_EINVAL, "summary_forward: n_cand = %d is outside 1..%d", n_cand, MAXC);
-  if (!cands || !cand_numel || !gt || !windows || !segments || !out || !workspace) return fail(JSPSR_EINVAL, "summary_forward: null pointer");
-  if (n_windows <= 0 || n_segments <= 0 || total <= 0 || gt_numel <= 0) return fail(JSPSR_EINVAL, "summary_forward: empty window or segment table");
-  if (total >= 0x100000000ll) return fail(JSPSR_EINVAL, "summary_forward: %lld pooled elements, the rank counters hold fewer than 2^32", total);
+template <bool MASKED>
+int summary_run(const char* name, const float* const* cands, const long long* cand_numel, int n_cand, const float* gt, long long gt_numel,
+                const unsigned char* valid, long long valid_numel, const long long* windows, int n_windows, const long long* segments,
+                int n_segments, long long total, long long total_chunks, double value_max, float* out, long long* counts,
+                void* workspace, jspsr_stream_t stream) {
+  if (n_cand < 1 || n_cand > MAXC) return fail(JSPSR_EINVAL, "%s: n_cand = %d is outside 1..%d", name, n_cand, MAXC);
+  if (!cands || !cand_numel || !gt || !windows || !segments || !out || !workspace) return fail(JSPSR_EINVAL, "%s: null pointer", name);
+  if (MASKED && (!valid || !counts)) return fail(JSPSR_EINVAL, "%s: null validity plane or counts", name);
+  if (n_windows <= 0 || n_segments <= 0 || total <= 0 || gt_numel <= 0) return fail(JSPSR_EINVAL, "%s: empty window or segment table", name);
+  if (MASKED && valid_numel != gt_numel)
+    return fail(JSPSR_EINVAL, "%s: the validity plane has %lld elements, the ground truth %lld", name, valid_numel, gt_numel);
+  if (total >= 0x100000000ll) return fail(JSPSR_EINVAL, "%s: %lld pooled elements, the rank counters hold fewer than 2^32", name, total);
   if (n_windows < n_segments || !sizes_ok(n_cand, n_segments, total, total_chunks))
-    return fail(JSPSR_EINVAL, "summary_forward: %d windows, %d segments, %lld elements and %lld chunks do not fit together", n_windows,
+    return fail(JSPSR_EINVAL, "%s: %d windows, %d segments, %lld elements and %lld chunks do not fit together", name, n_windows,
                 n_segments, total, total_chunks);
-  if ((long long)n_cand * n_segments > 0x7fffffffll) return fail(JSPSR_EINVAL, "summary_forward: too many rows");
+  if ((long long)n_cand * n_segments > 0x7fffffffll) return fail(JSPSR_EINVAL, "%s: too many rows", name);
   Buffers B;
   for (int c = 0; c < MAXC; ++c) {
     B.cand[c] = c < n_cand ? cands[c] : nullptr;
     B.cand_numel[c] = c < n_cand ? cand_numel[c] : 0;
-    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "summary_forward: candidate %d is null or empty", c);
-    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "summary_forward: candidate %d not 4-byte aligned", c);
+    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "%s: candidate %d is null or empty", name, c);
+    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "%s: candidate %d not 4-byte aligned", name, c);
   }
   B.gt = gt;
   B.gt_numel = gt_numel;
-  if (!aligned4(gt) || !aligned4(out)) return fail(JSPSR_EALIGN, "summary_forward: tensors not 4-byte aligned");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "summary_forward: workspace not 16-byte aligned");
+  if (!aligned4(gt) || !aligned4(out)) return fail(JSPSR_EALIGN, "%s: tensors not 4-byte aligned", name);
+  if (MASKED && (reinterpret_cast<uintptr_t>(counts) & 7u)) return fail(JSPSR_EALIGN, "%s: counts not 8-byte aligned", name);
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", name);
   const size_t rows = (size_t)n_cand * n_segments;
   char* ws = static_cast<char*>(workspace);
   float* e = reinterpret_cast<float*>(ws);
@@ -496,25 +614,77 @@ extern "C" int jspsr_summary_forward(const float* const* cands, const long long*
   const int reps = hist_replicas(rows, total_chunks);
   const size_t hist_bytes = rows * reps * NSTATE * 256 * sizeof(unsigned);
   off += hist_bytes;
+  size_t clear_bytes = hist_bytes;
+  Mask K = {nullptr, nullptr, nullptr, nullptr};
+  if (MASKED) {
+    K.plane = valid;
+    K.counts = counts;
+    K.chunk_n = reinterpret_cast<unsigned*>(ws + off);            // behind the histograms: one clear serves both
+    off += up16((size_t)total_chunks * sizeof(unsigned));
+    clear_bytes = off - (size_t)(reinterpret_cast<char*>(hist) - ws);
+  }
   RowState* st = reinterpret_cast<RowState*>(ws + off);
+  if (MASKED) K.keep = reinterpret_cast<unsigned char*>(ws + off + rows * sizeof(RowState) + 64);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(hist, 0, hist_bytes, s) != hipSuccess)
-    return fail(JSPSR_EINVAL, "summary_forward: clearing the histograms failed: %s", hipGetErrorString(hipGetLastError()));
+  if (hipMemsetAsync(hist, 0, clear_bytes, s) != hipSuccess)
+    return fail(JSPSR_EINVAL, "%s: clearing the histograms failed: %s", name, hipGetErrorString(hipGetLastError()));
+  // the census labels (string literals, found by pointer): the scans count as selects, as in K12
+  const char* const prepare_label = MASKED ? "summary_valid_prepare" : "summary_prepare";
+  const char* const select_label = MASKED ? "summary_valid_select" : "summary_select";
   const dim3 grid((unsigned)total_chunks, n_cand);
-  hipLaunchKernelGGL(summary_prepare_kernel, grid, dim3(MT), 0, s, B, windows, n_windows, segments, n_segments, total, total_chunks, reps,
-                     e, partial, hist);
-  if (int err = check_launch("summary_prepare")) return err;
+  hipLaunchKernelGGL(summary_prepare_kernel<MASKED>, grid, dim3(MT), 0, s, B, K, windows, n_windows, segments, n_segments, total,
+                     total_chunks, reps, e, partial, hist);
+  if (int err = check_launch(prepare_label)) return err;
   for (int group = 0; group < 2; ++group) {
     for (int pass = 3; pass >= 0; --pass) {
       const int init = group == 0 && pass == 3;                  // the top digit of e and |e| was counted by the first pass
       if (!init) {
-        hipLaunchKernelGGL(summary_select_kernel, grid, dim3(MT), 0, s, e, segments, n_segments, total, reps, group, pass, st, hist);
-        if (int err = check_launch("summary_select")) return err;
+        hipLaunchKernelGGL(summary_select_kernel<MASKED>, grid, dim3(MT), 0, s, e, K, segments, n_segments, total, reps, group, pass, st,
+                           hist);
+        if (int err = check_launch(select_label)) return err;
       }
-      hipLaunchKernelGGL(summary_scan_kernel, dim3((unsigned)rows), dim3(MT), 0, s, partial, total_chunks, segments, n_segments, reps,
-                         group, pass, init, value_max, st, hist, out);
-      if (int err = check_launch("summary_select")) return err;
+      hipLaunchKernelGGL(summary_scan_kernel<MASKED>, dim3((unsigned)rows), dim3(MT), 0, s, partial, K, total_chunks, segments, n_segments,
+                         reps, group, pass, init, value_max, st, hist, out);
+      if (int err = check_launch(select_label)) return err;
     }
   }
+  return JSPSR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t jspsr_summary_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks) {
+  return workspace_bytes(false, n_cand, n_segments, total, total_chunks);
+}
+
+extern "C" int jspsr_summary_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                                     long long gt_numel, const long long* windows, int n_windows, const long long* segments,
+                                     int n_segments, long long total, long long total_chunks, double value_max, float* out,
+                                     void* workspace, jspsr_stream_t stream) {
+  return summary_run<false>("summary_forward", cands, cand_numel, n_cand, gt, gt_numel, nullptr, 0, windows, n_windows, segments, n_segments,
+                            total, total_chunks, value_max, out, nullptr, workspace, stream);
+}
+
+extern "C" size_t jspsr_summary_valid_workspace_bytes(int n_cand, int n_segments, long long total, long long total_chunks) {
+  return workspace_bytes(true, n_cand, n_segments, total, total_chunks);
+}
+
+extern "C" int jspsr_summary_valid_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                                           long long gt_numel, const unsigned char* valid, long long valid_numel,
+                                           const long long* windows, int n_windows, const long long* segments, int n_segments,
+                                           long long total, long long total_chunks, double value_max, float* out, long long* counts,
+                                           void* workspace, jspsr_stream_t stream) {
+  return summary_run<true>("summary_valid_forward", cands, cand_numel, n_cand, gt, gt_numel, valid, valid_numel, windows, n_windows,
+                           segments, n_segments, total, total_chunks, value_max, out, counts, workspace, stream);
+}
+
+extern "C" int jspsr_summary_ranks(long long n, long long* out5) {
+  if (n < 1 || !out5) return fail(JSPSR_EINVAL, "summary_ranks: n = %lld (n >= 1 and a non-null result are taken)", n);
+  const Ranks r = segment_ranks_of(n);
+  out5[0] = r.m0;
+  out5[1] = r.m1;
+  out5[2] = r.l0;
+  out5[3] = r.l1;
+  __builtin_memcpy(&out5[4], &r.g, 8);
   return JSPSR_OK;
 }

@@ -69,7 +69,8 @@ class DeviceScenes:
     refused here.  `elev_min` / `elev_max` are the config's Python numbers (tensor_kwargs min / max).
 
     Voids (no-data pixels) are not taken here: `nodata` raises NotImplementedError together with `hr_dem`.  The store without
-    a ground truth, `infer.InferenceScenes(nodata=...)`, fills them on the device at construction (K17).
+    a ground truth, `infer.InferenceScenes(nodata=...)`, fills them on the device at construction (K17); scores over the
+    valid pixels only are `summary.summarise(valid=...)` with `summary.valid_plane` (K18).
     """
 
     def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
@@ -79,8 +80,8 @@ class DeviceScenes:
         if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
             raise KeyError("hr_dem")
         if nodata is not None:
-            raise NotImplementedError("nodata: voids in a store with hr_dem (training, scores over valid pixels) are not built; "
-                                      "`infer.InferenceScenes` takes them")
+            raise NotImplementedError("nodata: voids in a store with hr_dem (training on voids) are not built; "
+                                      "`infer.InferenceScenes` takes them, and `summary.summarise(valid=...)` scores over valid pixels")
         self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device)

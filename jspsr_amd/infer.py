@@ -135,7 +135,8 @@ class InferenceScenes(DeviceScenes):
     by the scene's base; fill_limit=0: every void.  After that the store is read-only and finite: prepare, the ensembles and
     the tiled passes read it unchanged.  `void_out` (`void_mask(i, out=True)`): void, or within the Euclidean distance
     `void_margin` of one (0: `void` itself, the same tensor); `predict_scenes(mask_voids=True)` writes np.float32(nodata)
-    there.  Voids in image, mask or canopy, voids together with hr_dem, and scores over valid pixels are not built."""
+    there.  Such results are scored over the valid pixels only by `summary.summarise(valid=...)` (K18).  Voids in image, mask
+    or canopy and voids together with hr_dem are not built."""
 
     def __init__(self, lr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *, relative: bool = False,
                  elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,

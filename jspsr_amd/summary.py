@@ -17,6 +17,12 @@ Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K
 richdem slope stay out; `upscale_dem` and whole-scene inference are in jspsr_amd/infer.py (K13), whose
 `predict_scenes(...).rasters()` gives the per-scene metre rasters `summarise` takes as `predictions`.
 
+Scores over valid pixels only (K18): `summarise(..., valid=valid_plane(scenes, nodata))`, `scores_pooled(..., valid=)` and
+`pooled_rows(..., valid=)` leave the pixels a uint8 plane in the ground truth's layout masks out of every sum and order
+statistic, whatever their values (the -32767 of a `predict_scenes(mask_voids=True)` result, a hole in the ground truth), and
+also return how many pixels were scored.  The count is data on the device, so the ranks are formed there: still one call of
+16 launches without a host synchronisation.
+
 Device fp32 tensors go through the HIP kernels; host tensors through the same formulas as numpy / torch operators.
 """
 from __future__ import annotations
@@ -74,11 +80,20 @@ def _row_host(e: np.ndarray, value_max: float) -> np.ndarray:
     return row
 
 
-def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], n_segments: int, value_max: float):
+def _nan_row() -> np.ndarray:
+    return np.full(len(ROW), np.nan, dtype=np.float32)
+
+
+def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], n_segments: int, value_max: float,
+                valid: torch.Tensor | None = None):
     """The raw table call.  cands: 1..8 flat fp32 buffers, gt one, all on one device; windows: (segment, h, w, (gt offset,
     gt pitch), [(offset, pitch) per candidate]) in elements -- crops are read in place; a segment pools its windows in the
     order given.  -> (n_cand, n_segments, 11) fp32 tensor, columns `ROW`, on the buffers' device.  No host
-    synchronisation on the device path (K12(b): one call, 16 launches)."""
+    synchronisation on the device path (K12(b): one call, 16 launches).
+    valid: a flat contiguous uint8 tensor of gt.numel() elements on gt's device, read at gt's offsets and pitches; an
+    element is scored iff its byte is non-zero, for every candidate alike (K18: still one call, 16 launches, no
+    synchronisation).  -> (rows, counts): rows as above, counts an int64 (n_segments,) tensor on the device, the elements
+    scored per segment; a segment with none has a NaN row and count 0."""
     n_cand = len(cands)
     if not 1 <= n_cand <= MAX_CANDIDATES:
         raise ValueError(f"pooled_rows: {n_cand} candidates, 1..{MAX_CANDIDATES} are taken")
@@ -87,6 +102,13 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
         raise ValueError("pooled_rows: flat contiguous float32 buffers")
     if len({b.device for b in bufs}) != 1:
         raise ValueError("pooled_rows: buffers on several devices")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or valid.dim() != 1 or not valid.is_contiguous():
+            raise ValueError("pooled_rows: valid must be a flat contiguous uint8 tensor")
+        if valid.numel() != gt.numel():
+            raise ValueError(f"pooled_rows: valid has {valid.numel()} elements, the ground truth {gt.numel()}")
+        if valid.device != gt.device:
+            raise ValueError(f"pooled_rows: valid on {valid.device}, the ground truth on {gt.device}")
     if n_segments < 1 or not windows:
         raise ValueError("pooled_rows: no windows or no segments")
     order = sorted(range(len(windows)), key=lambda i: windows[i][0])          # stable: a segment keeps its window order
@@ -106,9 +128,17 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
         raise ValueError("pooled_rows: a segment without windows")
     total = sum(seg_n)
     if gt.is_cuda:
-        return _pooled_device(cands, gt, [windows[i] for i in order], seg_n, total, value_max)
+        return _pooled_device(cands, gt, [windows[i] for i in order], seg_n, total, value_max, valid)
     out = np.empty((n_cand, n_segments, len(ROW)), dtype=np.float32)
     g_np = gt.numpy()
+    keep = None
+    if valid is not None:
+        v_np = valid.numpy()
+        keep = [[] for _ in range(n_segments)]
+        for i in order:
+            sg, h, w, (go, gp), _ = windows[i]
+            keep[sg].append(v_np[go + np.arange(h)[:, None] * gp + np.arange(w)[None, :]].reshape(-1) != 0)
+        keep = [np.concatenate(k) for k in keep]
     for c, cand in enumerate(cands):
         c_np = cand.numpy()
         parts = [[] for _ in range(n_segments)]
@@ -117,13 +147,19 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
             co, cp = cs[c]
             rows = np.arange(h)[:, None]
             cols = np.arange(w)[None, :]
-            parts[sg].append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
+            with np.errstate(invalid="ignore"):                 # inf - inf under a mask
+                parts[sg].append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
         for sg in range(n_segments):
-            out[c, sg] = _row_host(np.concatenate(parts[sg]).astype(np.float32, copy=False), value_max)
+            e = np.concatenate(parts[sg]).astype(np.float32, copy=False)
+            if keep is not None:
+                e = e[keep[sg]]
+            out[c, sg] = _row_host(e, value_max) if e.size else _nan_row()
+    if keep is not None:
+        return torch.from_numpy(out), torch.tensor([int(k.sum()) for k in keep], dtype=torch.int64)
     return torch.from_numpy(out)
 
 
-def _pooled_device(cands, gt, windows, seg_n, total, value_max):
+def _pooled_device(cands, gt, windows, seg_n, total, value_max, valid=None):
     n_cand, n_seg, n_win = len(cands), len(seg_n), len(windows)
     tab = np.zeros(n_win * _WIN_WORDS + n_seg * _SEG_WORDS, dtype=np.int64)
     win = tab[:n_win * _WIN_WORDS].reshape(n_win, _WIN_WORDS)
@@ -141,7 +177,8 @@ def _pooled_device(cands, gt, windows, seg_n, total, value_max):
         start += n
         chunk += (n + CHUNK - 1) // CHUNK
     lib = _lib.load()
-    nbytes = lib.jspsr_summary_workspace_bytes(n_cand, n_seg, total, chunk)
+    masked = valid is not None
+    nbytes = (lib.jspsr_summary_valid_workspace_bytes if masked else lib.jspsr_summary_workspace_bytes)(n_cand, n_seg, total, chunk)
     if nbytes == 0:
         raise ValueError(f"pooled_rows: {n_cand} candidates, {n_seg} segments, {total} pooled elements: not a size K12 takes "
                          "(fewer than 2^32 elements per call)")
@@ -153,6 +190,14 @@ def _pooled_device(cands, gt, windows, seg_n, total, value_max):
     out = torch.empty((n_cand, n_seg, len(ROW)), dtype=torch.float32, device=dev)
     ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
     numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+    if masked:
+        counts = torch.empty(n_seg, dtype=torch.int64, device=dev)
+        _lib.check(lib.jspsr_summary_valid_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), valid.data_ptr(), valid.numel(),
+                                                   table.data_ptr(), n_win, table.data_ptr() + n_win * _WIN_WORDS * 8, n_seg, total,
+                                                   chunk, float(value_max), out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream),
+                   "jspsr_summary_valid_forward")
+        return out, counts
     _lib.check(lib.jspsr_summary_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), table.data_ptr(), n_win,
                                          table.data_ptr() + n_win * _WIN_WORDS * 8, n_seg, total, chunk, float(value_max),
                                          out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
@@ -160,12 +205,14 @@ def _pooled_device(cands, gt, windows, seg_n, total, value_max):
     return out
 
 
-def scores_pooled(cands, gt, segments=None, value_max: float = 1.0):
+def scores_pooled(cands, gt, segments=None, value_max: float = 1.0, valid=None):
     """Pooled scores of equal-shape tensors, e.g. a 4096 x 4096 scene from `tiling.sharded_forward_owned` against its
     target.  cands: a tensor or a list of up to 8, each of gt's shape (..., H, W), fp32 metres.  segments: None pools
     everything into one segment; otherwise a list of segments, each a list of windows (plane, y0, x0, h, w) over the
     tensors flattened to (planes, H, W).  value_max: the numerator of PSNR = 20 log10(value_max / RMSE).
-    -> (n_cand, n_segments, 11) fp32 tensor on the inputs' device, columns `ROW`; no host synchronisation."""
+    -> (n_cand, n_segments, 11) fp32 tensor on the inputs' device, columns `ROW`; no host synchronisation.
+    valid: a bool or uint8 tensor of gt's shape on gt's device; only the pixels where it is set are scored (K18).
+    -> (rows, counts) as `pooled_rows` gives them."""
     cands = [cands] if isinstance(cands, torch.Tensor) else list(cands)
     if gt.dim() < 2 or any(c.shape != gt.shape for c in cands):
         raise ValueError(f"scores_pooled: equal (..., H, W) tensors, got {[tuple(c.shape) for c in cands]} / {tuple(gt.shape)}")
@@ -181,7 +228,14 @@ def scores_pooled(cands, gt, segments=None, value_max: float = 1.0):
             at = ((p * H + y0) * W + x0, W)
             windows.append((sg, h, w, at, [at] * len(cands)))
     flat = [t.detach().float().contiguous().reshape(-1) for t in cands]
-    return pooled_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, len(segments), value_max)
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != gt.shape:
+            raise ValueError(f"scores_pooled: valid must be a bool or uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
+        if valid.device != gt.device:
+            raise ValueError(f"scores_pooled: valid on {valid.device}, the ground truth on {gt.device}")
+        valid = valid.detach().contiguous().reshape(-1)
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid     # a bool is one byte, 0 or 1
+    return pooled_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, len(segments), value_max, valid=valid)
 
 
 class ScenePredictions:
@@ -309,7 +363,45 @@ def store_layout(scenes, rasters, name="baseline"):
     return torch.from_numpy(np.concatenate(flat)).to(scenes.device)
 
 
-def summarise(scenes, predictions, baselines=None, *, value_max: float, border: float = 0.0, patch_size: int, online: bool = False):
+def _valid_layout(scenes, valid, numel, device):
+    """`summarise`'s valid -> the flat uint8 plane in store layout on the store's device."""
+    if isinstance(valid, torch.Tensor) and valid.dim() == 1:
+        if valid.numel() != numel or valid.dtype != torch.uint8 or valid.device != device:
+            raise ValueError("summarise: a flat valid tensor must be uint8 with the store's layout and device")
+        return valid.contiguous()
+    if len(valid) != len(scenes):
+        raise ValueError(f"summarise: valid has {len(valid)} planes, the store {len(scenes)} scenes")
+    flat = []
+    for i, v in enumerate(valid):
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        a = a.reshape(a.shape[:2]) if a.ndim == 3 and a.shape[2] == 1 else a
+        if a.dtype not in (np.bool_, np.uint8) or tuple(a.shape) != tuple(scenes.shapes[i]):
+            raise ValueError(f"summarise: valid[{i}] is {a.dtype} {a.shape}, expected a bool or uint8 plane of {tuple(scenes.shapes[i])}")
+        flat.append((a.reshape(-1) != 0).astype(np.uint8))
+    return torch.from_numpy(np.concatenate(flat)).to(device)
+
+
+def valid_plane(scenes, nodata, also=None) -> torch.Tensor:
+    """The flat uint8 plane, in store layout on the store's device, of the pixels whose ground truth can be scored:
+    `hr_dem` finite and -- unless `nodata` is NaN -- != np.float32(nodata) (the complement of `data.void_pixels`), formed
+    with torch operators on the device.  also: one further plane of the same layout, or a list of them (bool or uint8,
+    e.g. `(inference_scenes.void_out == 0)` of a K17 store over the same scenes), ANDed in.  -> `summarise(valid=...)`."""
+    gt = scenes.store["hr_dem"]
+    keep = torch.isfinite(gt)
+    nd = np.float32(nodata)
+    if not np.isnan(nd):
+        keep &= gt != float(nd)
+    if also is not None:
+        for p in ([also] if isinstance(also, torch.Tensor) else list(also)):
+            if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() != gt.numel() or p.device != gt.device \
+                    or p.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("valid_plane: `also` takes flat bool / uint8 planes with the store's layout and device")
+            keep &= p != 0
+    return keep.to(torch.uint8)
+
+
+def summarise(scenes, predictions, baselines=None, *, value_max: float, border: float = 0.0, patch_size: int, online: bool = False,
+              valid=None):
     """summarise_evaluation (utils/utils.py:970-1368) on the device.
 
     scenes: the `data.DeviceScenes` store; the ground truth is `scenes.store["hr_dem"]`, read in place.
@@ -320,7 +412,12 @@ def summarise(scenes, predictions, baselines=None, *, value_max: float, border: 
     cropped size is taken whole.  value_max: tensor_kwargs.max, PSNR's numerator.
     -> {name: {"RMSE", "Median", "NMAD", "LE95", "PSNR"}} pooled over all pixels of all scenes ("offline"), for "SR" and
     each baseline.  online=True: -> (that dict, {name: the means of the per-scene values}, {name: {scene id: the five
-    values}}).  One K12(b) call, one device-to-host copy at the end, no other synchronisation."""
+    values}}).  One K12(b) call, one device-to-host copy at the end, no other synchronisation.
+    valid (K18): score only the pixels set in it -- a list of per-scene (h, w) bool / uint8 arrays, uploaded once in store
+    layout, or a flat uint8 device tensor in store layout (`valid_plane(scenes, nodata)`; `(inference_scenes.void_out ==
+    0).to(torch.uint8)` of a K17 store over the same scenes), cropped with the rasters.  One plane for all candidates: the
+    rows of a table are scored over the same pixels.  Every row dict then gains "N", the number of pixels scored (a row
+    without any is NaN); the means average the scenes with N > 0.  Still one call and one device-to-host copy."""
     names = ["SR"] + list(baselines or {})
     if len(names) > MAX_CANDIDATES:
         raise ValueError(f"summarise: {len(names)} candidates, at most {MAX_CANDIDATES}")
@@ -332,6 +429,8 @@ def summarise(scenes, predictions, baselines=None, *, value_max: float, border: 
     for h, w in scenes.shapes:
         offs.append(offs[-1] + h * w)
     gt = scenes.store["hr_dem"]
+    if valid is not None:
+        valid = _valid_layout(scenes, valid, gt.numel(), gt.device)
     if isinstance(predictions, ScenePredictions):
         if predictions.scenes is not scenes or not predictions.complete:
             raise ValueError("summarise: the collector must be complete and made on the same scenes")
@@ -372,12 +471,32 @@ def summarise(scenes, predictions, baselines=None, *, value_max: float, border: 
         windows.append((0, ch, cw, at, [sr_at] + [at] * (len(cands) - 1)))
     if online:
         windows += [(1 + i,) + wdw[1:] for i, wdw in enumerate(windows)]
-    rows = pooled_rows(cands, gt, windows, 1 + S if online else 1, value_max)
-    host = rows.cpu().numpy().astype(np.float64)              # the one device-to-host copy
-    pooled = {name: {k: float(host[c, 0, j]) for j, k in enumerate(COLUMNS)} for c, name in enumerate(names)}
+    n_seg = 1 + S if online else 1
+    if valid is None:
+        rows = pooled_rows(cands, gt, windows, n_seg, value_max)
+        host = rows.cpu().numpy().astype(np.float64)          # the one device-to-host copy
+        count = None
+    else:                                                     # the counts ride behind the rows: still one copy (exact below 2^53)
+        rows, counts = pooled_rows(cands, gt, windows, n_seg, value_max, valid=valid)
+        both = torch.cat((rows.double().reshape(-1), counts.double())).cpu().numpy()
+        host = both[:rows.numel()].reshape(tuple(rows.shape))
+        count = [int(v) for v in both[rows.numel():]]
+
+    def row(c, sg):
+        d = {k: float(host[c, sg, j]) for j, k in enumerate(COLUMNS)}
+        if count is not None:
+            d["N"] = count[sg]
+        return d
+
+    pooled = {name: row(c, 0) for c, name in enumerate(names)}
     if not online:
         return pooled
-    per_scene = {name: {sid: {k: float(host[c, 1 + i, j]) for j, k in enumerate(COLUMNS)} for i, sid in enumerate(scenes.ids)}
-                 for c, name in enumerate(names)}
-    means = {name: {k: sum(v[k] for v in per_scene[name].values()) / S for k in COLUMNS} for name in names}
+    per_scene = {name: {sid: row(c, 1 + i) for i, sid in enumerate(scenes.ids)} for c, name in enumerate(names)}
+    if count is None:
+        means = {name: {k: sum(v[k] for v in per_scene[name].values()) / S for k in COLUMNS} for name in names}
+    else:
+        means = {}
+        for name in names:
+            scored = [v for v in per_scene[name].values() if v["N"] > 0]
+            means[name] = {k: sum(v[k] for v in scored) / len(scored) if scored else float("nan") for k in COLUMNS}
     return pooled, means, per_scene
