@@ -174,6 +174,13 @@ int jspsr_elev_scale_f32(const float* in, float* out, long long n, int descale, 
 int jspsr_batch_make(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
                      const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples, int B,
                      int k, int flags, double elev_min, double elev_max, int mask_div, jspsr_stream_t stream);
+/* K19, jspsr_batch_valid: the validity plane of the same batch.  store: one byte per pixel (nonzero = valid), all scenes
+ *   back to back at the pixel offsets of `scenes`, 4-byte aligned, store_bytes of it (a device pointer, like out, scenes and
+ *   samples).  out (B, 1, k, k) bytes, 1 = valid, made from the same sample rows through the same D4 map as
+ *   jspsr_batch_make, so it lines up with every raster of the batch element for element.  A row that leaves its scene or
+ *   the store writes 0 (where the float kinds write NaN).  One launch, no host synchronisation. */
+int jspsr_batch_valid(const unsigned char* store, long long store_bytes, unsigned char* out, const long long* scenes,
+                      int n_scenes, const int* samples, int B, int k, jspsr_stream_t stream);
 
 /* ---- K1 in the models (round 4): logits + offsets as PLANES of one tensor ---------------------------------------
  * The same operator as jspsr_prop_forward_f32 / jspsr_prop_backward_f32 -- same kernels, same 108 / 208 algorithmic bytes
@@ -458,6 +465,30 @@ int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int p
 int jspsr_loss_menu_backward(const float* pred, const float* gt, int terms, int planes, int H, int W,
                              const double* slot_weight, const float* grad_total, float* grad_pred,
                              const void* workspace, jspsr_stream_t stream);
+/* K19: both loss families over the elements a validity plane keeps (training on a ground truth with voids).  valid:
+ * [planes][H][W] bytes beside pred and gt, nonzero = valid; every other argument as in the unmasked call of the same name.
+ * A masked element has no influence whatever pred and gt hold there (NaN, inf, a no-data code): they are read only behind
+ * a select on the plane.  With d = pred - gt and N the valid elements of the whole call: L1 = sum_valid |d| / N, L2 =
+ * sum_valid d^2 / N; a Sobel output counts iff its nine replicate-clamped taps are valid, Grad = sum_counted (|gx| + |gy|)
+ * / (2 N_g); BerHu's threshold is 0.6 max_valid |d|; BerHu, BCE and Norm are their pointwise expressions over the valid
+ * elements, divided by N.  N = 0 (N_g = 0) gives value 0 and gradient 0.  N and N_g are counted exactly, as integers, by
+ * the forward and stay in the workspace, where the backward reads them: no host synchronisation, capturable in a graph.
+ * The gradient is +0.0 at every invalid element: jspsr_loss_valid_backward writes it, jspsr_loss_menu_valid_backward leaves
+ * the caller's value (which it ADDS to elsewhere) untouched there.  An all-ones plane gives the bits of the unmasked calls.
+ * SSIM (term bit 8, slot 6) over a plane is not built: JSPSR_EINVAL, workspace query 0. */
+size_t jspsr_loss_valid_workspace_bytes(int B, int H, int W);
+int jspsr_loss_valid_forward(const float* pred, const float* gt, const unsigned char* valid, float w1, float w2, float wg,
+                             float* losses, void* workspace, int B, int H, int W, jspsr_stream_t stream);
+int jspsr_loss_valid_backward(const float* pred, const float* gt, const unsigned char* valid, const float* grad_total,
+                              float w1, float w2, float wg, float* grad_pred, const void* workspace, int B, int H, int W,
+                              jspsr_stream_t stream);
+size_t jspsr_loss_menu_valid_workspace_bytes(int terms, int planes, int H, int W);
+int jspsr_loss_menu_valid_forward(const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
+                                  int H, int W, int n_keys, const int* key_slot, const double* key_weight,
+                                  const float* base_losses, float* out, void* workspace, jspsr_stream_t stream);
+int jspsr_loss_menu_valid_backward(const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
+                                   int H, int W, const double* slot_weight, const float* grad_total, float* grad_pred,
+                                   const void* workspace, jspsr_stream_t stream);
 /* Mean SSIM of prepared [0,1] tiles (MeterSSIM.update, evaluation/metrics.py:275-335), pred clamped to [0,1]:
  * same = 0 is piq.ssim(downsample=False) on the valid map with the Gaussian window (window11 ignored, may be NULL);
  * same = 1 is the local ssim (metrics.py:20-63): H x W map over the zero-padded planes with the 11-tap window11 (host

@@ -79,6 +79,12 @@ SIGNATURES = {
     "jspsr_loss_menu_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "jspsr_loss_menu_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_loss_menu_backward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_loss_valid_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "jspsr_loss_valid_forward": (c_i, [c_p, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "jspsr_loss_valid_backward": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "jspsr_loss_menu_valid_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "jspsr_loss_menu_valid_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_loss_menu_valid_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_ssim_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "jspsr_ssim_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "jspsr_metrics_workspace_bytes": (ctypes.c_size_t, [c_i, c_i]),
@@ -107,6 +113,7 @@ SIGNATURES = {
     "jspsr_gate_mlp_backward": (c_i, [c_p] * 7 + [c_i, c_i, c_i] + [c_p] * 6),
     "jspsr_gate_mlp_legacy": (c_i, [c_i]),
     "jspsr_batch_make": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
+    "jspsr_batch_valid": (c_i, [c_p, c_ll, c_p, c_p, c_i, c_p, c_i, c_i, c_p]),
     "jspsr_scene_prepare": (c_i, [c_p] * 7 + [c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),
     "jspsr_scene_finish": (c_i, [c_i, c_p, c_p, c_p] + [c_i] * 9 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_scene_prepare_d4": (c_i, [c_p] * 7 + [c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i, c_p]),

@@ -129,7 +129,88 @@ __global__ __launch_bounds__(256) void batch_kernel(BatchArgs a, int tiles_x) {
   }
 }
 
+// K19 -- the validity plane of a batch: batch_kernel's sample rows and D4 map over a one-byte-per-pixel store, written as
+// (B, 1, k, k) bytes, 1 = valid.  One workgroup makes one 32 x 32 tile of one sample.  Staged through LDS for the same
+// reason as above: a quarter turn walks a COLUMN of the byte store, which read straight from global memory would cost one
+// 64-byte request per output byte; instead the window's rows (runs of up to 32 bytes at any alignment) come in as the
+// aligned dwords that cover them, and the column walk happens on the LDS read, over an odd dword pitch.  Each thread
+// writes four consecutive output bytes (one dword store when k % 4 == 0 and the output is 4-byte aligned).
+constexpr int kVPitch = (kTile + 8) / 4 | 1;                // 32 bytes + the unaligned head, odd: 11 dwords
+
+__global__ __launch_bounds__(256) void batch_valid_kernel(const unsigned char* __restrict__ src, long long src_bytes,
+                                                         unsigned char* __restrict__ out,
+                                                         const long long* __restrict__ scenes, int n_scenes,
+                                                         const int* __restrict__ samples, int k, int tiles_x, int vec) {
+  __shared__ unsigned int lds[kTile * kVPitch];
+  __shared__ int rowoff[kTile];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int ty0 = (blockIdx.x / tiles_x) * kTile, tx0 = (blockIdx.x % tiles_x) * kTile;
+  const int th = min(kTile, k - ty0), tw = min(kTile, k - tx0);
+  const int* row = samples + (size_t)b * 8;
+  const int scene = row[0], y0 = row[1], x0 = row[2], code = row[3];
+  long long off = 0, H = 0, W = 0;
+  bool ok = scene >= 0 && scene < n_scenes && code >= 0 && code < 16;
+  if (ok) {
+    off = scenes[scene * 3]; H = scenes[scene * 3 + 1]; W = scenes[scene * 3 + 2];
+    ok = y0 >= 0 && x0 >= 0 && y0 + k <= H && x0 + k <= W && off >= 0 && off + H * W <= src_bytes;
+  }
+  int sy0, sx0, sy1, sx1;
+  d4_source(code & 15, k, ty0, tx0, sy0, sx0);
+  d4_source(code & 15, k, ty0 + th - 1, tx0 + tw - 1, sy1, sx1);
+  if (sy0 > sy1) { const int t = sy0; sy0 = sy1; sy1 = t; }
+  if (sx0 > sx1) { const int t = sx0; sx0 = sx1; sx1 = t; }
+  const int rows = sy1 - sy0 + 1, seg = sx1 - sx0 + 1;               // window rows (<= 32), bytes per window row (<= 32)
+  if (tid < rows) rowoff[tid] = tid * kVPitch * 4 + (int)((off + (long long)(y0 + sy0 + tid) * W + x0 + sx0) & 3);
+  if (ok) {
+    const int ndw = seg / 4 + 2;                                     // <= 10 < kVPitch
+    for (int idx = tid; idx < rows * ndw; idx += 256) {
+      const int r = idx / ndw, i = idx - r * ndw;
+      const long long s = off + (long long)(y0 + sy0 + r) * W + x0 + sx0;
+      const long long a0 = (s & ~3ll) + 4ll * i;
+      if (a0 >= s + seg) continue;
+      unsigned int v;
+      if (a0 + 4 <= src_bytes) {
+        v = *reinterpret_cast<const unsigned int*>(src + a0);
+      } else {                                                       // a dword that straddles the store's end: byte by byte
+        v = 0;
+        for (int q = 0; q < 4; ++q)
+          if (a0 + q < src_bytes) v |= (unsigned int)src[a0 + q] << (8 * q);
+      }
+      lds[r * kVPitch + i] = v;
+    }
+  }
+  __syncthreads();
+  const int oy = tid >> 3, ox = (tid & 7) * 4;
+  if (oy >= th || ox >= tw) return;
+  const int n = min(4, tw - ox);
+  const unsigned char* l8 = reinterpret_cast<const unsigned char*>(lds);
+  unsigned int v[4];
+  for (int p = 0; p < 4; ++p) {
+    int sy, sx;
+    d4_source(code & 15, k, ty0 + oy, tx0 + ox + min(p, n - 1), sy, sx);
+    v[p] = ok ? (l8[rowoff[sy - sy0] + (sx - sx0)] != 0 ? 1u : 0u) : 0u;     // 0 marks a row outside its scene or store
+  }
+  unsigned char* o = out + ((size_t)b * k + ty0 + oy) * k + tx0 + ox;
+  if (vec) {
+    *reinterpret_cast<unsigned int*>(o) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+  } else {
+    for (int p = 0; p < n; ++p) o[p] = (unsigned char)v[p];
+  }
+}
+
 }  // namespace
+
+extern "C" int jspsr_batch_valid(const unsigned char* store, long long store_bytes, unsigned char* out, const long long* scenes,
+                                 int n_scenes, const int* samples, int B, int k, jspsr_stream_t stream) {
+  if (!store || store_bytes <= 0 || !out || !scenes || !samples || n_scenes <= 0 || B <= 0 || k <= 0 || B > 65535)
+    return jspsr::fail(JSPSR_EINVAL, "batch_valid: bad arguments");
+  if (!jspsr::aligned4(store)) return jspsr::fail(JSPSR_EALIGN, "batch_valid: store not 4-byte aligned");
+  const int tiles_x = (k + kTile - 1) / kTile;
+  const int vec = (k & 3) == 0 && jspsr::aligned4(out);
+  hipLaunchKernelGGL(batch_valid_kernel, dim3(tiles_x * tiles_x, B), dim3(256), 0, static_cast<hipStream_t>(stream), store,
+                     store_bytes, out, scenes, n_scenes, samples, k, tiles_x, vec);
+  return jspsr::check_launch("batch_valid");
+}
 
 extern "C" int jspsr_batch_make(const void* const* src, const long long* src_bytes, float* const* out, const int* channels,
                                 const int* coff, const int* cpitch, const long long* scenes, int n_scenes, const int* samples,

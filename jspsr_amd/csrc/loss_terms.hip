@@ -392,6 +392,155 @@ bool dims_ok(int planes, int H, int W) {
   return planes > 0 && H > 0 && W > 0 && planes <= 65535 && (long long)planes * H * W < (1ll << 40);
 }
 
+// ---- K19: the pointwise terms over the elements a validity plane keeps ---------------------------------------------------
+// valid: one byte per element, nonzero = valid.  The kernels above with pred / gt read behind a select on the plane (never
+// multiplied by it: NaN * 0 is NaN), the same grids, loop order and fold order, so an all-ones plane gives their bits.
+// N, the number of valid elements, is counted as an integer by the sum pass, folded by the combine kernel and left in the
+// workspace for the backward, which forms the host's coefficients (float)(w / (double)N) on the device.  N = 0: every term
+// and every gradient element is 0.
+struct ValidLayout {
+  int nb = 0, nbm = 0;
+  size_t pmax = 0, psum = 0, pcnt = 0, nn = 0, bytes = 0;
+};
+
+ValidLayout valid_layout(int planes, int H, int W) {
+  ValidLayout L;
+  const long long n = (long long)planes * H * W;
+  L.nb = pw_blocks(n);
+  L.nbm = max_blocks(n);
+  size_t off = 16;          // th[4], as in Layout
+  L.pmax = off; off += al16((size_t)L.nbm * 4);
+  L.psum = off; off += al16((size_t)L.nb * 3 * 4);
+  L.pcnt = off; off += al16((size_t)L.nb * 4);
+  L.nn = off; off += 16;    // long long N
+  L.bytes = off;
+  return L;
+}
+
+__global__ __launch_bounds__(PT) void menu_max_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                           const unsigned char* __restrict__ valid, long long n,
+                                                           float* __restrict__ pmax) {
+  __shared__ float red[PT / 64];
+  float m = 0.f;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    const float ad = fabsf(pred[i] - gt[i]);          // loaded beside the plane's byte, not after it; used behind the select
+    m = fmaxf(m, valid[i] ? ad : 0.f);
+  }
+  m = block_reduce<true>(m, red);
+  if (threadIdx.x == 0) pmax[blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(PT) void menu_sum_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                           const unsigned char* __restrict__ valid, long long n, int terms,
+                                                           const float* __restrict__ pmax, int nb, float* __restrict__ th,
+                                                           float* __restrict__ psum, unsigned int* __restrict__ pcnt) {
+  __shared__ float red[3][PT / 64];
+  __shared__ unsigned int redc[PT / 64];
+  float thf = 0.f, t2f = 0.f, tw = 0.f;
+  if (terms & T_BERHU) {
+    float m = 0.f;
+    for (int r = threadIdx.x; r < nb; r += PT) m = fmaxf(m, pmax[r]);
+    m = block_reduce<true>(m, red[0]);
+    __syncthreads();
+    const double t = 0.6 * (double)m;
+    thf = (float)t; t2f = (float)(t * t); tw = (float)(2.0 * t);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { th[0] = thf; th[1] = t2f; th[2] = tw; th[3] = 0.f; }
+  }
+  float sb = 0.f, sc = 0.f, sn = 0.f;
+  unsigned int nv = 0;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    const float x = pred[i], y = gt[i];               // loaded beside the plane's byte, not after it
+    if (!valid[i]) continue;
+    ++nv;
+    if (terms & T_BERHU) sb += berhu_elem(fabsf(x - y), thf, t2f, tw);
+    if (terms & T_BCE) sc += bce_elem(x, y);
+    if (terms & T_NORM) sn += 1.f - unit(x) * unit(y);
+  }
+  float v[3] = {sb, sc, sn};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
+    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v[q];
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) nv += __shfl_xor(nv, d, 64);
+  if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = nv;
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    float t = 0.f;
+    for (int w = 0; w < PT / 64; ++w) t += red[threadIdx.x][w];
+    psum[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+  } else if (threadIdx.x == 3) {
+    unsigned int t = 0;
+    for (int w = 0; w < PT / 64; ++w) t += redc[w];
+    pcnt[blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(PT) void menu_bwd_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                           const unsigned char* __restrict__ valid, long long n, int terms,
+                                                           const float* __restrict__ th, const long long* __restrict__ nn,
+                                                           const float* __restrict__ gscale, double wb, double wc, double wn,
+                                                           float* __restrict__ grad) {
+  const long long nv = nn[0];
+  if (nv <= 0) return;                            // nothing valid: the caller's zeros stand
+  const double dn = (double)nv;
+  const float cb = (float)(wb / dn), cc = (float)(wc / dn), cn = (float)(wn / (1e-12 * dn));
+  const float up = gscale ? gscale[0] : 1.f;
+  const float thf = (terms & T_BERHU) ? th[0] : 0.f, tw = (terms & T_BERHU) ? th[2] : 1.f;
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    if (!valid[i]) continue;                      // the gradient there stays the +0.0 the caller wrote
+    const float x = pred[i], y = gt[i];
+    float g = 0.f;
+    if (terms & T_BERHU) {
+      const float d = x - y, ad = fabsf(d);
+      g += cb * (ad <= thf ? sgnf(d) : 2.f * ad / tw * sgnf(d));
+    }
+    if (terms & T_BCE) g += cc * (1.f / (1.f + expf(-x)) - y);
+    if (terms & T_NORM) g += fabsf(x) <= 1e-12f ? -cn * unit(y) : 0.f;
+    grad[i] += up * g;
+  }
+}
+
+// menu_combine_kernel with the fourth wave folding the integer counts instead of SSIM's partials; nn[0] = N
+__global__ void menu_combine_valid_kernel(const float* __restrict__ psum, const unsigned int* __restrict__ pcnt, int nb,
+                                          const float* __restrict__ base, KeyMap km, float* __restrict__ out,
+                                          long long* __restrict__ nn) {
+  __shared__ double acc[3];
+  __shared__ long long cnt;
+  const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (q < 3) {
+    const double s = wave_fold(psum, nb, 3, q);
+    if (lane == 0) acc[q] = s;
+  } else {
+    long long s = 0;
+    for (int r = lane; r < nb; r += 64) s += (long long)pcnt[r];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+    if (lane == 0) cnt = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const long long n = cnt;
+    float f[NSLOT];
+    for (int i = 0; i < 3; ++i) f[i] = base ? base[i] : 0.f;
+    f[S_BERHU] = n > 0 ? (float)(acc[0] / (double)n) : 0.f;
+    f[S_BCE] = n > 0 ? (float)(acc[1] / (double)n) : 0.f;
+    f[S_NORM] = n > 0 ? (float)(acc[2] / (double)n) : 0.f;
+    f[S_SSIM] = 0.f;
+    double tot = 0.0;
+    for (int i = 0; i < km.n; ++i) {
+      const float v = f[km.slot[i]];
+      out[i] = v;
+      tot += km.w[i] * (double)v;
+    }
+    out[km.n] = (float)tot;
+    nn[0] = n;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W) {
@@ -468,6 +617,63 @@ extern "C" int jspsr_loss_menu_backward(const float* pred, const float* gt, int 
     if (int e = check_launch("ssim_backward")) return e;
   }
   return JSPSR_OK;
+}
+
+extern "C" size_t jspsr_loss_menu_valid_workspace_bytes(int terms, int planes, int H, int W) {
+  if (terms <= 0 || (terms & ~T_ALL) || (terms & T_SSIM) || !dims_ok(planes, H, W)) return 0;
+  return valid_layout(planes, H, W).bytes;
+}
+
+extern "C" int jspsr_loss_menu_valid_forward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                             int planes, int H, int W, int n_keys, const int* key_slot,
+                                             const double* key_weight, const float* base_losses, float* out, void* workspace,
+                                             jspsr_stream_t stream) {
+  if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
+      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
+    return fail(JSPSR_EINVAL, "loss_menu_valid_forward: bad arguments");
+  if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_forward: SSIM over a validity plane is not built");
+  KeyMap km{};
+  km.n = n_keys;
+  for (int i = 0; i < n_keys; ++i) {
+    const int s = key_slot[i];
+    const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < S_SSIM && (terms & (1 << (s - S_BERHU))));
+    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_valid_forward: key %d has slot %d outside the configured terms", i, s);
+    km.slot[i] = s;
+    km.w[i] = key_weight[i];
+  }
+  const ValidLayout L = valid_layout(planes, H, W);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  if (terms & T_BERHU) {
+    hipLaunchKernelGGL(menu_max_valid_kernel, dim3(L.nbm), dim3(PT), 0, st, pred, gt, valid, n,
+                       reinterpret_cast<float*>(ws + L.pmax));
+    if (int e = check_launch("loss_menu_valid_max")) return e;
+  }
+  hipLaunchKernelGGL(menu_sum_valid_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
+                     reinterpret_cast<const float*>(ws + L.pmax), L.nbm, reinterpret_cast<float*>(ws),
+                     reinterpret_cast<float*>(ws + L.psum), reinterpret_cast<unsigned int*>(ws + L.pcnt));
+  if (int e = check_launch("loss_menu_valid_sum")) return e;
+  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const float*>(ws + L.psum),
+                     reinterpret_cast<const unsigned int*>(ws + L.pcnt), L.nb, base_losses, km, out,
+                     reinterpret_cast<long long*>(ws + L.nn));
+  return check_launch("loss_menu_valid_combine");
+}
+
+extern "C" int jspsr_loss_menu_valid_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                              int planes, int H, int W, const double* slot_weight, const float* grad_total,
+                                              float* grad_pred, const void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
+      !dims_ok(planes, H, W))
+    return fail(JSPSR_EINVAL, "loss_menu_valid_backward: bad arguments");
+  if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_backward: SSIM over a validity plane is not built");
+  const ValidLayout L = valid_layout(planes, H, W);
+  const char* ws = static_cast<const char*>(workspace);
+  const long long n = (long long)planes * H * W;
+  hipLaunchKernelGGL(menu_bwd_valid_kernel, dim3(L.nb), dim3(PT), 0, static_cast<hipStream_t>(stream), pred, gt, valid, n,
+                     terms, reinterpret_cast<const float*>(ws), reinterpret_cast<const long long*>(ws + L.nn), grad_total,
+                     slot_weight[S_BERHU], slot_weight[S_BCE], slot_weight[S_NORM], grad_pred);
+  return check_launch("loss_menu_valid_backward");
 }
 
 extern "C" size_t jspsr_ssim_workspace_bytes(int planes, int H, int W, int same) {

@@ -68,29 +68,43 @@ class DeviceScenes:
     give a crop that fails.  This is stricter than the reference: a scene whose only bad pixels no crop ever covers is
     refused here.  `elev_min` / `elev_max` are the config's Python numbers (tensor_kwargs min / max).
 
-    Voids (no-data pixels) are not taken here: `nodata` raises NotImplementedError together with `hr_dem`.  The store without
-    a ground truth, `infer.InferenceScenes(nodata=...)`, fills them on the device at construction (K17); scores over the
-    valid pixels only are `summary.summarise(valid=...)` with `summary.valid_plane` (K18).
+    Voids (no-data pixels) of the GROUND TRUTH (K19): `hr_nodata=v` marks an hr_dem pixel as a void if it is not finite or
+    equals `np.float32(v)` (`void_pixels`' rule; v = NaN: not finite only), and `valid=[per-scene (H,W) uint8 / bool
+    planes]` is ANDed in (a water mask, or an `InferenceScenes.void_out == 0`).  Either keyword gives the store the member
+    `store["valid"]`: one byte per pixel, 1 = valid, all scenes back to back at the pixel offsets of `scene_table`, padded
+    to a multiple of 4 bytes.  hr_dem is uploaded unchanged, voids included; the batches then carry `batch["valid"]`
+    ((B,1,k,k) uint8, lined up with `batch["hr_dem"]` under every crop and D4 code, a second launch: jspsr_batch_valid),
+    which the masked criterion takes: `criterion(pred, gt, valid=batch["valid"])` -- a masked pixel has no influence whatever
+    the rasters hold there.  The hr_dem range checks read the valid pixels only; a scene without a valid hr_dem pixel is a
+    ValueError naming it.  With both keywords None nothing changes and "valid" is absent from the store and the batches.
+    lr_dem must still be finite: voids in lr_dem AND hr_dem of one store are not built, so `nodata` (the lr_dem voids of
+    `infer.InferenceScenes`, filled on the device at construction, K17) still raises NotImplementedError together with
+    hr_dem.  Scores over the valid pixels only are `summary.summarise(valid=...)` with `summary.valid_plane` (K18).
     """
 
     def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
                  relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
-                 normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda", nodata=None):
+                 normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda", nodata=None,
+                 hr_nodata=None, valid=None):
         if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
             raise KeyError("hr_dem")
         if nodata is not None:
-            raise NotImplementedError("nodata: voids in a store with hr_dem (training on voids) are not built; "
-                                      "`infer.InferenceScenes` takes them, and `summary.summarise(valid=...)` scores over valid pixels")
+            raise NotImplementedError("nodata: voids of lr_dem in a store with hr_dem are not built (`infer.InferenceScenes` "
+                                      "takes them); the voids of the ground truth are `hr_nodata=` / `valid=`, and "
+                                      "`summary.summarise(valid=...)` scores over valid pixels")
         self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
-                    image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device)
+                    image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device,
+                    hr_nodata=hr_nodata, valid=valid)
 
     def _setup(self, raw: dict, coord, *, relative, elev_min, elev_max, elev_log, scale_mask, mask_channel, image_range,
-               label_range, normalize, ids, device, base=None, nodata=None, void_margin=0, fill_limit=None):
+               label_range, normalize, ids, device, base=None, nodata=None, void_margin=0, fill_limit=None, hr_nodata=None,
+               valid=None):
         """Checks, layout and upload of a store holding the kinds of `raw` that are not None (`infer.InferenceScenes` is
         the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`.  nodata, void_margin,
-        fill_limit: the voids of lr_dem (K17, `infer.InferenceScenes`); nodata=None changes nothing."""
+        fill_limit: the voids of lr_dem (K17, `infer.InferenceScenes`); nodata=None changes nothing.  hr_nodata, valid: the
+        voids of hr_dem (K19, see the class docstring); both None changes nothing."""
         lr_dem = raw["lr_dem"]
         void_margin = _whole("void_margin", void_margin)
         fill_limit = None if fill_limit is None else _whole("fill_limit", fill_limit)
@@ -152,10 +166,15 @@ class DeviceScenes:
             if len(base) != n:
                 raise ValueError(f"base: {len(base)} values, lr_dem has {n} scenes")
             self.base = list(base)
+        planes = None
+        if hr_nodata is not None or valid is not None:
+            planes = self._valid_planes(host, hr_nodata, valid)
         for i in range(n):
             s = {k: v[i] for k, v in host.items()}
             if voids is not None:
                 s["lr_dem"] = s["lr_dem"][~voids[i]]                 # the range checks read the valid pixels only
+            if planes is not None:
+                s["hr_dem"] = s["hr_dem"][planes[i]]
             self._check_scene(i, s)
         offs = np.zeros(n + 1, dtype=np.int64)
         offs[1:] = np.cumsum([h * w for h, w in self.shapes])
@@ -167,6 +186,35 @@ class DeviceScenes:
                       | (LABEL_11 if label_range == "[-1, 1]" else 0) | (IMAGE_255 if image_range == "[0, 255]" else 0))
         if voids is not None:
             self._fill_voids(voids, nodata, void_margin, fill_limit)
+        if planes is not None:                   # K19: one byte per pixel at the scenes' pixel offsets, padded to 4 bytes
+            flat = np.concatenate([p.reshape(-1) for p in planes]).astype(np.uint8)
+            self.store["valid"] = torch.from_numpy(np.concatenate([flat, np.zeros(-flat.size % 4, dtype=np.uint8)])).to(self.device)
+            self.hr_nodata = hr_nodata
+
+    hr_nodata = None                             # K19: the no-data value `store["valid"]` was made with, if any
+
+    def _valid_planes(self, host: dict, hr_nodata, valid) -> list:
+        """Per-scene (H, W) bool planes of the hr_dem pixels that count: not a void by `hr_nodata`, and set in `valid`."""
+        if "hr_dem" not in host:
+            raise ValueError("hr_nodata / valid: the store has no hr_dem")
+        n = len(host["hr_dem"])
+        for i, a in enumerate(host["lr_dem"]):
+            if not np.isfinite(a).all():
+                raise ValueError(f"scene {self.ids[i]}: lr_dem is not finite; voids in lr_dem and hr_dem of one store are not built")
+        if valid is not None and len(valid) != n:
+            raise ValueError(f"valid: {len(valid)} planes, hr_dem has {n} scenes")
+        planes = []
+        for i, a in enumerate(host["hr_dem"]):
+            p = np.ones(a.shape[:2], dtype=bool) if hr_nodata is None else ~void_pixels(a[..., 0], hr_nodata)
+            if valid is not None:
+                u = valid[i].cpu().numpy() if isinstance(valid[i], torch.Tensor) else np.asarray(valid[i])
+                if u.dtype not in (np.uint8, np.bool_) or u.shape != a.shape[:2]:
+                    raise ValueError(f"valid[{i}]: expected a uint8 or bool plane of {a.shape[:2]}, got {u.dtype} {u.shape}")
+                p = p & (u != 0)
+            if not p.any():
+                raise ValueError(f"scene {self.ids[i]}: no valid pixel, every hr_dem value is a void or masked")
+            planes.append(p)
+        return planes
 
     # K17: the members of a store built with `nodata`; None otherwise (and then absent from the instance)
     nodata = void = void_out = void_counts = None
@@ -250,6 +298,17 @@ class DeviceScenes:
                                         len(self.mask_channel) + 1, torch.cuda.current_stream(self.device).cuda_stream),
                    "jspsr_batch_make")
 
+    def make_valid(self, table: torch.Tensor, k: int) -> torch.Tensor:
+        """The batch's validity plane, (B, 1, k, k) uint8, from the same sample rows (K19, one launch of jspsr_batch_valid);
+        only for a store built with `hr_nodata` or `valid`."""
+        plane = self.store["valid"]
+        B = table.shape[0]
+        out = torch.empty((B, 1, k, k), dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.load().jspsr_batch_valid(plane.data_ptr(), plane.numel(), out.data_ptr(), self.scene_table.data_ptr(),
+                                                 len(self), table.data_ptr(), B, k,
+                                                 torch.cuda.current_stream(self.device).cuda_stream), "jspsr_batch_valid")
+        return out
+
 
 def ctypes_arrays(scenes: DeviceScenes, outs: dict):
     """The six-entry host arrays of jspsr_batch_make (include/jspsr_hip.h)."""
@@ -321,6 +380,8 @@ class _Batches:
                 outs[kind] = (torch.empty((B, S.channels[kind], side, side), **kw), 0)
                 batch[kind] = outs[kind][0]
         S.make(table, side, outs)
+        if "valid" in S.store:                               # K19: a second launch, only for a store that has the plane
+            batch["valid"] = S.make_valid(table, side)
         batch["base"] = table[:, 4].view(torch.float32)      # (B,) fp32 view of the rows' base elevations, on the device
         batch["meta"] = meta
         return batch
@@ -360,7 +421,8 @@ class RandomCropBatches(_Batches):
     batch is fetched: the stream is the same unless the caller draws from the same RandomState in between).
     Each yielded dict holds the present rasters as (B, C, k, k) fp32 device tensors, `base` (B,) on the device and `meta`
     as collate_fn gives it.  concat=True writes [lr_dem | image | mask | canopy | coord] into one tensor `images` (EDSR's
-    input) and gives the kinds as its channel slices.
+    input) and gives the kinds as its channel slices.  A store built with `hr_nodata` / `valid` adds `valid`, the
+    (B, 1, k, k) uint8 plane of the hr_dem pixels that count (K19).
     """
 
     def __init__(self, scenes: DeviceScenes, batch_size: int, patch_size: int, augment: bool = True, rng=None,

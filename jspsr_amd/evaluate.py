@@ -238,29 +238,47 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
     Loss values and scores stay on the device until the end: the pass synchronises once (one device-to-host copy).
 
     collector: e.g. a `summary.ScenePredictions`; its `add(pred, meta)` is called after each forward (the scene mosaics in
-    metres for `summary.summarise`, the whole-set table of summarise_evaluation).  None (the default) changes nothing."""
+    metres for `summary.summarise`, the whole-set table of summarise_evaluation).  None (the default) changes nothing.
+
+    Batches that carry "valid" (a store built with `hr_nodata` / `valid`, K19): the criterion is fed ONE SAMPLE AT A TIME
+    with its slice of the plane, each sample weighing 1 as in the reference's batch of one -- a masked batch value is not
+    the mean of its samples' values, because their counts of valid pixels differ.  The per-tile meters (K10) are not masked:
+    a meter together with such a batch raises NotImplementedError before the forward.  Pass meter=None (the scores are then
+    None; compare_input is refused) and take the whole-set table from `collector=summary.ScenePredictions(...)` followed by
+    `summary.summarise(valid=...)`."""
     model.eval()
-    meter.reset()
+    if meter is None and compare_input:
+        raise ValueError("evaluate: compare_input needs a meter")
+    if meter is not None:
+        meter.reset()
     meter_in = meter.clone() if compare_input else None
     additive = _sample_additive(criterion)
     keys, rows, weights = None, [], []
     for batch in batches:
         criterion.reset()
         inputs, gt, _base, meta = batch_pair(batch, model_name, input_data)
+        valid = batch.get("valid")
+        if valid is not None and meter is not None:
+            raise NotImplementedError("evaluate: a batch with a validity plane and a meter: masked per-tile meters are not "
+                                      "built; pass meter=None and score with collector=ScenePredictions + summarise(valid=)")
         pred = model(*inputs)
         if collector is not None:
             collector.add(pred, meta)
         B = gt.size(0)
-        spans = [(0, B)] if additive else [(i, i + 1) for i in range(B)]
+        spans = [(0, B)] if additive and valid is None else [(i, i + 1) for i in range(B)]
         for lo, hi in spans:
             if lo > 0:
                 criterion.reset()
-            out = criterion(pred[lo:hi], gt[lo:hi])
+            if valid is None:
+                out = criterion(pred[lo:hi], gt[lo:hi])
+            else:
+                out = criterion(pred[lo:hi], gt[lo:hi], valid=valid[lo:hi])
             if keys is None:
                 keys = list(out)
             rows.append(torch.stack([out[k].detach().float().reshape(()) for k in keys]))
             weights.append(hi - lo)
-        meter.update(pred, gt, meta=meta)
+        if meter is not None:
+            meter.update(pred, gt, meta=meta)
         if compare_input:
             data_input = inputs[0][:, 0:1]
             if data_input.shape[-2:] != gt.shape[-2:]:
@@ -269,10 +287,11 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
             meter_in.update(data_input, gt, meta=meta)
     if keys is None:
         raise ValueError("evaluate: no batches")
-    vals = _fetch([meter] + ([meter_in] if compare_input else []), torch.stack(rows)).astype(np.float64)
+    vals = _fetch(([meter] if meter is not None else []) + ([meter_in] if compare_input else []),
+                  torch.stack(rows)).astype(np.float64)
     total_w = sum(weights)
     means = {k: sum(float(vals[i, j]) * weights[i] for i in range(len(weights))) / total_w for j, k in enumerate(keys)}
-    result = (meter.get_score(), means["Total"], {k: v for k, v in means.items() if k != "Total"})
+    result = (meter.get_score() if meter is not None else None, means["Total"], {k: v for k, v in means.items() if k != "Total"})
     return result + (meter_in.get_score(),) if compare_input else result
 
 

@@ -52,6 +52,64 @@ class _FusedLoss(torch.autograd.Function):
         return gp, None, None, None, None
 
 
+def _plane(pred, valid):
+    """The validity plane of a masked call as contiguous (B,C,H,W) bytes: (B,1,H,W) or (B,C,H,W), uint8 or bool, on pred's
+    device; nonzero = valid.  Raised before any launch: TypeError for another dtype, ValueError for another shape."""
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"loss: valid must be a uint8 or bool tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
+    B, C, H, W = pred.shape
+    if valid.dim() != 4 or tuple(valid.shape) not in {(B, 1, H, W), (B, C, H, W)}:
+        raise ValueError(f"loss: valid must be (B,1,H,W) or (B,C,H,W) of pred {tuple(pred.shape)}, got {tuple(valid.shape)}")
+    if valid.device != pred.device:
+        raise ValueError(f"loss: valid is on {valid.device}, pred on {pred.device}")
+    if valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    return valid.expand(B, C, H, W).contiguous()
+
+
+class _FusedLossValid(torch.autograd.Function):
+    """_FusedLoss over the elements `valid` keeps (jspsr_loss_valid_forward / _backward, K19)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, valid, w1, w2, wg):
+        pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
+        B, C, H, W = pred_c.shape
+        lib = _lib.load()
+        ws = torch.empty(lib.jspsr_loss_valid_workspace_bytes(B * C, H, W), dtype=torch.uint8, device=pred.device)
+        losses = torch.empty(4, dtype=torch.float32, device=pred.device)
+        _lib.check(lib.jspsr_loss_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), w1, w2, wg,
+                                                losses.data_ptr(), ws.data_ptr(), B * C, H, W, _stream()),
+                   "jspsr_loss_valid_forward")
+        ctx.save_for_backward(pred_c, gt_c, valid, ws)
+        ctx.w = (w1, w2, wg)
+        ctx.mark_non_differentiable(gt)
+        return losses
+
+    @staticmethod
+    def backward(ctx, glosses):
+        pred, gt, valid, ws = ctx.saved_tensors
+        w1, w2, wg = ctx.w
+        B, C, H, W = pred.shape
+        g = glosses.float().contiguous()
+        gp = torch.empty_like(pred)
+        lib = _lib.load()
+        _lib.check(lib.jspsr_loss_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), g[3:4].contiguous().data_ptr(),
+                                                 w1, w2, wg, gp.data_ptr(), ws.data_ptr(), B * C, H, W, _stream()),
+                   "jspsr_loss_valid_backward")
+        return gp, None, None, None, None, None
+
+
+def _fused(pred, gt, valid, weights):
+    """The fused L1 + L2 + Grad pair, unmasked (valid None: today's calls) or over a validity plane."""
+    if valid is None:
+        return _FusedLoss.apply(pred, gt, *weights)
+    if not pred.is_cuda:
+        raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
+    if pred.shape != gt.shape or pred.dim() != 4:
+        raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
+    return _FusedLossValid.apply(pred, gt, _plane(pred, valid), *weights)
+
+
 class MultiLoss(torch.nn.Module):
     """Returns the reference's dict {"L1","L2","Grad","Total"} (loss_schemes.py:61-72).  Gradients flow
     through "Total" (what the reference back-propagates, train/train_utils.py:217)."""
@@ -61,8 +119,10 @@ class MultiLoss(torch.nn.Module):
         self.weights = (float(l1), float(l2), float(grad))
         self.out = {}
 
-    def forward(self, pred, gt):
-        v = _FusedLoss.apply(pred, gt, *self.weights)
+    def forward(self, pred, gt, valid=None):
+        """valid: None, or the plane of the elements that count ((B,1,H,W) or (B,C,H,W), uint8 or bool, on the device; see
+        `Criterion`): a masked element has no influence, whatever pred and gt hold there."""
+        v = _fused(pred, gt, valid, self.weights)
         self.out = {"L1": v[0].detach(), "L2": v[1].detach(), "Grad": v[2].detach(), "Total": v[3]}
         return self.out
 
@@ -165,14 +225,70 @@ class _MenuLoss(torch.autograd.Function):
         return gp, None, None
 
 
-def _evaluate(spec, pred, gt):
-    """-> (components in config order, Total): one fused forward, one fused backward."""
+class _MenuLossValid(torch.autograd.Function):
+    """_MenuLoss over the elements `valid` keeps (jspsr_loss_valid_* for the L1 / L2 / Grad part, jspsr_loss_menu_valid_*
+    for the rest, K19)."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, valid, spec):
+        pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
+        B, C, H, W = pred_c.shape
+        P = B * C
+        lib = _lib.load()
+        base, bws = None, None
+        if spec.base:
+            bws = torch.empty(lib.jspsr_loss_valid_workspace_bytes(P, H, W), dtype=torch.uint8, device=pred.device)
+            base = torch.empty(4, dtype=torch.float32, device=pred.device)
+            _lib.check(lib.jspsr_loss_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), *spec.base_w,
+                                                    base.data_ptr(), bws.data_ptr(), P, H, W, _stream()),
+                       "jspsr_loss_valid_forward")
+        ws = torch.empty(lib.jspsr_loss_menu_valid_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
+        out = torch.empty(len(spec.keys) + 1, dtype=torch.float32, device=pred.device)
+        _lib.check(lib.jspsr_loss_menu_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
+                                                     len(spec.keys), spec.c_slots, spec.c_weights,
+                                                     base.data_ptr() if base is not None else None, out.data_ptr(),
+                                                     ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_forward")
+        ctx.save_for_backward(pred_c, gt_c, valid, ws, bws)
+        ctx.spec = spec
+        ctx.mark_non_differentiable(gt)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, valid, ws, bws = ctx.saved_tensors
+        spec = ctx.spec
+        B, C, H, W = pred.shape
+        P = B * C
+        n = len(spec.keys)
+        g = gout[n:n + 1].float().contiguous()
+        lib = _lib.load()
+        if spec.base:   # writes the L1 / L2 / Grad part, +0.0 at the invalid elements; the menu adds at the valid ones
+            gp = torch.empty_like(pred)
+            _lib.check(lib.jspsr_loss_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), g.data_ptr(),
+                                                     *spec.base_w, gp.data_ptr(), bws.data_ptr(), P, H, W, _stream()),
+                       "jspsr_loss_valid_backward")
+        else:
+            gp = torch.zeros_like(pred)
+        _lib.check(lib.jspsr_loss_menu_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
+                                                      spec.c_slot_w, g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
+                   "jspsr_loss_menu_valid_backward")
+        return gp, None, None, None
+
+
+def _evaluate(spec, pred, gt, valid=None):
+    """-> (components in config order, Total): one fused forward, one fused backward.  valid: the plane of the elements
+    that count, or None (today's calls)."""
     spec.check(pred, gt)
     n = len(spec.keys)
+    if valid is not None:
+        if 6 in spec.slots:
+            raise NotImplementedError("loss SSIM: a validity plane is not built (an 11x11-window validity rule is a feature "
+                                      "of its own); drop SSIM from the criterion or pass valid=None")
+        valid = _plane(pred, valid)
     if spec.terms == 0:      # L1 / L2 / Grad (any aliases) only: exactly the fused pair MultiLoss runs
-        v = _FusedLoss.apply(pred, gt, *spec.base_w)
+        v = _FusedLoss.apply(pred, gt, *spec.base_w) if valid is None else _FusedLossValid.apply(pred, gt, valid, *spec.base_w)
         return [v[s].detach() for s in spec.slots], v[3]
-    v = _MenuLoss.apply(pred, gt, spec)
+    v = _MenuLoss.apply(pred, gt, spec) if valid is None else _MenuLossValid.apply(pred, gt, valid, spec)
     return [v[i].detach() for i in range(n)], v[n]
 
 
@@ -184,8 +300,8 @@ class LossTerm(torch.nn.Module):
         self.name = str(name)
         self.spec = _Spec({self.name: 1.0})
 
-    def forward(self, pred, gt):
-        return _evaluate(self.spec, pred, gt)[1]
+    def forward(self, pred, gt, valid=None):
+        return _evaluate(self.spec, pred, gt, valid)[1]
 
     def __str__(self):
         return f"{self.__class__.__name__}({self.name}), fused HIP"
@@ -215,7 +331,15 @@ def get_loss(name):
 class Criterion(torch.nn.Module):
     """get_criterion's criterion on the device: the components (detached device scalars, keys in the config's spelling
     and order) and "Total" (what carries gradient, train/train_utils.py:214-226).  One fused forward and one fused
-    backward for the whole dict; no host synchronisation, so GraphedStep can capture it."""
+    backward for the whole dict; no host synchronisation, so GraphedStep can capture it.
+
+    forward(pred, gt, valid=None) -- valid (K19): the plane of the elements that count, (B,1,H,W) or (B,C,H,W), uint8 or
+    bool, on the device (a batch's `batch["valid"]`); a (B,1,H,W) plane is expanded over C here.  A masked element has no
+    influence whatever pred and gt hold there, and its gradient is +0.0.  With d = pred - gt and N the valid elements of the
+    whole call: L1, L2, BerHu (th = 0.6 max_valid |d|), BCE and Norm sum over the valid elements and divide by N; a Sobel
+    output counts iff its nine replicate-clamped taps are valid, Grad = sum_counted (|gx| + |gy|) / (2 N_g).  N = 0 or N_g =
+    0 gives value and gradient 0, not NaN.  N and N_g stay on the device, so the masked pair captures in a graph as well.
+    An all-ones plane gives the bits of valid=None.  SSIM with a plane raises NotImplementedError before any launch."""
 
     def __init__(self, weights, single=False):
         super().__init__()
@@ -225,8 +349,8 @@ class Criterion(torch.nn.Module):
         self.spec = _Spec(weights)
         self.out = {}
 
-    def forward(self, pred, gt):
-        comps, total = _evaluate(self.spec, pred, gt)
+    def forward(self, pred, gt, valid=None):
+        comps, total = _evaluate(self.spec, pred, gt, valid)
         self.out = dict(zip(self.spec.keys, comps))
         self.out.pop("Total", None)
         self.out["Total"] = total

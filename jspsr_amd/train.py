@@ -143,7 +143,11 @@ def train_one_epoch(model, batches, criterion, optimizer, scheduler, reducer, mo
     step: a `graph.GraphedStep` built over the same model, reducer, optimizer and criterion.  The body then is
     `step(inputs, gt)`; only "Total" is reported (the graph's loss tensor; per-term values are not available under a
     graph), "grad" needs `optimizer.grad_range` to have been set BEFORE the capture (`optimizer.fused_grad_range()`), and
-    "pred" is not available."""
+    "pred" is not available.
+
+    A batch that carries "valid" (a store built with `hr_nodata` / `valid`, K19) is scored over its valid pixels:
+    `criterion(pred, gt, valid=batch["valid"])`; the reported values are the masked ones.  With a GraphedStep such a batch
+    raises NotImplementedError."""
     monitor_value = tuple(monitor_value or ())
     for m in monitor_value:
         if m not in MONITORS:
@@ -166,13 +170,17 @@ def train_one_epoch(model, batches, criterion, optimizer, scheduler, reducer, mo
         for batch in batches:
             criterion.reset()
             inputs, gt, _base, _meta = batch_pair(batch, model_name, input_data)
+            valid = batch.get("valid")
             if step is not None:
+                if valid is not None:
+                    raise NotImplementedError("train_one_epoch: a batch with a validity plane (a store built with hr_nodata / "
+                                              "valid) and a GraphedStep: the masked graphed step is not built, use the eager step")
                 values = [step(inputs, gt).detach().float().reshape(())]
                 names, pred = ["Total"], None
             else:
                 reducer.zero_grad()
                 pred = model(*inputs)
-                out = criterion(pred, gt)
+                out = criterion(pred, gt) if valid is None else criterion(pred, gt, valid=valid)
                 out["Total"].backward()
                 reducer.finish()
                 optimizer.step()
