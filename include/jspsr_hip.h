@@ -362,7 +362,18 @@ int jspsr_conv2d_wgrad_scaled(int dtype, const void* G, int Cg, int g_cstride, i
  * Tensors are (pointer, channel pitch, channel offset) slices of NHWC buffers, `npix` pixels,
  * `C` channels (multiple of 4 for fp32 / 8 for bf16); statistics and parameters are fp32.
  * workspace: jspsr_reduce_workspace_bytes(dtype, C, nseg) bytes, 16-byte aligned
- * (nseg = 1, or the batch size for the per-image gate kernels).
+ * (nseg = 1, or the batch size for the per-image gate kernels).  It is the maximum over what the entry points write,
+ * in floats, with chunks = the pixel chunks of a segment (at most max(1, JSPSR_RED_BLOCKS / (ceil(C / vec / 64) * nseg)),
+ * JSPSR_RED_BLOCKS = 1024 by default) and rows = nseg * chunks:
+ *   jspsr_bn_forward            scale | shift [2][C], then partial rows [r][2][C]: r = chunks with its own statistics
+ *                               pass, r = min(ext_rows, 256) with ext_partial (copied, or folded when ext_rows > 256)
+ *                               -> up to (2 + 2 * 256) C whatever the chunk count
+ *   jspsr_bn_backward           coef [3][C], then partial rows [r][2][C], r = chunks (own reduce pass, or the fold of
+ *                               more than 1024 ext_partial rows; up to 1024 such rows are read in place)
+ *   jspsr_act_backward          partial rows [chunks][C]
+ *   jspsr_gate_pool             sum | max | index, [rows][C] each
+ *   jspsr_gate_backward_reduce  partial rows [rows][C]
+ * -> max(3 rows + 4, 2 + 2 * 256) * C floats (+ 64 bytes).
  */
 size_t jspsr_reduce_workspace_bytes(int dtype, int C, int nseg);
 

@@ -757,7 +757,12 @@ extern "C" size_t jspsr_reduce_workspace_bytes(int dtype, int C, int nseg) {
   const int vec = dtype == JSPSR_F32 ? 4 : 8;
   const RedGeom g = make_red(1LL << 40, nseg, C, vec);  // the most chunks any pixel count can get
   const size_t rows = (size_t)nseg * g.chunks;
-  return (rows * 3 + 4) * (size_t)C * sizeof(float) + 64;
+  // the maximum over what the entry points of this file write (include/jspsr_hip.h has the table): the three-plane
+  // layouts over `rows` partial rows, and the BatchNorm forward's copy / fold of external statistics rows, which is
+  // 256 rows deep whatever the chunk count (it alone is the larger one from 7 channel blocks on, or under a small
+  // JSPSR_RED_BLOCKS)
+  const size_t planes = rows * 3 + 4, fwd_ext = 2 + 2 * 256;
+  return (planes > fwd_ext ? planes : fwd_ext) * (size_t)C * sizeof(float) + 64;
 }
 
 extern "C" int jspsr_bn_forward(int dtype, const void* x, int x_cs, int x_coff, const void* res, int r_cs, int r_coff,
