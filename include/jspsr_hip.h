@@ -202,7 +202,7 @@ int jspsr_prop_logits_backward_f32(const float* grad_out, const float* dem, cons
  * Replaces conv_weight (without its Sigmoid) and conv_offset of Generator.forward, models/components/spn.py:41-52,66-68
  * (and BasicDepthEncoder's heads, models/LRRU.py:238-247), and their autograd.
  *   x      NHWC feature (B,H,W,Cin) of `dtype` (0 fp32 / 1 bf16, as JSPSR_F32 / JSPSR_BF16 below), channel pitch x_cstride,
- *          first channel x_coff (elements; multiples of 4 fp32 / 8 bf16), 16-byte aligned
+ *          first channel x_coff >= 0 (elements; multiples of 4 fp32 / 8 bf16), 16-byte aligned
  *   w25    [25][Cin] fp32: rows 0..8 = conv_weight.0.weight, rows 9..24 = conv_offset.conv.0.weight;  b25 [25] the biases
  *   planes [B][25][H][W] fp32 = the `head` operand of jspsr_prop_logits_forward_f32
  * jspsr_head_ok(dtype, B, H, W, Cin) != 0: H * W a multiple of 32, Cin in {32, 64, 128}.

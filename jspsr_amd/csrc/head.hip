@@ -341,7 +341,7 @@ int check_shape(const char* who, int dtype, int B, int HW, int Cin, int cs, int 
   if (B <= 0 || HW <= 0 || HW % 32) return jspsr::fail(JSPSR_EINVAL, "%s: H*W = %d must be a positive multiple of 32", who, HW);
   if (!cin_ok(Cin)) return jspsr::fail(JSPSR_EINVAL, "%s: Cin = %d (built: 32, 64, 128)", who, Cin);
   const int e = dtype == JSPSR_BF16 ? 8 : 4;
-  if (cs < coff + Cin || cs % e || coff % e) return jspsr::fail(JSPSR_EINVAL, "%s: channel pitch %d / offset %d (Cin %d, 16-byte chunks)", who, cs, coff, Cin);
+  if (cs < coff + Cin || coff < 0 || cs % e || coff % e) return jspsr::fail(JSPSR_EINVAL, "%s: channel pitch %d / offset %d (Cin %d, 16-byte chunks)", who, cs, coff, Cin);
   if (!jspsr::aligned16(x)) return jspsr::fail(JSPSR_EALIGN, "%s: tensor not 16-byte aligned", who);
   return JSPSR_OK;
 }
