@@ -818,6 +818,37 @@ int jspsr_summary_valid_forward(const float* const* cands, const long long* cand
                                 void* workspace, jspsr_stream_t stream);
 int jspsr_summary_ranks(long long n, long long* out5);
 
+/* ---- K20 (ABI v25, additive): per-tile scores over valid pixels -- the masked form of K10 (csrc/scores.hip)
+ * A ground truth with voids (K19's stores) makes K10's per-tile scores useless: one -32767 in a 64 x 64 tile is an RMSE of
+ * about 500 m, the ranks are taken over the wrong n, and a void beside terrain is the largest Sobel edge of the tile.
+ *
+ * jspsr_scores_batch_valid_forward: jspsr_scores_batch_forward over the pixels a validity plane keeps.  Arguments as K10's, plus
+ *   valid   device uint8 [B][H][W], cropped by the same int(H * border) / int(W * border) as the rasters.  A pixel counts
+ *     iff its byte is non-zero.  pred and gt at a masked pixel have no influence whatever they hold (NaN, inf, -32767,
+ *     1e30): they are read behind a select only and never multiplied by the mask.
+ *   counts  device int32 [B][3] = {N, N_sl, N_sk}, exact: the valid pixels of the crop; the interior positions (1 <= y <
+ *     h - 1, 1 <= x < w - 1) whose nine taps are all valid; the positions whose nine replicate-clamped taps (clamped to the
+ *     crop) are all valid -- K19's rule for the Grad loss, so a void never makes an edge.
+ *   Columns 0, 1, 2: sums over the valid pixels, divisor N; PSNR "local" is 100 where the masked mse is 0 and N > 0.
+ *   Columns 3, 4, 5: exact selections over the valid differences, K10's ranks of N ((N - 1) / 2; llrint(0.95 (N - 1))) formed
+ *     on the device; the NMAD centre is the masked median.  Column 6: the N_sl counted positions, divisor N_sl.  Column 7:
+ *     the N_sk counted positions, divisor 2 N_sk.
+ *   A column whose count is 0 is NaN (all eight when N = 0; the slope columns when their own count is 0); not an error,
+ *     and no rank is formed from a zero count.
+ *   Departure from K10: none in the arithmetic.  The sums fold in K10's order with masked elements adding nothing in place,
+ *     and the path is chosen from the cropped size alone, so a call with an all-ones plane has exactly the bits of
+ *     jspsr_scores_batch_forward, all eight columns.  The mask travels inside the de-scaled prediction (a NaN there; a counted
+ *     pixel's is finite after the clamp), so the LDS path still holds 142 x 142.
+ *   One launch (LDS path) or 27 (streaming path) whatever B and the mask are (census labels scores_batch_valid (lds) /
+ *   scores_batch_valid (stream); K10's labels do not move).  Row b does not depend on B, on the other tiles or on their masks;
+ *   the same bits on every run.  No host synchronisation.
+ *   JSPSR_EINVAL: K10's cases, a null valid or counts.  workspace: jspsr_scores_batch_valid_workspace_bytes(B, H, W) bytes
+ *   (K10's plus 16 per streaming block; 0 = bad arguments), 16-byte aligned (JSPSR_EALIGN); counts 4-byte aligned. */
+size_t jspsr_scores_batch_valid_workspace_bytes(int B, int H, int W);
+int jspsr_scores_batch_valid_forward(const float* pred, const float* gt, const unsigned char* valid, int B, int H, int W,
+                                     float border, float value_min, float value_max, int elev_log, float* scores,
+                                     int* counts, void* workspace, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -91,6 +91,8 @@ SIGNATURES = {
     "jspsr_metrics_forward": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p]),
     "jspsr_scores_batch_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "jspsr_scores_batch_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p]),
+    "jspsr_scores_batch_valid_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "jspsr_scores_batch_valid_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p]),
     "jspsr_scenes_assemble_f32": (c_i, [c_p] * 5 + [c_ll] + [c_i] * 6 + [ctypes.c_double, ctypes.c_double, c_p]),
     "jspsr_summary_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_ll, c_ll]),
     "jspsr_summary_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_i, c_p, c_i, c_ll, c_ll, ctypes.c_double, c_p, c_p, c_p]),

@@ -60,10 +60,52 @@ def _ssim_torch(p, g, package):
     return (((2 * mx * my + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))).mean()
 
 
-def _scores_torch(pred, gt, vmin, vmax, border, elev_log):
-    """metrics.batch_scores as torch operators, for CPU tensors: (B,1,H,W) -> (B, 8) fp32."""
+def _masked_row(p, g, v, vmin, vmax, elev_log, sob):
+    """One tile of `_scores_torch(valid=)`: p, g the prepared (1,1,h,w) pair, v the cropped (1,1,h,w) bool plane ->
+    ((8,) fp32, [N, N_sl, N_sk]).  pred and gt are zeroed at the masked pixels first (they have no influence by
+    definition, and a NaN there would poison the convolutions' products); a counted Sobel output reads valid taps only."""
+    zero = torch.zeros_like(p)
+    p, g = torch.where(v, p, zero), torch.where(v, g, zero)
+    P, G = M.descale_data(p, vmin, vmax, elev_log), M.descale_data(g, vmin, vmax, elev_log)
+    P, G = torch.where(v, P, zero), torch.where(v, G, zero)
+    vf = v.float()
+    c_sl = -F.max_pool2d(-vf, 3, stride=1) == 1                                          # nine taps valid, interior positions
+    c_sk = -F.max_pool2d(-F.pad(vf, (1, 1, 1, 1), mode="replicate"), 3, stride=1) == 1   # nine clamped taps valid
+    n, n_sl, n_sk = int(v.sum()), int(c_sl.sum()), int(c_sk.sum())
+    nan = torch.tensor(float("nan"))
+    row = [nan] * 8
+    if n:
+        dh = (P - G)[v]
+        mse = ((p - g)[v] ** 2).mean()
+        row[0] = -10.0 * torch.log10(mse + 1e-8)
+        row[1] = 20.0 * torch.log10(1.0 / torch.sqrt(mse)) if mse.item() != 0 else torch.tensor(100.0)
+        row[2:6] = M.rmse(dh), M.median(dh), M.nmad(dh), M.le95(dh)
+    if n_sl:
+        slope = F.conv2d(P, sob).pow(2).sum(1, keepdim=True).sqrt() - F.conv2d(G, sob).pow(2).sum(1, keepdim=True).sqrt()
+        row[6] = (slope[c_sl].pow(2).sum() / n_sl).sqrt()
+    if n_sk:
+        grad = F.conv2d(F.pad(P - G, (1, 1, 1, 1), mode="replicate"), sob) / 16.0
+        row[7] = (grad.pow(2).sum(1, keepdim=True)[c_sk].sum() / (2 * n_sk)).sqrt()
+    return torch.stack([r.float().reshape(()) for r in row]), [n, n_sl, n_sk]
+
+
+def _scores_torch(pred, gt, vmin, vmax, border, elev_log, valid=None):
+    """metrics.batch_scores as torch operators, for CPU tensors: (B,1,H,W) -> (B, 8) fp32; with a (B,1,H,W) bool / uint8
+    plane `valid` -> ((B, 8) fp32, (B, 3) int32 counts), the rules of the masked kernel (K20)."""
     rows = []
     sob = _sobel_pair(torch.float32)
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.shape != pred.shape or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"_scores_torch: valid must be a {tuple(pred.shape)} bool / uint8 plane")
+        H, W = pred.shape[-2:]
+        bh, bw = int(H * border), int(W * border)
+        counts = []
+        for i in range(pred.shape[0]):
+            p, g = M.prepare(pred[i:i + 1].float(), gt[i:i + 1].float(), border)
+            row, cnt = _masked_row(p, g, valid[i:i + 1, :, bh:H - bh, bw:W - bw] != 0, vmin, vmax, elev_log, sob)
+            rows.append(row)
+            counts.append(cnt)
+        return torch.stack(rows), torch.tensor(counts, dtype=torch.int32).reshape(-1, 3)
     for i in range(pred.shape[0]):
         p, g = M.prepare(pred[i:i + 1].float(), gt[i:i + 1].float(), border)
         P, G = M.descale_data(p, vmin, vmax, elev_log), M.descale_data(g, vmin, vmax, elev_log)
@@ -90,9 +132,18 @@ class PerformanceMeter:
     update() writes the batch's rows into a device table and returns without a host synchronisation: GPU batches go
     through `metrics.batch_scores` (one launch for all scores of all tiles), CPU tensors through the same formulas as
     torch operators.  SSIM is not part of that kernel: `metrics.ssim` gives a batch mean, so it is called once per sample.
-    get_score() copies the table to the host once and averages in Python floats, as the reference adds `.item()` values."""
+    get_score() copies the table to the host once and averages in Python floats, as the reference adds `.item()` values.
 
-    def __init__(self, metric_config, value_min, value_max, border=0.05, elev_log=True):
+    masked=True (K20): update() accepts `valid`, a (B,1,H,W) bool / uint8 plane on pred's device; the tile's scores are
+    then taken over its valid pixels (`metrics.batch_scores(valid=)`; valid=None scores every pixel, with the full counts).
+    The meter keeps each tile's counts {N, N_sl, N_sk} (`metrics.COUNT_COLUMNS`) beside its row -- `counts()` -- and they
+    ride in the same single copy as the rows, bit for bit (int32 viewed as fp32, not converted).  A column whose count is 0
+    is NaN; get_score() averages each metric over the tiles whose count FOR THAT COLUMN is positive (as summary's online
+    means average the scenes with N > 0) and raises ValueError naming a metric no tile has; worst() skips NaN rows.
+    Masked SSIM is not built: an SSIM entry in a masked meter raises NotImplementedError here.  An unmasked meter refuses
+    `valid=`."""
+
+    def __init__(self, metric_config, value_min, value_max, border=0.05, elev_log=True, masked=False):
         self.config = {k: dict(v or {}) for k, v in dict(metric_config).items()}
         if not self.config:
             raise ValueError("PerformanceMeter: empty metric config")
@@ -106,27 +157,46 @@ class PerformanceMeter:
             for key, mine in (("border", self.border), ("min", self.vmin), ("max", self.vmax)):
                 if kw.get(key) is not None and float(kw[key]) != mine:
                     raise NotImplementedError(f"PerformanceMeter: metric {name!r} asks for {key} = {kw[key]}, the meter has {mine}")
+            if masked and isinstance(col, str):
+                raise NotImplementedError(f"PerformanceMeter: metric {name!r} in a masked meter: masked SSIM is not built")
             self.names.append(name)
             self.columns.append(col)
+        self.masked = bool(masked)
         self.reset()
 
     def clone(self):
         """A fresh meter with the same configuration (the reference builds a second one for the input's score)."""
-        return PerformanceMeter(self.config, self.vmin, self.vmax, self.border, self.elev_log)
+        return PerformanceMeter(self.config, self.vmin, self.vmax, self.border, self.elev_log, masked=self.masked)
 
     def reset(self):
         self._rows, self._meta, self._host = [], [], None
+        self._counts, self._host_counts = [], None
 
     def __len__(self):
         return len(self._meta)
 
     @torch.no_grad()
-    def update(self, pred, gt, meta=None):
+    def update(self, pred, gt, meta=None, valid=None):
         if pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 1:
             raise ValueError(f"PerformanceMeter.update: equal (B,1,H,W) tensors, got {tuple(pred.shape)} {tuple(gt.shape)}")
         B = pred.shape[0]
         if meta is not None and len(meta) != B:
             raise ValueError(f"PerformanceMeter.update: {len(meta)} meta entries for a batch of {B}")
+        if valid is not None and not self.masked:
+            raise ValueError("PerformanceMeter.update: valid= given to a meter that was not built with masked=True")
+        if self.masked:
+            if valid is None:
+                valid = torch.ones(pred.shape, dtype=torch.uint8, device=pred.device)
+            elif not torch.is_tensor(valid) or valid.shape != pred.shape or valid.dtype not in (torch.bool, torch.uint8) or \
+                    valid.device != pred.device:
+                raise ValueError(f"PerformanceMeter.update: valid must be a {tuple(pred.shape)} bool / uint8 plane on {pred.device}")
+            score = M.batch_scores if pred.is_cuda else _scores_torch
+            full, counts = score(pred, gt, self.vmin, self.vmax, self.border, self.elev_log, valid=valid)
+            self._rows.append(torch.stack([full[:, c] for c in self.columns], dim=1))
+            self._counts.append(counts)
+            self._meta.extend(meta if meta is not None else [None] * B)
+            self._host = self._host_counts = None
+            return
         if all(isinstance(c, str) for c in self.columns):
             full = None
         elif pred.is_cuda:
@@ -155,10 +225,32 @@ class PerformanceMeter:
             self._rows = [torch.cat(self._rows)]
         return self._rows[0]
 
+    def _device_counts(self):
+        """(N, 3) int32 on the device the rows were made on (masked meters); no host synchronisation."""
+        if not self._counts:
+            return torch.empty((0, 3), dtype=torch.int32)
+        if len(self._counts) > 1:
+            self._counts = [torch.cat(self._counts)]
+        return self._counts[0]
+
+    def _fetch_own(self):
+        if self._host is None or (self.masked and self._host_counts is None):
+            _fetch([self], None)
+
+    def counts(self):
+        """(N_tiles, 3) int32 numpy array, columns `metrics.COUNT_COLUMNS`, of a masked meter: the same single copy as the
+        table's."""
+        if not self.masked:
+            raise ValueError("PerformanceMeter.counts: the meter was not built with masked=True")
+        self._fetch_own()
+        return self._host_counts
+
     def table(self):
         """-> ((N, n_metrics) float32 numpy array in config order, the list of meta entries): ONE device-to-host copy,
         kept until the next update."""
-        if self._host is None:
+        if self.masked:
+            self._fetch_own()
+        elif self._host is None:
             self._host = self._device_table().cpu().numpy()
         return self._host, list(self._meta)
 
@@ -167,7 +259,15 @@ class PerformanceMeter:
         t, _ = self.table()
         if t.shape[0] == 0:
             raise ValueError("PerformanceMeter.get_score: no sample scored")
-        return {name: sum(float(v) for v in t[:, j]) / t.shape[0] for j, name in enumerate(self.names)}
+        if not self.masked:
+            return {name: sum(float(v) for v in t[:, j]) / t.shape[0] for j, name in enumerate(self.names)}
+        counts, out = self.counts(), {}
+        for j, name in enumerate(self.names):
+            keep = counts[:, M.COUNT_OF_COLUMN[self.columns[j]]] > 0
+            if not keep.any():
+                raise ValueError(f"PerformanceMeter.get_score: no tile has a valid pixel for metric {name!r}")
+            out[name] = sum(float(v) for v in t[keep, j]) / int(keep.sum())
+        return out
 
     def worst(self, name="RMSE", n=3):
         """MeterRMSE.get_score's "worst three" (metrics.py:404-420): the n largest values of metric `name` as
@@ -179,6 +279,9 @@ class PerformanceMeter:
             raise KeyError(f"PerformanceMeter.worst: {name!r} is not among {self.names}")
         vals = [float(v) for v in t[:, lower.index(str(name).lower())]]
         ids = [m["id"] if isinstance(m, dict) and "id" in m else i for i, m in enumerate(meta)]
+        if self.masked:                   # a tile without a valid pixel for this metric has no value to rank
+            keep = [v == v for v in vals]
+            vals, ids = [v for v, k in zip(vals, keep) if k], [i for i, k in zip(ids, keep) if k]
         out = []
         if len(vals) > 3:
             for _ in range(min(n, len(vals))):
@@ -193,7 +296,9 @@ def _fetch(meters, extra):
     """One device-to-host copy for everything a pass produced: the meters' tables (left in their caches) and `extra`
     (a 2-D device tensor or None) -> extra as a numpy array."""
     tabs = [m._device_table() for m in meters]
-    parts = [t.reshape(-1) for t in tabs] + ([extra.reshape(-1).float()] if extra is not None else [])
+    cnts = [m._device_counts() if m.masked else None for m in meters]          # int32 bits behind the rows: exact
+    parts = [t.reshape(-1) for t in tabs] + [c.reshape(-1).view(torch.float32) for c in cnts if c is not None] + \
+            ([extra.reshape(-1).float()] if extra is not None else [])
     dev = {p.device for p in parts if p.numel()}
     if len(dev) > 1:
         raise ValueError(f"evaluate: results on several devices {sorted(map(str, dev))}")
@@ -203,6 +308,10 @@ def _fetch(meters, extra):
     for m, t in zip(meters, tabs):
         m._host = flat[off:off + t.numel()].reshape(tuple(t.shape)).copy()
         off += t.numel()
+    for m, c in zip(meters, cnts):
+        if c is not None:
+            m._host_counts = flat[off:off + c.numel()].copy().view(np.int32).reshape(tuple(c.shape))
+            off += c.numel()
     return flat[off:].reshape(tuple(extra.shape)).copy() if extra is not None else None
 
 
@@ -242,10 +351,10 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
 
     Batches that carry "valid" (a store built with `hr_nodata` / `valid`, K19): the criterion is fed ONE SAMPLE AT A TIME
     with its slice of the plane, each sample weighing 1 as in the reference's batch of one -- a masked batch value is not
-    the mean of its samples' values, because their counts of valid pixels differ.  The per-tile meters (K10) are not masked:
-    a meter together with such a batch raises NotImplementedError before the forward.  Pass meter=None (the scores are then
-    None; compare_input is refused) and take the whole-set table from `collector=summary.ScenePredictions(...)` followed by
-    `summary.summarise(valid=...)`."""
+    the mean of its samples' values, because their counts of valid pixels differ.  A meter built with masked=True (K20) is
+    given the plane too, and so is the input's meter under compare_input: both are scored over the same pixels, each metric
+    averaged over the tiles that have a valid pixel for it, and `meter.counts()` holds every tile's counts.  A meter that
+    was not built with masked=True together with such a batch raises NotImplementedError before the forward."""
     model.eval()
     if meter is None and compare_input:
         raise ValueError("evaluate: compare_input needs a meter")
@@ -258,9 +367,9 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
         criterion.reset()
         inputs, gt, _base, meta = batch_pair(batch, model_name, input_data)
         valid = batch.get("valid")
-        if valid is not None and meter is not None:
-            raise NotImplementedError("evaluate: a batch with a validity plane and a meter: masked per-tile meters are not "
-                                      "built; pass meter=None and score with collector=ScenePredictions + summarise(valid=)")
+        if valid is not None and meter is not None and not getattr(meter, "masked", False):
+            raise NotImplementedError("evaluate: a batch with a validity plane needs a meter built with masked=True "
+                                      "(PerformanceMeter(..., masked=True)); this meter scores every pixel")
         pred = model(*inputs)
         if collector is not None:
             collector.add(pred, meta)
@@ -278,13 +387,19 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
             rows.append(torch.stack([out[k].detach().float().reshape(()) for k in keys]))
             weights.append(hi - lo)
         if meter is not None:
-            meter.update(pred, gt, meta=meta)
+            if valid is not None:
+                meter.update(pred, gt, meta=meta, valid=valid)
+            else:
+                meter.update(pred, gt, meta=meta)
         if compare_input:
             data_input = inputs[0][:, 0:1]
             if data_input.shape[-2:] != gt.shape[-2:]:
                 raise NotImplementedError(f"evaluate: the input DEM is {tuple(data_input.shape[-2:])}, the target "
                                           f"{tuple(gt.shape[-2:])}; the reference's bicubic resize is not built")
-            meter_in.update(data_input, gt, meta=meta)
+            if valid is not None:
+                meter_in.update(data_input, gt, meta=meta, valid=valid)
+            else:
+                meter_in.update(data_input, gt, meta=meta)
     if keys is None:
         raise ValueError("evaluate: no batches")
     vals = _fetch(([meter] if meter is not None else []) + ([meter_in] if compare_input else []),

@@ -104,7 +104,12 @@ def tile_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
 SCORE_COLUMNS = ("PSNR_piq", "PSNR_local", "RMSE", "Median", "NMAD", "LE95", "Slope_local", "Slope_kornia")
 
 
-def batch_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
+COUNT_COLUMNS = ("N", "N_slope_local", "N_slope_kornia")
+# SCORE_COLUMNS index -> COUNT_COLUMNS index: the count a masked column divides by (NaN where it is 0)
+COUNT_OF_COLUMN = (0, 0, 0, 0, 0, 0, 1, 2)
+
+
+def batch_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True, valid=None):
     """All scores of a whole batch (B,1,H,W) of GPU tiles in one C-ABI call (K10, jspsr_scores_batch_forward) -> (B, 8)
     fp32 device tensor, columns ``SCORE_COLUMNS``: PSNR as piq.psnr and as the reference's local psnr (metrics.py:97-113),
     RMSE / median / NMAD / LE95 exactly as ``tile_scores`` gives them (the same elevation differences, exact selections),
@@ -114,12 +119,36 @@ def batch_scores(pred, gt, value_min, value_max, border=0.05, elev_log=True):
     source and is NOT pinned against kornia itself (not installed here); the richdem form is not built.
     One launch per call for tiles of up to 142 x 142 after the crop (one workgroup per tile, both de-scaled rasters in LDS),
     27 launches whatever B is for larger ones.  Row b does not depend on B or on the other tiles.  No host
-    synchronisation."""
+    synchronisation.
+
+    valid: a (B,1,H,W) bool or uint8 plane on pred's device (nonzero = valid; K20, jspsr_scores_batch_valid_forward) ->
+    (scores, counts): the scores over the valid pixels of every tile, whatever pred and gt hold at the others, and the
+    (B, 3) int32 device tensor ``COUNT_COLUMNS`` -- the valid pixels of the crop, the interior positions whose nine taps
+    are valid (the divisor of Slope_local) and the positions whose nine replicate-clamped taps are valid (Slope_kornia).
+    The ranks of the order statistics are the unmasked formulas of N.  A column whose count is 0 is NaN.  An all-ones
+    plane gives the bits of the unmasked call; the launch counts are the same."""
     if not pred.is_cuda or pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 1:
         raise ValueError(f"batch_scores: equal (B,1,H,W) GPU tensors, got {tuple(pred.shape)} {tuple(gt.shape)}")
     B, _, H, W = pred.shape
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.shape != pred.shape or valid.dtype not in (torch.bool, torch.uint8) or \
+                valid.device != pred.device:
+            raise ValueError(f"batch_scores: valid must be a {tuple(pred.shape)} bool / uint8 plane on {pred.device}, got "
+                             f"{tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} "
+                             f"{getattr(valid, 'dtype', None)} on {getattr(valid, 'device', None)}")
     p, g = pred.float().contiguous(), gt.float().contiguous()
     lib = _lib.load()
+    if valid is not None:
+        v = valid.contiguous()
+        v = v.view(torch.uint8) if v.dtype == torch.bool else v          # a bool is one byte, 0 or 1
+        ws = torch.empty(max(lib.jspsr_scores_batch_valid_workspace_bytes(B, H, W), 16), dtype=torch.uint8, device=pred.device)
+        out = torch.empty((B, len(SCORE_COLUMNS)), dtype=torch.float32, device=pred.device)
+        counts = torch.empty((B, len(COUNT_COLUMNS)), dtype=torch.int32, device=pred.device)
+        _lib.check(lib.jspsr_scores_batch_valid_forward(p.data_ptr(), g.data_ptr(), v.data_ptr(), B, H, W, float(border), float(value_min),
+                                                        float(value_max), int(bool(elev_log)), out.data_ptr(), counts.data_ptr(),
+                                                        ws.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                   "jspsr_scores_batch_valid_forward")
+        return out, counts
     ws = torch.empty(max(lib.jspsr_scores_batch_workspace_bytes(B, H, W), 16), dtype=torch.uint8, device=pred.device)
     out = torch.empty((B, len(SCORE_COLUMNS)), dtype=torch.float32, device=pred.device)
     _lib.check(lib.jspsr_scores_batch_forward(p.data_ptr(), g.data_ptr(), B, H, W, float(border), float(value_min), float(value_max),

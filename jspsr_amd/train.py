@@ -285,7 +285,12 @@ def fit(p, model, train_batches, val_batches, criterion, optimizer, scheduler, r
 
     history[0] is the initial evaluation {"epoch": start_epoch, "scores", "val_loss", "input_scores"}; every later entry
     is one epoch {"epoch" (1-based), "train_loss", "lr", "terms", "ranges", "evaluated"} plus, where evaluated, "scores",
-    "val_loss", "is_better", "best", and "stopped" on the epoch the stopper ended the run."""
+    "val_loss", "is_better", "best", and "stopped" on the epoch the stopper ended the run.
+
+    A store whose ground truth has voids (`DeviceScenes(hr_nodata=)`, K19: its batches carry "valid") is fitted with a
+    meter built with `masked=True` (K20): the criterion and both meters then see the plane, the scores are over valid pixels
+    and `meter.counts()` holds the last evaluation's per-tile counts.  Any other meter raises NotImplementedError in the
+    initial evaluation."""
     epochs = int(_get(p, "epochs"))
     name, input_data = _get(p, "model_name"), _get(p, "input_data")
     start_epoch = 0
