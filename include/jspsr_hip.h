@@ -849,6 +849,60 @@ int jspsr_scores_batch_valid_forward(const float* pred, const float* gt, const u
                                      float border, float value_min, float value_max, int elev_log, float* scores,
                                      int* counts, void* workspace, jspsr_stream_t stream);
 
+/* ---- K21 (ABI v25, additive): the whole-set error distribution -- float16 histogram and Gaussian KDE (csrc/errdist.hip;
+ * DESIGN.md).  The numbers behind the reference's figure "Elevation Error Distribution in [-5, 5] m" (summarise_evaluation,
+ * utils/utils.py:1394-1456): per candidate the pooled errors with lo <= e <= hi, stored as float16, drawn by
+ * sns.kdeplot(bw_adjust=1, cut=0.5, common_norm=False).  What these entries replace is a device-to-host copy of every
+ * raster, boolean indexing and a KDE over 10^8 points on the host.  seaborn was not available to pin against: the curve is
+ * pinned to scipy.stats.gaussian_kde (scotts_factor, set_bandwidth(factor * bw_adjust)) and to the rules written here, which
+ * are seaborn 0.12's _define_support_grid with clip=None and numpy's linspace.
+ *
+ * jspsr_errdist_bins (HOST, no device is touched): *key0 = key(f16(float32(lo))), *K = key(f16(float32(hi))) - key0 + 1, with
+ *   f16 = round to nearest, ties to even, subnormals produced (np.float32(x).astype(np.float16), formed in integer arithmetic by
+ *   one __host__ __device__ function: the wave's FP16 denormal mode cannot matter) and key(bits) = bits ^ (bits & 0x8000 ?
+ *   0xffff : 0x8000), the order-preserving key.  Bin b holds the float16 of key key0 + b; -0 and +0 are two neighbouring
+ *   bins of value 0.  (-5, 5): K = 35 330.  JSPSR_EINVAL unless lo <= hi, both finite, both magnitudes <= 65504.
+ * jspsr_errdist_key (HOST twin of the kernel's classification): the bin of an error e, or -1 below the range, -2 above it,
+ *   -3 for a NaN; -4 for a bad range.  In range iff e >= float32(lo) && e <= float32(hi): NaN fails, -inf is below, +inf above.
+ *   With lo = +0 the element -0 is in range although its key is key0 - 1: it is counted in bin 0 (the same value, 0).
+ * jspsr_errdist_hist_forward: cands / cand_numel / gt / gt_numel / windows / n_windows / total as K12's; the windows'
+ *   segment word is NOT read, everything the call is given is one pool.  valid: K18's plane (device uint8 [valid_numel] in the
+ *   ground truth's layout, valid_numel == gt_numel) or NULL for "no mask".
+ *   Per pooled element and candidate: e = cand - gt in fp32, one rounded subtraction, as K12.  With a plane an element whose
+ *     byte is 0 is not scored and influences nothing whatever the rasters hold there (read behind a select).  A scored
+ *     element in range increments bin key(f16(e)) - key0.  Departure from K12's rows: a NaN or an infinity poisons nothing
+ *     here, it is counted and left out, as the reference's comparison leaves it out.  An element no window covers, or read
+ *     outside a buffer, is scored and is a NaN.
+ *   hist    device int64 [n_cand][K], exact.
+ *   counts  device int64 [n_cand][4] = { n_scored, n_in, n_below, n_above }; n_scored is equal for all candidates and
+ *     n_scored - n_in - n_below - n_above is the number of NaNs.
+ *   Two clears and ONE launch whatever the sizes, the candidates and the range are (census labels errdist_hist /
+ *   errdist_hist (valid)); a range of more bins than one LDS image of 36 864 holds is walked twice inside that launch.
+ *   Integer adds only: a candidate's histogram does not depend on the other candidates of the call, nor on the run.  No host
+ *   synchronisation, no workspace.  Departures from the arithmetic above: none intended.
+ *   JSPSR_EINVAL: a null pointer, n_cand outside 1..8, an empty table, a bad range, total >= 2^32, valid_numel != gt_numel;
+ *   JSPSR_EALIGN: rasters not 4-byte, hist / counts not 8-byte aligned.
+ * jspsr_errdist_kde_forward: the curves of n_cand histograms hist [n_cand][K] of bins key0 .. key0 + K - 1, all in fp64:
+ *   n = sum c_b, v_b the value of bin b; mean = sum c_b v_b / n; var = sum c_b (v_b - mean)^2 / (n - 1); bw = sqrt(var) *
+ *   n^(-1/5) * bw_adjust; with vmin, vmax the values of the lowest and highest occupied bins, support = linspace(vmin - cut bw,
+ *   vmax + cut bw, gridsize) by numpy's rule (start + i * step, two roundings; the last point is stop exactly); density_j = sum
+ *   c_b exp(-(g_j - v_b)^2 / (2 bw^2)) / (n bw sqrt(2 pi)).  Every sum is folded per thread over bins t, t + 256, ... and then by
+ *   a fixed tree: the bits depend on K and the counts alone.  n < 2 or var == 0: support and density are NaN (seaborn draws
+ *   nothing there); std and bw are NaN for n < 2, mean for n = 0.
+ *   support, density  device fp64 [n_cand][gridsize];  stats  device fp64 [n_cand][3] = { mean, std, bw }.
+ *   Two launches (census label errdist_kde), no host synchronisation.  JSPSR_EINVAL: a null pointer, n_cand outside 1..8, bins
+ *   that are not finite float16 values, gridsize outside 2..65535, cut < 0, bw_adjust <= 0.  workspace:
+ *   jspsr_errdist_workspace_bytes(n_cand, gridsize) bytes (0 = bad arguments), 16-byte aligned (JSPSR_EALIGN). */
+int jspsr_errdist_bins(double lo, double hi, int* key0, int* K);
+int jspsr_errdist_key(float e, double lo, double hi);
+size_t jspsr_errdist_workspace_bytes(int n_cand, int gridsize);
+int jspsr_errdist_hist_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                               long long gt_numel, const unsigned char* valid, long long valid_numel,
+                               const long long* windows, int n_windows, long long total, double lo, double hi,
+                               long long* hist, long long* counts, jspsr_stream_t stream);
+int jspsr_errdist_kde_forward(const long long* hist, int n_cand, int key0, int K, int gridsize, double cut, double bw_adjust,
+                              double* support, double* density, double* stats, void* workspace, jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -100,6 +100,12 @@ SIGNATURES = {
     "jspsr_summary_valid_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_ll, c_p, c_i, c_p, c_i, c_ll, c_ll, ctypes.c_double,
                                           c_p, c_p, c_p, c_p]),
     "jspsr_summary_ranks": (c_i, [c_ll, c_p]),
+    "jspsr_errdist_bins": (c_i, [ctypes.c_double, ctypes.c_double, c_p, c_p]),
+    "jspsr_errdist_key": (c_i, [c_f, ctypes.c_double, ctypes.c_double]),
+    "jspsr_errdist_workspace_bytes": (ctypes.c_size_t, [c_i, c_i]),
+    "jspsr_errdist_hist_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_ll, c_p, c_i, c_ll, ctypes.c_double, ctypes.c_double,
+                                         c_p, c_p, c_p]),
+    "jspsr_errdist_kde_forward": (c_i, [c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_adamw_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p]),
     "jspsr_adamw_step_dev": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_p, c_p]),
     "jspsr_optim_workspace_bytes": (ctypes.c_size_t, []),

@@ -13,8 +13,8 @@ both for the prediction and for every baseline DEM against the ground truth.
 
 The pooled numbers differ from the per-tile meters of `metrics.batch_scores` (K10) by definition: numpy's median is the
 mean of the two middle elements (torch.median: the lower one) and numpy's percentile interpolates (kthvalue: one element).
-Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K12.  GeoTIFF output, plotting and the
-richdem slope stay out; `upscale_dem` and whole-scene inference are in jspsr_amd/infer.py (K13), whose
+Arithmetic and its departures from numpy / the reference: include/jspsr_hip.h, K12.  GeoTIFF output, drawing and the
+richdem slope stay out (drawing stays out; the curves are `error_distribution`, K21); `upscale_dem` and whole-scene inference are in jspsr_amd/infer.py (K13), whose
 `predict_scenes(...).rasters()` gives the per-scene metre rasters `summarise` takes as `predictions`.
 
 Scores over valid pixels only (K18): `summarise(..., valid=valid_plane(scenes, nodata))`, `scores_pooled(..., valid=)` and
@@ -22,6 +22,11 @@ Scores over valid pixels only (K18): `summarise(..., valid=valid_plane(scenes, n
 statistic, whatever their values (the -32767 of a `predict_scenes(mask_voids=True)` result, a hole in the ground truth), and
 also return how many pixels were scored.  The count is data on the device, so the ranks are formed there: still one call of
 16 launches without a host synchronisation.
+
+The error distribution (K21, csrc/errdist.hip): `pooled_histogram` counts the pooled errors inside [lo, hi], rounded to
+float16 as the reference stores them, into one exact integer histogram per candidate (35 330 bins for [-5, 5]);
+`kde_curves` evaluates the Gaussian kernel density estimate of seaborn's kdeplot from it in fp64; `error_distribution`
+does both for the candidates `summarise` takes.  Only the curves leave the card.
 
 Device fp32 tensors go through the HIP kernels; host tensors through the same formulas as numpy / torch operators.
 """
@@ -84,6 +89,37 @@ def _nan_row() -> np.ndarray:
     return np.full(len(ROW), np.nan, dtype=np.float32)
 
 
+def _check_pool(what, cands, gt, windows, valid):
+    """The argument checks `pooled_rows` and `pooled_histogram` share: buffers, validity plane, every window inside its
+    buffers.  -> the number of pooled elements."""
+    n_cand = len(cands)
+    if not 1 <= n_cand <= MAX_CANDIDATES:
+        raise ValueError(f"{what}: {n_cand} candidates, 1..{MAX_CANDIDATES} are taken")
+    bufs = [gt] + list(cands)
+    if any(b.dtype != torch.float32 or b.dim() != 1 or not b.is_contiguous() for b in bufs):
+        raise ValueError(f"{what}: flat contiguous float32 buffers")
+    if len({b.device for b in bufs}) != 1:
+        raise ValueError(f"{what}: buffers on several devices")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or valid.dim() != 1 or not valid.is_contiguous():
+            raise ValueError(f"{what}: valid must be a flat contiguous uint8 tensor")
+        if valid.numel() != gt.numel():
+            raise ValueError(f"{what}: valid has {valid.numel()} elements, the ground truth {gt.numel()}")
+        if valid.device != gt.device:
+            raise ValueError(f"{what}: valid on {valid.device}, the ground truth on {gt.device}")
+    total = 0
+    for sg, h, w, g_, cs in windows:
+        if h <= 0 or w <= 0:
+            raise ValueError(f"{what}: an empty window ({h} x {w})")
+        if len(cs) != n_cand:
+            raise ValueError(f"{what}: a window names {len(cs)} candidates, {n_cand} were given")
+        for (off, pitch), b in zip([g_] + list(cs), bufs):
+            if off < 0 or pitch < 0 or off + (h - 1) * pitch + w > b.numel():
+                raise ValueError(f"{what}: window {h} x {w} at {off} (pitch {pitch}) leaves its buffer of {b.numel()}")
+        total += h * w
+    return total
+
+
 def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], n_segments: int, value_max: float,
                 valid: torch.Tensor | None = None):
     """The raw table call.  cands: 1..8 flat fp32 buffers, gt one, all on one device; windows: (segment, h, w, (gt offset,
@@ -95,20 +131,7 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
     synchronisation).  -> (rows, counts): rows as above, counts an int64 (n_segments,) tensor on the device, the elements
     scored per segment; a segment with none has a NaN row and count 0."""
     n_cand = len(cands)
-    if not 1 <= n_cand <= MAX_CANDIDATES:
-        raise ValueError(f"pooled_rows: {n_cand} candidates, 1..{MAX_CANDIDATES} are taken")
-    bufs = [gt] + list(cands)
-    if any(b.dtype != torch.float32 or b.dim() != 1 or not b.is_contiguous() for b in bufs):
-        raise ValueError("pooled_rows: flat contiguous float32 buffers")
-    if len({b.device for b in bufs}) != 1:
-        raise ValueError("pooled_rows: buffers on several devices")
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or valid.dim() != 1 or not valid.is_contiguous():
-            raise ValueError("pooled_rows: valid must be a flat contiguous uint8 tensor")
-        if valid.numel() != gt.numel():
-            raise ValueError(f"pooled_rows: valid has {valid.numel()} elements, the ground truth {gt.numel()}")
-        if valid.device != gt.device:
-            raise ValueError(f"pooled_rows: valid on {valid.device}, the ground truth on {gt.device}")
+    _check_pool("pooled_rows", cands, gt, windows, valid)
     if n_segments < 1 or not windows:
         raise ValueError("pooled_rows: no windows or no segments")
     order = sorted(range(len(windows)), key=lambda i: windows[i][0])          # stable: a segment keeps its window order
@@ -116,13 +139,6 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
     for sg, h, w, g_, cs in windows:
         if not 0 <= sg < n_segments:
             raise ValueError(f"pooled_rows: segment {sg} of {n_segments}")
-        if h <= 0 or w <= 0:
-            raise ValueError(f"pooled_rows: an empty window ({h} x {w})")
-        if len(cs) != n_cand:
-            raise ValueError(f"pooled_rows: a window names {len(cs)} candidates, {n_cand} were given")
-        for (off, pitch), b in zip([g_] + list(cs), bufs):
-            if off < 0 or pitch < 0 or off + (h - 1) * pitch + w > b.numel():
-                raise ValueError(f"pooled_rows: window {h} x {w} at {off} (pitch {pitch}) leaves its buffer of {b.numel()}")
         seg_n[sg] += h * w
     if min(seg_n) == 0:
         raise ValueError("pooled_rows: a segment without windows")
@@ -349,34 +365,34 @@ def compose_scene(tiles, base, full, border, elev_min, elev_max, elev_log):
     return T.merge_tiles(m, full, border)
 
 
-def store_layout(scenes, rasters, name="baseline"):
+def store_layout(scenes, rasters, name="baseline", what="summarise"):
     """A list of (h, w) metre rasters -> one flat fp32 buffer in the store's layout, uploaded once."""
     if len(rasters) != len(scenes):
-        raise ValueError(f"summarise: baseline {name!r} has {len(rasters)} rasters, the store {len(scenes)} scenes")
+        raise ValueError(f"{what}: baseline {name!r} has {len(rasters)} rasters, the store {len(scenes)} scenes")
     flat = []
     for i, r in enumerate(rasters):
         a = r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else np.asarray(r)
         a = a.reshape(a.shape[:2]) if a.ndim == 3 and a.shape[2] == 1 else a
         if tuple(a.shape) != tuple(scenes.shapes[i]):
-            raise ValueError(f"summarise: baseline {name!r}[{i}] is {a.shape}, the scene {scenes.shapes[i]}")
+            raise ValueError(f"{what}: baseline {name!r}[{i}] is {a.shape}, the scene {scenes.shapes[i]}")
         flat.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
     return torch.from_numpy(np.concatenate(flat)).to(scenes.device)
 
 
-def _valid_layout(scenes, valid, numel, device):
+def _valid_layout(scenes, valid, numel, device, what="summarise"):
     """`summarise`'s valid -> the flat uint8 plane in store layout on the store's device."""
     if isinstance(valid, torch.Tensor) and valid.dim() == 1:
         if valid.numel() != numel or valid.dtype != torch.uint8 or valid.device != device:
-            raise ValueError("summarise: a flat valid tensor must be uint8 with the store's layout and device")
+            raise ValueError(f"{what}: a flat valid tensor must be uint8 with the store's layout and device")
         return valid.contiguous()
     if len(valid) != len(scenes):
-        raise ValueError(f"summarise: valid has {len(valid)} planes, the store {len(scenes)} scenes")
+        raise ValueError(f"{what}: valid has {len(valid)} planes, the store {len(scenes)} scenes")
     flat = []
     for i, v in enumerate(valid):
         a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
         a = a.reshape(a.shape[:2]) if a.ndim == 3 and a.shape[2] == 1 else a
         if a.dtype not in (np.bool_, np.uint8) or tuple(a.shape) != tuple(scenes.shapes[i]):
-            raise ValueError(f"summarise: valid[{i}] is {a.dtype} {a.shape}, expected a bool or uint8 plane of {tuple(scenes.shapes[i])}")
+            raise ValueError(f"{what}: valid[{i}] is {a.dtype} {a.shape}, expected a bool or uint8 plane of {tuple(scenes.shapes[i])}")
         flat.append((a.reshape(-1) != 0).astype(np.uint8))
     return torch.from_numpy(np.concatenate(flat)).to(device)
 
@@ -400,6 +416,63 @@ def valid_plane(scenes, nodata, also=None) -> torch.Tensor:
     return keep.to(torch.uint8)
 
 
+def _assemble(what, scenes, predictions, baselines, border, patch_size, valid):
+    """What `summarise` and `error_distribution` score: the candidates' names and flat buffers ("SR" first), the ground
+    truth, one border-cropped window per scene in segment 0 and the validity plane in store layout (or None)."""
+    names = ["SR"] + list(baselines or {})
+    if len(names) > MAX_CANDIDATES:
+        raise ValueError(f"{what}: {len(names)} candidates, at most {MAX_CANDIDATES}")
+    if "SR" in (baselines or {}):
+        raise ValueError(f"{what}: 'SR' names the prediction")
+    S = len(scenes)
+    b = int(patch_size * border)
+    offs = [0]
+    for h, w in scenes.shapes:
+        offs.append(offs[-1] + h * w)
+    gt = scenes.store["hr_dem"]
+    if valid is not None:
+        valid = _valid_layout(scenes, valid, gt.numel(), gt.device, what)
+    if isinstance(predictions, ScenePredictions):
+        if predictions.scenes is not scenes or not predictions.complete:
+            raise ValueError(f"{what}: the collector must be complete and made on the same scenes")
+        sr, sr_off, sr_shape = predictions.buffer, predictions.offsets, [predictions.shape] * S
+    else:
+        if len(predictions) != S:
+            raise ValueError(f"{what}: {len(predictions)} predictions for {S} scenes")
+        arrs = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float32) for p in predictions]
+        sr_shape = [tuple(a.shape) for a in arrs]
+        sr_off = [0]
+        for a in arrs:
+            sr_off.append(sr_off[-1] + a.size)
+        sr = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs])).to(scenes.device)
+    cands = [sr]
+    for name, src in (baselines or {}).items():
+        if isinstance(src, str):
+            if src != "lr_dem":
+                raise ValueError(f"{what}: baseline {name!r}: {src!r} is not a raster of the store ('lr_dem')")
+            cands.append(scenes.store["lr_dem"])
+        elif isinstance(src, torch.Tensor) and src.dim() == 1:           # already in store layout, e.g. uploaded by an earlier call
+            if src.numel() != gt.numel() or src.dtype != torch.float32 or src.device != gt.device:
+                raise ValueError(f"{what}: baseline {name!r}: a flat tensor must have the store's layout, dtype and device")
+            cands.append(src.contiguous())
+        else:
+            cands.append(store_layout(scenes, src, name, what))
+    windows = []
+    for i, (h, w) in enumerate(scenes.shapes):
+        ch, cw = h - 2 * b, w - 2 * b
+        if ch <= 0 or cw <= 0:
+            raise ValueError(f"{what}: nothing left of scene {scenes.ids[i]} ({h} x {w}) after a crop of {b}")
+        at = (offs[i] + b * w + b, w)
+        if sr_shape[i] == (h, w):
+            sr_at = (sr_off[i] + b * w + b, w)
+        elif sr_shape[i] == (ch, cw):
+            sr_at = (sr_off[i], cw)
+        else:
+            raise ValueError(f"{what}: prediction {scenes.ids[i]} is {sr_shape[i]}, expected {(h, w)} or {(ch, cw)}")
+        windows.append((0, ch, cw, at, [sr_at] + [at] * (len(cands) - 1)))
+    return names, cands, gt, windows, valid
+
+
 def summarise(scenes, predictions, baselines=None, *, value_max: float, border: float = 0.0, patch_size: int, online: bool = False,
               valid=None):
     """summarise_evaluation (utils/utils.py:970-1368) on the device.
@@ -418,57 +491,8 @@ def summarise(scenes, predictions, baselines=None, *, value_max: float, border: 
     0).to(torch.uint8)` of a K17 store over the same scenes), cropped with the rasters.  One plane for all candidates: the
     rows of a table are scored over the same pixels.  Every row dict then gains "N", the number of pixels scored (a row
     without any is NaN); the means average the scenes with N > 0.  Still one call and one device-to-host copy."""
-    names = ["SR"] + list(baselines or {})
-    if len(names) > MAX_CANDIDATES:
-        raise ValueError(f"summarise: {len(names)} candidates, at most {MAX_CANDIDATES}")
-    if "SR" in (baselines or {}):
-        raise ValueError("summarise: 'SR' names the prediction")
+    names, cands, gt, windows, valid = _assemble("summarise", scenes, predictions, baselines, border, patch_size, valid)
     S = len(scenes)
-    b = int(patch_size * border)
-    offs = [0]
-    for h, w in scenes.shapes:
-        offs.append(offs[-1] + h * w)
-    gt = scenes.store["hr_dem"]
-    if valid is not None:
-        valid = _valid_layout(scenes, valid, gt.numel(), gt.device)
-    if isinstance(predictions, ScenePredictions):
-        if predictions.scenes is not scenes or not predictions.complete:
-            raise ValueError("summarise: the collector must be complete and made on the same scenes")
-        sr, sr_off, sr_shape = predictions.buffer, predictions.offsets, [predictions.shape] * S
-    else:
-        if len(predictions) != S:
-            raise ValueError(f"summarise: {len(predictions)} predictions for {S} scenes")
-        arrs = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float32) for p in predictions]
-        sr_shape = [tuple(a.shape) for a in arrs]
-        sr_off = [0]
-        for a in arrs:
-            sr_off.append(sr_off[-1] + a.size)
-        sr = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs])).to(scenes.device)
-    cands = [sr]
-    for name, src in (baselines or {}).items():
-        if isinstance(src, str):
-            if src != "lr_dem":
-                raise ValueError(f"summarise: baseline {name!r}: {src!r} is not a raster of the store ('lr_dem')")
-            cands.append(scenes.store["lr_dem"])
-        elif isinstance(src, torch.Tensor) and src.dim() == 1:           # already in store layout, e.g. uploaded by an earlier call
-            if src.numel() != gt.numel() or src.dtype != torch.float32 or src.device != gt.device:
-                raise ValueError(f"summarise: baseline {name!r}: a flat tensor must have the store's layout, dtype and device")
-            cands.append(src.contiguous())
-        else:
-            cands.append(store_layout(scenes, src, name))
-    windows = []
-    for i, (h, w) in enumerate(scenes.shapes):
-        ch, cw = h - 2 * b, w - 2 * b
-        if ch <= 0 or cw <= 0:
-            raise ValueError(f"summarise: nothing left of scene {scenes.ids[i]} ({h} x {w}) after a crop of {b}")
-        at = (offs[i] + b * w + b, w)
-        if sr_shape[i] == (h, w):
-            sr_at = (sr_off[i] + b * w + b, w)
-        elif sr_shape[i] == (ch, cw):
-            sr_at = (sr_off[i], cw)
-        else:
-            raise ValueError(f"summarise: prediction {scenes.ids[i]} is {sr_shape[i]}, expected {(h, w)} or {(ch, cw)}")
-        windows.append((0, ch, cw, at, [sr_at] + [at] * (len(cands) - 1)))
     if online:
         windows += [(1 + i,) + wdw[1:] for i, wdw in enumerate(windows)]
     n_seg = 1 + S if online else 1
@@ -500,3 +524,180 @@ def summarise(scenes, predictions, baselines=None, *, value_max: float, border: 
             scored = [v for v in per_scene[name].values() if v["N"] > 0]
             means[name] = {k: sum(v[k] for v in scored) / len(scored) if scored else float("nan") for k in COLUMNS}
     return pooled, means, per_scene
+
+
+# ---- K21: the error distribution -------------------------------------------------------------------------------------
+def _f16_key(bits):
+    """The order-preserving key of float16 bits (uint16 array or int): negative values reversed below the positive ones."""
+    bits = np.asarray(bits, dtype=np.int64)
+    return bits ^ np.where(bits & 0x8000, 0xffff, 0x8000)
+
+
+def histogram_bins(lo: float = -5.0, hi: float = 5.0):
+    """-> (key0, K): the key of float16(float32(lo)) and the number of float16 values from there to float16(float32(hi)),
+    both included.  (-5, 5): K = 35330.  ValueError unless lo <= hi, both finite, both magnitudes <= 65504."""
+    lo, hi = float(lo), float(hi)
+    if not (lo <= hi and abs(lo) <= 65504.0 and abs(hi) <= 65504.0):
+        raise ValueError(f"histogram_bins: lo = {lo}, hi = {hi} (lo <= hi, both finite, magnitudes <= 65504)")
+    k = _f16_key(np.array([lo, hi], dtype=np.float32).astype(np.float16).view(np.uint16))
+    return int(k[0]), int(k[1] - k[0] + 1)
+
+
+def histogram_values(key0: int, K: int, device=None) -> torch.Tensor:
+    """-> (K,) float64: the float16 value of every bin of a `pooled_histogram` (-0 and +0 are two bins of value 0)."""
+    if K < 1 or key0 < 0x0400 or key0 + K - 1 > 0xfbff:
+        raise ValueError(f"histogram_values: key0 = {key0}, K = {K} are not bins of finite float16 values")
+    k = np.arange(key0, key0 + K, dtype=np.int64)
+    bits = np.where(k & 0x8000, k ^ 0x8000, k ^ 0xffff).astype(np.uint16)
+    return torch.from_numpy(bits.view(np.float16).astype(np.float64)).to(device or "cpu")
+
+
+def pooled_histogram(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], lo: float = -5.0, hi: float = 5.0,
+                     valid: torch.Tensor | None = None):
+    """The float16 histogram of the pooled errors (K21).  cands, gt, windows, valid: as `pooled_rows` takes them; the
+    windows' segment entry is not read -- everything a call is given is one pool.  Per pooled element and candidate e =
+    cand - gt in fp32; with `valid`, an element whose byte is 0 is not scored, whatever the rasters hold there.  A scored
+    element with float32(lo) <= e <= float32(hi) is rounded to float16 (nearest, ties to even, subnormals kept: numpy's
+    astype) and counted in bin key(e) - key0; NaN and infinities fail the comparison and poison nothing (unlike K12's rows).
+    -> (hist (n_cand, K) int64, counts (n_cand, 4) int64 = {n_scored, n_in, n_below, n_above}, key0) on the buffers' device;
+    n_scored - n_in - n_below - n_above is the number of NaNs.  `histogram_values(key0, K)` gives the bins' values.  Exact
+    and order-free: the same bits on every run, whatever candidates share the call.  Device: one launch, no host
+    synchronisation."""
+    n_cand = len(cands)
+    total = _check_pool("pooled_histogram", cands, gt, windows, valid)
+    if not windows:
+        raise ValueError("pooled_histogram: no windows")
+    key0, K = histogram_bins(lo, hi)
+    if total >= 2 ** 32:
+        raise ValueError(f"pooled_histogram: {total} pooled elements, the bin counters hold fewer than 2^32")
+    if gt.is_cuda:
+        tab = np.zeros((len(windows), _WIN_WORDS), dtype=np.int64)
+        e_off = 0
+        for i, (_, h, w, (go, gp), cs) in enumerate(windows):
+            tab[i, :6] = (0, h, w, e_off, go, gp)
+            for c, (co, cp) in enumerate(cs):
+                tab[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
+            e_off += h * w
+        dev = gt.device
+        host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)     # one stream-ordered upload, never written again
+        host.numpy()[...] = tab
+        table = host.to(dev, non_blocking=True)
+        hist = torch.empty((n_cand, K), dtype=torch.int64, device=dev)
+        counts = torch.empty((n_cand, 4), dtype=torch.int64, device=dev)
+        ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
+        numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+        _lib.check(_lib.load().jspsr_errdist_hist_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(),
+                                                          valid.data_ptr() if valid is not None else None,
+                                                          valid.numel() if valid is not None else 0, table.data_ptr(), len(windows),
+                                                          total, float(lo), float(hi), hist.data_ptr(), counts.data_ptr(),
+                                                          torch.cuda.current_stream(dev).cuda_stream),
+                   "jspsr_errdist_hist_forward")
+        return hist, counts, key0
+    g_np = gt.numpy()
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    keep = None
+    if valid is not None:
+        v_np = valid.numpy()
+        keep = np.concatenate([v_np[go + np.arange(h)[:, None] * gp + np.arange(w)[None, :]].reshape(-1) != 0
+                               for _, h, w, (go, gp), _ in windows])
+    hist = np.zeros((n_cand, K), dtype=np.int64)
+    counts = np.zeros((n_cand, 4), dtype=np.int64)
+    for c, cand in enumerate(cands):
+        c_np = cand.numpy()
+        parts = []
+        for _, h, w, (go, gp), cs in windows:
+            co, cp = cs[c]
+            rows, cols = np.arange(h)[:, None], np.arange(w)[None, :]
+            with np.errstate(invalid="ignore"):                 # inf - inf under a mask
+                parts.append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
+        e = np.concatenate(parts).astype(np.float32, copy=False)
+        if keep is not None:
+            e = e[keep]
+        inside = (e >= lo32) & (e <= hi32)
+        b = _f16_key(e[inside].astype(np.float16).view(np.uint16)) - key0
+        hist[c] = np.bincount(np.clip(b, 0, K - 1), minlength=K)              # lo = +0 keeps -0: counted with +0
+        counts[c] = (e.size, int(inside.sum()), int((e < lo32).sum()), int((e > hi32).sum()))
+    return torch.from_numpy(hist), torch.from_numpy(counts), key0
+
+
+def _kde_host(h: np.ndarray, v: np.ndarray, gridsize: int, cut: float, bw_adjust: float):
+    """One candidate's curve from its counts h and the bins' values v, the formulas of include/jspsr_hip.h (K21) as numpy."""
+    nan = np.full(gridsize, np.nan)
+    occ = np.nonzero(h)[0]
+    n = int(h.sum())
+    if n < 1:
+        return nan, nan, (np.nan, np.nan, np.nan)
+    c, x = h[occ].astype(np.float64), v[occ]
+    mean = float(np.sum(c * x) / n)
+    if n < 2:
+        return nan, nan, (mean, np.nan, np.nan)
+    var = float(np.sum(c * (x - mean) ** 2) / (n - 1))
+    sd = math.sqrt(var)
+    bw = sd * float(n) ** -0.2 * bw_adjust
+    if not var > 0.0:
+        return nan, nan, (mean, sd, bw)
+    support = np.linspace(x[0] - cut * bw, x[-1] + cut * bw, gridsize)
+    dens = np.array([np.sum(c * np.exp(-(g - x) ** 2 / (2.0 * (bw * bw)))) for g in support]) / (n * bw * math.sqrt(2.0 * math.pi))
+    return support, dens, (mean, sd, bw)
+
+
+def kde_curves(hist: torch.Tensor, key0: int, gridsize: int = 200, cut: float = 0.5, bw_adjust: float = 1.0):
+    """The Gaussian kernel density estimates seaborn's `kdeplot(bw_adjust=, cut=, gridsize=, common_norm=False)` draws, from
+    `pooled_histogram`'s counts, all in fp64 (K21).  hist: (n_cand, K) or (K,) int64.  Per candidate, with c_b the counts and
+    v_b the bins' values: n = sum c_b; mean = sum c_b v_b / n; var = sum c_b (v_b - mean)^2 / (n - 1); bw = sqrt(var) *
+    n^(-1/5) * bw_adjust (scipy's gaussian_kde with scotts_factor and set_bandwidth(factor * bw_adjust), what seaborn 0.12+
+    does); support = linspace(vmin - cut bw, vmax + cut bw, gridsize) over the occupied bins (seaborn's
+    _define_support_grid with clip=None); density_j = sum c_b exp(-(g_j - v_b)^2 / (2 bw^2)) / (n bw sqrt(2 pi)).
+    seaborn is not a dependency and was not available to pin against: the curve is pinned to scipy.stats.gaussian_kde and to
+    the rule above (tests/errdist_ref.py), not to seaborn itself.
+    -> (support (n_cand, gridsize), density (n_cand, gridsize), stats (n_cand, 3) = {mean, std, bw}), fp64 tensors on the
+    histogram's device ((gridsize,), (gridsize,), (3,) for a (K,) histogram).  n < 2 or var == 0: support and density are NaN
+    (seaborn draws nothing there).  Device: two launches, no host synchronisation; the same bits on every run."""
+    if not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or hist.dim() not in (1, 2):
+        raise ValueError("kde_curves: an int64 (n_cand, K) or (K,) histogram")
+    one = hist.dim() == 1
+    h2 = (hist[None] if one else hist).contiguous()
+    n_cand, K = h2.shape
+    if not 1 <= n_cand <= MAX_CANDIDATES:
+        raise ValueError(f"kde_curves: {n_cand} candidates, 1..{MAX_CANDIDATES} are taken")
+    if K < 1 or key0 < 0x0400 or key0 + K - 1 > 0xfbff:
+        raise ValueError(f"kde_curves: key0 = {key0}, K = {K} are not bins of finite float16 values")
+    gridsize, cut, bw_adjust = int(gridsize), float(cut), float(bw_adjust)
+    if not (2 <= gridsize <= 65535 and 0.0 <= cut < math.inf and 0.0 < bw_adjust < math.inf):
+        raise ValueError(f"kde_curves: gridsize = {gridsize}, cut = {cut}, bw_adjust = {bw_adjust} (gridsize >= 2, cut >= 0, bw_adjust > 0)")
+    if h2.is_cuda:
+        dev = h2.device
+        lib = _lib.load()
+        support = torch.empty((n_cand, gridsize), dtype=torch.float64, device=dev)
+        density = torch.empty((n_cand, gridsize), dtype=torch.float64, device=dev)
+        stats = torch.empty((n_cand, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(lib.jspsr_errdist_workspace_bytes(n_cand, gridsize), dtype=torch.uint8, device=dev)
+        _lib.check(lib.jspsr_errdist_kde_forward(h2.data_ptr(), n_cand, key0, K, gridsize, cut, bw_adjust, support.data_ptr(),
+                                                 density.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "jspsr_errdist_kde_forward")
+    else:
+        v = histogram_values(key0, K).numpy()
+        got = [_kde_host(h, v, gridsize, cut, bw_adjust) for h in h2.numpy()]
+        support, density, stats = (torch.from_numpy(np.array([g[i] for g in got], dtype=np.float64)) for i in range(3))
+    return (support[0], density[0], stats[0]) if one else (support, density, stats)
+
+
+def error_distribution(scenes, predictions, baselines=None, *, border: float = 0.0, patch_size: int, valid=None, lo: float = -5.0,
+                       hi: float = 5.0, gridsize: int = 200, cut: float = 0.5, bw_adjust: float = 1.0):
+    """The curves of the reference's figure "Elevation Error Distribution in [-5, 5] m" (summarise_evaluation,
+    utils/utils.py:1394-1456) on the device: per candidate all pooled errors with lo <= e <= hi, as float16, under
+    `sns.kdeplot(bw_adjust=1, cut=0.5, common_norm=False)`.  Drawing stays out.
+    scenes, predictions, baselines, border, patch_size, valid: as `summarise` takes them, with the same crops.
+    -> {name: {"support", "density" (numpy float64, (gridsize,)), "n" (pixels scored), "n_in", "n_below", "n_above", "mean",
+    "std", "bw"}} for "SR" and each baseline.  `pooled_histogram` and `kde_curves` (whose docstrings state the arithmetic
+    and what it is pinned to), then one device-to-host copy; no other synchronisation."""
+    names, cands, gt, windows, valid = _assemble("error_distribution", scenes, predictions, baselines, border, patch_size, valid)
+    hist, counts, key0 = pooled_histogram(cands, gt, windows, lo, hi, valid=valid)
+    support, density, stats = kde_curves(hist, key0, gridsize, cut, bw_adjust)
+    n_c, G = len(names), support.shape[1]
+    both = torch.cat((support.reshape(-1), density.reshape(-1), stats.reshape(-1), counts.double().reshape(-1))).cpu().numpy()   # the one copy
+    sup, den = both[:n_c * G].reshape(n_c, G), both[n_c * G:2 * n_c * G].reshape(n_c, G)
+    st, cnt = both[2 * n_c * G:2 * n_c * G + 3 * n_c].reshape(n_c, 3), both[2 * n_c * G + 3 * n_c:].reshape(n_c, 4)   # counts: exact below 2^53
+    return {name: {"support": sup[c].copy(), "density": den[c].copy(), "n": int(cnt[c, 0]), "n_in": int(cnt[c, 1]),
+                   "n_below": int(cnt[c, 2]), "n_above": int(cnt[c, 3]), "mean": float(st[c, 0]), "std": float(st[c, 1]),
+                   "bw": float(st[c, 2])} for c, name in enumerate(names)}
