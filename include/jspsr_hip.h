@@ -374,6 +374,8 @@ int jspsr_conv2d_wgrad_scaled(int dtype, const void* G, int Cg, int g_cstride, i
  *   jspsr_gate_pool             sum | max | index, [rows][C] each
  *   jspsr_gate_backward_reduce  partial rows [rows][C]
  * -> max(3 rows + 4, 2 + 2 * 256) * C floats (+ 64 bytes).
+ *   jspsr_bn_backward_pair      coef [6][C], then partial rows [chunks][3][C] = (3 rows + 6) C: two C MORE than the above
+ *                               at the full chunk count -> its own query, jspsr_bn_backward_pair_workspace_bytes
  */
 size_t jspsr_reduce_workspace_bytes(int dtype, int C, int nseg);
 
@@ -422,6 +424,26 @@ int jspsr_bn_backward(int dtype, const void* dy, int dy_cs, int dy_coff, const v
                       const float* save_invstd, int training, int relu, float res_scale, void* dx, void* dres,
                       float* dgamma, float* dbeta, int accumulate, long long npix, int C, void* workspace,
                       const float* ext_partial, int ext_rows, const void* mask, jspsr_stream_t stream);
+
+/* (ABI v25, additive) The backward of a projecting BasicBlock's two BatchNorms in one reduce and one apply pass: the block's
+ * second BatchNorm (input x2; residual + ReLU, `mask` = the bit mask jspsr_bn_forward wrote; sees dz * res_scale) and the
+ * shortcut's BatchNorm (input xd = the raw 1x1 output; no ReLU, no scale) receive the same gradient dz = dy where the ReLU
+ * was open.  Equivalent, bit for bit, to
+ *   jspsr_bn_backward(dy, x2, relu = 1, mask, res_scale, dx = dx2, dres)  then  jspsr_bn_backward(dres, xd, relu = 0, 1.0, dx = dxd)
+ * without dres: 8.12 tensor passes instead of 11.06, 3 launches instead of 6 (census labels bn_bwd_reduce_pair,
+ * bn_bwd_finalize_pair, bn_bwd_apply_pair).  dy, x2, xd: channel slices (pitch, offset); dx2, dxd: dense, pitch C, distinct.
+ * training / accumulate / the parameter-gradient buffers are per layer, with jspsr_bn_backward's meaning.
+ * JSPSR_EINVAL: a null pointer (mask included: the mask-from-y and ReLU-free forms stay with the two calls), npix <= 0, C,
+ * a pitch or an offset that is no multiple of the vector width, a slice that does not fit its pitch, shared outputs;
+ * JSPSR_EALIGN: a tensor or the workspace not 16-byte aligned; all decided before any launch.
+ * workspace: jspsr_bn_backward_pair_workspace_bytes(dtype, C) bytes (0 = bad arguments). */
+size_t jspsr_bn_backward_pair_workspace_bytes(int dtype, int C);
+int jspsr_bn_backward_pair(int dtype, const void* dy, int dy_cs, int dy_coff, const void* mask, const void* x2, int x2_cs,
+                           int x2_coff, const float* gamma2, const float* save_mean2, const float* save_invstd2,
+                           int training2, float res_scale, const void* xd, int xd_cs, int xd_coff, const float* gammad,
+                           const float* save_meand, const float* save_invstdd, int trainingd, void* dx2, void* dxd,
+                           float* dgamma2, float* dbeta2, int accumulate2, float* dgammad, float* dbetad, int accumulated,
+                           long long npix, int C, void* workspace, jspsr_stream_t stream);
 
 /* Backward of the conv epilogue `y = [relu](conv + bias)` of the BN-free Basic2d (basics.py:36-53):
  * dz = dy * [y > 0] (y read with channel pitch y_cs; dz written with pitch dz_cs if dz != NULL),

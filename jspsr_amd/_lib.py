@@ -68,6 +68,9 @@ SIGNATURES = {
     "jspsr_bn_reduce_params": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "jspsr_bn_backward": (c_i, [c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f,
                                 c_p, c_p, c_p, c_p, c_i, c_ll, c_i, c_p, c_p, c_i, c_p, c_p]),
+    "jspsr_bn_backward_pair_workspace_bytes": (ctypes.c_size_t, [c_i, c_i]),
+    "jspsr_bn_backward_pair": (c_i, [c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_i, c_i, c_p, c_p, c_p, c_i,
+                                     c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_ll, c_i, c_p, c_p]),
     "jspsr_act_backward": (c_i, [c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_p, c_ll, c_i, c_p, c_p]),
     "jspsr_gate_pool": (c_i, [c_i, c_p, c_i, c_ll, c_i, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_gate_scale": (c_i, [c_i, c_p, c_p, c_p, c_i, c_ll, c_i, c_p]),

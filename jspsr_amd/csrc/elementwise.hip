@@ -137,7 +137,8 @@ dim3 red_grid(const RedGeom& g, int vec) { return dim3(g.nseg * g.chunks, (g.C /
 // of one pixel, `use(pix, c, raw[, acc])` consumes them; a trip issues the loads of four pixels back to back and only then
 // works through them, in pixel order (so sums keep their order and their bits).  One pixel per trip left 2-3 x 16 bytes
 // per lane in flight -- about 32 KB per CU at 16 waves, under half of what hides an HBM miss; the BatchNorm backward
-// pair ran at 4.5 TB/s effective where a plain stream reaches 5.5 (tools/bench_bn.py).
+// pair ran at 4.5 TB/s effective where a plain stream reaches 5.5 (tools/bench_bn.py).  for_pixels_mlp takes the count as
+// FLY for a kernel whose registers want fewer (bn_bwd_apply_pair_kernel); pixels are consumed in order whatever it is.
 #ifndef K4_PIX_FLY
 #define K4_PIX_FLY 4      // (lab builds: -DK4_PIX_FLY=2|8)
 #endif
@@ -192,7 +193,7 @@ __device__ __forceinline__ void reduce_pixels_mlp(const RedGeom& g, float* __res
       }
   }
 }
-template <typename T, int NTEN, typename L, typename F>
+template <typename T, int NTEN, int FLY = PIX_FLY, typename L, typename F>
 __device__ __forceinline__ void for_pixels_mlp(const RedGeom& g, L&& load, F&& use) {
   constexpr int N = V<T>::N;
   const LaneMap lm = lane_map<N>(g);
@@ -203,12 +204,12 @@ __device__ __forceinline__ void for_pixels_mlp(const RedGeom& g, L&& load, F&& u
   const long long p1 = (p0 + g.chunk_pix < g.npix) ? p0 + g.chunk_pix : g.npix;
   const long long step = TY * g.pl, base = (long long)seg * g.npix;
   long long p = p0 + threadIdx.y * g.pl + lm.sub;
-  for (; p + (PIX_FLY - 1) * step < p1; p += PIX_FLY * step) {
-    uint4 raw[PIX_FLY][NTEN];
+  for (; p + (FLY - 1) * step < p1; p += FLY * step) {
+    uint4 raw[FLY][NTEN];
 #pragma unroll
-    for (int u = 0; u < PIX_FLY; ++u) load(base + p + u * step, c, raw[u]);
+    for (int u = 0; u < FLY; ++u) load(base + p + u * step, c, raw[u]);
 #pragma unroll
-    for (int u = 0; u < PIX_FLY; ++u) use(p + u * step, base + p + u * step, c, raw[u]);
+    for (int u = 0; u < FLY; ++u) use(p + u * step, base + p + u * step, c, raw[u]);
   }
   for (; p < p1; p += step) {
     uint4 raw[NTEN];
@@ -517,6 +518,137 @@ __global__ __launch_bounds__(TX * TY) void bn_bwd_apply_kernel(const T* __restri
         }
         store_vec<T>(dx + (size_t)pix * C + c, o);
         if (dres) store_vec<T>(dres + (size_t)pix * C + c, d);
+      });
+}
+
+// ---------------------------------------------------------------- BatchNorm backward, projection blocks: two layers, one walk
+// The block's second BatchNorm (input x2, residual + ReLU, bit mask) and its shortcut's BatchNorm (input xd, no ReLU) take
+// the same gradient dz = dy where the ReLU was open: one reduce pass and one apply pass serve both, and dz is never
+// stored.  Per lane the pixel order, the expressions and the LDS fold are those of bn_bwd_reduce_kernel<T, 3, true> /
+// <T, 0, false> and bn_bwd_apply_kernel<T, 0>, so every sum and every output has the bits of the two separate calls
+// (the shortcut layer summed the very floats keep_bits produced: sum dz is shared).  Partial rows [chunk][3][C] =
+// sum dz | sum dz xhat2 | sum dz xhatd.
+template <typename T>
+__global__ __launch_bounds__(TX * TY) void bn_bwd_reduce_pair_kernel(const T* __restrict__ dy, int dy_cs, int dy_coff,
+                                                                    const unsigned char* __restrict__ mask,
+                                                                    const T* __restrict__ x2, int x2_cs, int x2_coff,
+                                                                    const float* __restrict__ mean2, const float* __restrict__ invstd2,
+                                                                    const T* __restrict__ xd, int xd_cs, int xd_coff,
+                                                                    const float* __restrict__ meand, const float* __restrict__ invstdd,
+                                                                    RedGeom g, float* __restrict__ partial) {
+  constexpr int N = V<T>::N;
+  const int groups = g.C / N;
+  float mu2[N], is2[N], mud[N], isd[N];
+  const int c0 = lane_map<N>(g).c;
+  if (c0 < g.C) {
+    load_param<N>(mean2 + c0, mu2); load_param<N>(invstd2 + c0, is2);
+    load_param<N>(meand + c0, mud); load_param<N>(invstdd + c0, isd);
+  }
+  reduce_pixels_mlp<T, 3, 4>(
+      g, partial,
+      [&](long long pix, int c, uint4 (&raw)[4]) {
+        raw[0] = load_raw<T>(dy + (size_t)pix * dy_cs + dy_coff + c);
+        raw[1] = load_raw<T>(x2 + (size_t)pix * x2_cs + x2_coff + c);
+        raw[2] = load_raw<T>(xd + (size_t)pix * xd_cs + xd_coff + c);
+        raw[3].x = mask[(size_t)pix * groups + c / N];
+      },
+      [&](long long, int, const uint4 (&raw)[4], float (&acc)[3][N]) {
+        float d[N], xv[N], xw[N];
+        const unsigned m = raw[3].x;
+        unpack<T>(raw[0], d);
+        unpack<T>(raw[1], xv);
+        unpack<T>(raw[2], xw);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const float xhat = (xv[i] - mu2[i]) * is2[i];
+          const float xhatd = (xw[i] - mud[i]) * isd[i];
+          const float dz = !((m >> i) & 1u) ? 0.f : d[i];
+          acc[0][i] += dz;
+          acc[1][i] += dz * xhat;
+          acc[2][i] += dz * xhatd;
+        }
+      });
+}
+
+// both layers' dbeta / dgamma and coefficient triples (coef [6][C]: k | a | b of the block's BatchNorm, then of the
+// shortcut's); the columns are summed as bn_bwd_finalize_kernel sums them.  The shortcut layer sees no res_scale.
+__global__ void bn_bwd_finalize_pair_kernel(const float* __restrict__ partial, int rows, int C, long long count,
+                                            const float* __restrict__ gamma2, const float* __restrict__ invstd2, int training2,
+                                            float res_scale, int accumulate2, float* __restrict__ dgamma2, float* __restrict__ dbeta2,
+                                            const float* __restrict__ gammad, const float* __restrict__ invstdd, int trainingd,
+                                            int accumulated, float* __restrict__ dgammad, float* __restrict__ dbetad,
+                                            float* __restrict__ coef) {
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // one wave per channel
+  if (c >= C) return;
+  double s, sx;
+  wave_sum_rows2(partial, rows, (size_t)3 * C, c, (size_t)C + c, s, sx);
+  const double sd = wave_sum_rows(partial, rows, (size_t)3 * C, (size_t)2 * C + c);
+  if ((threadIdx.x & 63) != 0) return;
+  auto layer = [&](double sxl, const float* gamma, const float* invstd, int training, float rs, int accumulate,
+                   float* dgamma, float* dbeta, float* co) {
+    dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)(s * rs);
+    dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)(sxl * rs);
+    const float k = gamma[c] * invstd[c] * rs;
+    co[c] = k;
+    co[C + c] = training ? (float)(s / (double)count) : 0.f;
+    co[2 * C + c] = training ? (float)(sxl / (double)count) : 0.f;
+  };
+  layer(sx, gamma2, invstd2, training2, res_scale, accumulate2, dgamma2, dbeta2, coef);
+  layer(sd, gammad, invstdd, trainingd, 1.0f, accumulated, dgammad, dbetad, coef + 3 * C);
+}
+
+// The pair apply pass keeps ten per-channel parameter vectors in registers (80 VGPRs in bf16): with four pixels in flight it
+// needs 163 VGPRs -- three waves per SIMD -- and ran at 3.7-4.0 TB/s; with ONE (loads issued first and consumed in pixel
+// order either way: the same bits) 123 VGPRs, four waves, 4.7-5.0 TB/s over the whole call (8 x 512^2 x 64 bf16: 436 us
+// against 543-568; 2 and 3 in flight: 141 / 151 VGPRs, three waves, no better than four).  The pair reduce pass stays at
+// four: 243 VGPRs and two waves, yet 1, 2 and 3 in flight (113 / 158 / 153 VGPRs) measured the same or slower.
+#ifndef K4_PAIR_APPLY_FLY
+#define K4_PAIR_APPLY_FLY 1      // (lab builds: -DK4_PAIR_APPLY_FLY=2|3|4)
+#endif
+constexpr int PAIR_APPLY_FLY = K4_PAIR_APPLY_FLY;
+template <typename T>
+__global__ __launch_bounds__(TX * TY) void bn_bwd_apply_pair_kernel(const T* __restrict__ dy, int dy_cs, int dy_coff,
+                                                                   const unsigned char* __restrict__ mask,
+                                                                   const T* __restrict__ x2, int x2_cs, int x2_coff,
+                                                                   const float* __restrict__ mean2, const float* __restrict__ invstd2,
+                                                                   const T* __restrict__ xd, int xd_cs, int xd_coff,
+                                                                   const float* __restrict__ meand, const float* __restrict__ invstdd,
+                                                                   const float* __restrict__ coef, T* __restrict__ dx2,
+                                                                   T* __restrict__ dxd, RedGeom g) {
+  constexpr int N = V<T>::N;
+  const int C = g.C, groups = C / N;
+  float mu2[N], is2[N], k2[N], a2[N], b2[N], mud[N], isd[N], kd[N], ad[N], bd[N];
+  const int c0 = lane_map<N>(g).c;
+  if (c0 < C) {
+    load_param<N>(mean2 + c0, mu2); load_param<N>(invstd2 + c0, is2);
+    load_param<N>(coef + c0, k2); load_param<N>(coef + C + c0, a2); load_param<N>(coef + 2 * C + c0, b2);
+    load_param<N>(meand + c0, mud); load_param<N>(invstdd + c0, isd);
+    load_param<N>(coef + 3 * C + c0, kd); load_param<N>(coef + 4 * C + c0, ad); load_param<N>(coef + 5 * C + c0, bd);
+  }
+  for_pixels_mlp<T, 4, PAIR_APPLY_FLY>(
+      g,
+      [&](long long pix, int c, uint4 (&raw)[4]) {
+        raw[0] = load_raw<T>(dy + (size_t)pix * dy_cs + dy_coff + c);
+        raw[1] = load_raw<T>(x2 + (size_t)pix * x2_cs + x2_coff + c);
+        raw[2] = load_raw<T>(xd + (size_t)pix * xd_cs + xd_coff + c);
+        raw[3].x = mask[(size_t)pix * groups + c / N];
+      },
+      [&](long long, long long pix, int c, const uint4 (&raw)[4]) {
+        float d[N], xv[N], xw[N], o[N], od[N];
+        const unsigned m = raw[3].x;
+        unpack<T>(raw[0], d);
+        unpack<T>(raw[1], xv);
+        unpack<T>(raw[2], xw);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const float xhat = (xv[k] - mu2[k]) * is2[k];
+          const float xhatd = (xw[k] - mud[k]) * isd[k];
+          const float dz = !((m >> k) & 1u) ? 0.f : d[k];
+          o[k] = k2[k] * (dz - a2[k] - xhat * b2[k]);
+          od[k] = kd[k] * (dz - ad[k] - xhatd * bd[k]);
+        }
+        store_vec<T>(dx2 + (size_t)pix * C + c, o);
+        store_vec<T>(dxd + (size_t)pix * C + c, od);
       });
 }
 
@@ -907,6 +1039,51 @@ extern "C" int jspsr_bn_backward(int dtype, const void* dy, int dy_cs, int dy_co
   else { BN_BWD_APPLY(3, dy, dy_cs, dy_coff, dres); }
 #undef BN_BWD_APPLY
   return check_launch("bn_bwd_apply");
+}
+
+// coef [6][C], then partial rows [chunks][3][C]: two C more than the three-plane layouts jspsr_reduce_workspace_bytes counts
+extern "C" size_t jspsr_bn_backward_pair_workspace_bytes(int dtype, int C) {
+  const size_t base = jspsr_reduce_workspace_bytes(dtype, C, 1);
+  return base ? base + (size_t)2 * C * sizeof(float) : 0;
+}
+
+extern "C" int jspsr_bn_backward_pair(int dtype, const void* dy, int dy_cs, int dy_coff, const void* mask, const void* x2, int x2_cs,
+                                      int x2_coff, const float* gamma2, const float* save_mean2, const float* save_invstd2,
+                                      int training2, float res_scale, const void* xd, int xd_cs, int xd_coff, const float* gammad,
+                                      const float* save_meand, const float* save_invstdd, int trainingd, void* dx2, void* dxd,
+                                      float* dgamma2, float* dbeta2, int accumulate2, float* dgammad, float* dbetad, int accumulated,
+                                      long long npix, int C, void* workspace, jspsr_stream_t stream) {
+  if (int e = check_c(dtype, C, "bn_backward_pair")) return e;
+  if (!dy || !mask || !x2 || !gamma2 || !save_mean2 || !save_invstd2 || !xd || !gammad || !save_meand || !save_invstdd || !dx2 ||
+      !dxd || !dgamma2 || !dbeta2 || !dgammad || !dbetad || !workspace || npix <= 0)
+    return fail(JSPSR_EINVAL, "bn_backward_pair: null pointer or empty tensor");
+  const int vec = dtype == JSPSR_F32 ? 4 : 8;
+  if (dy_cs % vec || dy_coff % vec || x2_cs % vec || x2_coff % vec || xd_cs % vec || xd_coff % vec)
+    return fail(JSPSR_EINVAL, "bn_backward_pair: channel pitches/offsets must be multiples of %d", vec);
+  if (dy_coff < 0 || x2_coff < 0 || xd_coff < 0 || dy_cs < dy_coff + C || x2_cs < x2_coff + C || xd_cs < xd_coff + C)
+    return fail(JSPSR_EINVAL, "bn_backward_pair: a channel slice of %d channels does not fit its pitch", C);
+  if (dx2 == dxd || dgamma2 == dgammad || dbeta2 == dbetad)
+    return fail(JSPSR_EINVAL, "bn_backward_pair: the two layers' outputs must be distinct");
+  for (const void* p : {dy, x2, xd, (const void*)dx2, (const void*)dxd, (const void*)workspace})
+    if (reinterpret_cast<uintptr_t>(p) % 16) return fail(JSPSR_EALIGN, "bn_backward_pair: tensors and workspace must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* coef = static_cast<float*>(workspace);
+  float* partial = coef + 6 * C;
+  const RedGeom g = make_red(npix, 1, C, vec);
+  const unsigned char* mk = static_cast<const unsigned char*>(mask);
+  DISPATCH(dtype, hipLaunchKernelGGL(bn_bwd_reduce_pair_kernel<T>, red_grid(g, vec), dim3(TX, TY), 0, s, static_cast<const T*>(dy), dy_cs,
+                                     dy_coff, mk, static_cast<const T*>(x2), x2_cs, x2_coff, save_mean2, save_invstd2,
+                                     static_cast<const T*>(xd), xd_cs, xd_coff, save_meand, save_invstdd, g, partial));
+  if (int e = check_launch("bn_bwd_reduce_pair")) return e;
+  hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, g.chunks, C, npix, gamma2, save_invstd2,
+                     training2, res_scale, accumulate2, dgamma2, dbeta2, gammad, save_invstdd, trainingd, accumulated, dgammad, dbetad,
+                     coef);
+  if (int e = check_launch("bn_bwd_finalize_pair")) return e;
+  DISPATCH(dtype, hipLaunchKernelGGL(bn_bwd_apply_pair_kernel<T>, red_grid(g, vec), dim3(TX, TY), 0, s, static_cast<const T*>(dy), dy_cs,
+                                     dy_coff, mk, static_cast<const T*>(x2), x2_cs, x2_coff, save_mean2, save_invstd2,
+                                     static_cast<const T*>(xd), xd_cs, xd_coff, save_meand, save_invstdd, coef, static_cast<T*>(dx2),
+                                     static_cast<T*>(dxd), g));
+  return check_launch("bn_bwd_apply_pair");
 }
 
 extern "C" int jspsr_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var,

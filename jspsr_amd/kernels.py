@@ -242,8 +242,10 @@ _ws_cache = {}
 
 def _workspace(dtype_code: int, C: int, nseg: int, device) -> torch.Tensor:
     """Scratch for the reduction kernels; cached per (stream, size class) -- stream-ordered reuse."""
-    lib = _lib.load()
-    n = lib.jspsr_reduce_workspace_bytes(dtype_code, C, nseg)
+    return _workspace_bytes(_lib.load().jspsr_reduce_workspace_bytes(dtype_code, C, nseg), device)
+
+
+def _workspace_bytes(n: int, device) -> torch.Tensor:
     key = (device, _stream())
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < n:
@@ -337,6 +339,49 @@ def bn_backward(dy, y, x, gamma, mean, invstd, training, relu, res_scale=1.0, wa
     if grads_into is not None:
         return dx, dres, None, None
     return dx, dres, dgamma, dbeta
+
+
+def bn_backward_pair(dy, mask, x2, gamma2, mean2, invstd2, training2, res_scale, xd, gammad, meand, invstdd, trainingd,
+                     grads_into2=None, grads_intod=None):
+    """The two BatchNorm backwards of a projecting residual block in one reduce and one apply pass -> (dx2, dxd, dgamma2,
+    dbeta2, dgammad, dbetad), the bits of
+        dx2, dres, .. = bn_backward(dy, None, x2, gamma2, mean2, invstd2, training2, 1, res_scale, want_dres=True, mask=mask)
+        dxd, .. = bn_backward(dres, None, xd, gammad, meand, invstdd, trainingd, 0)
+    without dres.  mask: the bit mask of bn_forward(want_mask=True).  grads_into2 / grads_intod: as bn_backward's
+    grads_into, per layer (that layer's dgamma, dbeta then come back as None)."""
+    _chk_s(dy, "bn_backward_pair")
+    _chk_s(x2, "bn_backward_pair")
+    _chk_s(xd, "bn_backward_pair")
+    B, H, W, C = x2.shape
+    if tuple(xd.shape) != (B, H, W, C) or tuple(dy.shape) != (B, H, W, C) or xd.dtype != x2.dtype or dy.dtype != x2.dtype:
+        raise ValueError(f"bn_backward_pair: dy {tuple(dy.shape)} {dy.dtype}, x2 {tuple(x2.shape)} {x2.dtype} and xd "
+                         f"{tuple(xd.shape)} {xd.dtype} must agree")
+    dx2 = torch.empty((B, H, W, C), dtype=x2.dtype, device=x2.device)
+    dxd = torch.empty((B, H, W, C), dtype=x2.dtype, device=x2.device)
+    sinks = []
+    for into in (grads_into2, grads_intod):
+        if into is not None:
+            for t in into:
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C or not t.is_cuda:
+                    raise ValueError("bn_backward_pair: grads_into buffers must be contiguous fp32 of C elements on the GPU")
+            sinks.append(tuple(into))
+        else:
+            sinks.append((torch.empty(C, dtype=torch.float32, device=x2.device), torch.empty(C, dtype=torch.float32, device=x2.device)))
+    dt = _dt(x2)
+    lib = _lib.load()
+    if mask is None or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != lib.jspsr_bn_mask_bytes(dt, B * H * W, C):
+        raise ValueError("bn_backward_pair: mask is not the bit mask bn_forward(want_mask=True) made for this shape")
+    ws = _workspace_bytes(lib.jspsr_bn_backward_pair_workspace_bytes(dt, C), x2.device)
+    _lib.check(lib.jspsr_bn_backward_pair(dt, dy.data_ptr(), pitch(dy), 0, mask.data_ptr(), x2.data_ptr(), pitch(x2), 0,
+                                          gamma2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(), int(training2), float(res_scale),
+                                          xd.data_ptr(), pitch(xd), 0, gammad.data_ptr(), meand.data_ptr(), invstdd.data_ptr(),
+                                          int(trainingd), dx2.data_ptr(), dxd.data_ptr(), sinks[0][0].data_ptr(), sinks[0][1].data_ptr(),
+                                          int(grads_into2 is not None), sinks[1][0].data_ptr(), sinks[1][1].data_ptr(),
+                                          int(grads_intod is not None), B * H * W, C, ws.data_ptr(), _stream()),
+               "jspsr_bn_backward_pair")
+    g2 = (None, None) if grads_into2 is not None else sinks[0]
+    gd = (None, None) if grads_intod is not None else sinks[1]
+    return dx2, dxd, g2[0], g2[1], gd[0], gd[1]
 
 
 def act_backward(dy, y, relu, want_dz=True, want_dbias=True, dz_channels=None):

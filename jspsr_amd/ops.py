@@ -608,6 +608,8 @@ bn_reduce_fused = os.environ.get("JSPSR_BN_REDUCE_FUSE", "1") != "0"      # bn1'
 # BatchNorm + residual + ReLU: the forward writes the ReLU's bit mask (1 bit per element) and the backward reads it in place
 # of the saved output
 bn_relu_mask = os.environ.get("JSPSR_BN_RELU_MASK", "1") != "0"
+# projection blocks: the shortcut BatchNorm's backward rides in bn2's two passes (jspsr_bn_backward_pair); 0: two calls
+bn_shortcut_merge = os.environ.get("JSPSR_BN_SHORTCUT_MERGE", "1") != "0"
 
 
 def aux_streams():
@@ -970,11 +972,20 @@ class _ResUnit(torch.autograd.Function):
         # bn2 (+ residual split): dz2 for the conv branch, dres for the shortcut
         pg1, pb1, pg2, pb2, pgd, pbd = ctx.bparams
         sink2, sink1 = _bn_sink(pg2, pb2), _bn_sink(pg1, pb1)
-        dz2, dres, dg2, db2 = K.bn_backward(dout, out, z2, g2, m2, i2, tr2, 1 if act else 0, scale,
-                                            want_dres=(need_x or has_d), beta=b2, grads_into=sink2, mask=mask2)
+        # a projection block's masked gradient feeds the shortcut's BatchNorm and nothing else: both backwards in one
+        # reduce and one apply pass, and it is never written (the mask-from-output and ReLU-free forms keep the two calls)
+        paired = bn_shortcut_merge and has_d and act and mask2 is not None
+        if paired:
+            sinkd = _bn_sink(pgd, pbd)
+            dz2, dzd, dg2, db2, dgd, dbd = K.bn_backward_pair(dout, mask2, z2, g2, m2, i2, tr2, scale, zd, gd, md, idd, trd,
+                                                              grads_into2=sink2, grads_intod=sinkd)
+            dres = None
+        else:
+            dz2, dres, dg2, db2 = K.bn_backward(dout, out, z2, g2, m2, i2, tr2, 1 if act else 0, scale,
+                                                want_dres=(need_x or has_d), beta=b2, grads_into=sink2, mask=mask2)
         if sink2 is not None:
             _bn_ready(pg2, pb2)
-        if dres is None:
+        if dres is None and not paired:
             dres = dout
         p1, p2, pd = ctx.wparams
 
@@ -1004,7 +1015,9 @@ class _ResUnit(torch.autograd.Function):
             _bn_ready(pg1, pb1)
         del dy1
         dW1 = None if wgrad_after_dgrad else _wgrad_async(p1, dz1, x, O, Cin, 3, 3, stride, 1)
-        dWd = dgd = dbd = None
+        dWd = None
+        if not paired:
+            dgd = dbd = None
         side = dres                      # what reaches x along the shortcut
         # gradient of x parked by its other consumer (SliceBuffer.join(defer=...)): rides along as an addend too
         deposit = None
@@ -1036,10 +1049,11 @@ class _ResUnit(torch.autograd.Function):
             if tuple(extra.shape) != tuple(x.shape):
                 raise RuntimeError(f"res_unit: deferred gradient {tuple(extra.shape)} does not match the input {tuple(x.shape)}")
             if not (has_d and need_x):
-                side, extra = side + extra, None
+                side, extra = (side + extra if side is not None else None), None   # (paired and no gradient of x wanted: unused)
         if has_d:
-            sinkd = _bn_sink(pgd, pbd)
-            dzd, _, dgd, dbd = K.bn_backward(dres, None, zd, gd, md, idd, trd, 0, 1.0, beta=bd, grads_into=sinkd)
+            if not paired:
+                sinkd = _bn_sink(pgd, pbd)
+                dzd, _, dgd, dbd = K.bn_backward(dres, None, zd, gd, md, idd, trd, 0, 1.0, beta=bd, grads_into=sinkd)
             if sinkd is not None:
                 _bn_ready(pgd, pbd)
             dWd = _wgrad_async(pd, dzd, x, O, Cin, 1, 1, stride, 0)
