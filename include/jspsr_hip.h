@@ -925,6 +925,61 @@ int jspsr_errdist_hist_forward(const float* const* cands, const long long* cand_
 int jspsr_errdist_kde_forward(const long long* hist, int n_cand, int key0, int K, int gridsize, double cut, double bw_adjust,
                               double* support, double* density, double* stats, void* workspace, jspsr_stream_t stream);
 
+/* ---- K22 (ABI v25, additive): whole-set scores by terrain class -- the stratified pooled table (csrc/strata.hip)
+ * Every DEM accuracy assessment reports its scores per land-cover class and per slope class.  What these entries replace is
+ * one jspsr_summary_valid_forward call per class (16 launches and a full read of every candidate each), or a device-to-host
+ * copy of every raster, boolean indexing and numpy.  The version stays 25: the entries are additive, as K16..K21 were.
+ *
+ * jspsr_strata_forward: K12's eleven-column row for every candidate and every class of a label plane, from ONE pool.
+ *   cands / cand_numel / n_cand / gt / gt_numel / windows / n_windows / total as K21's jspsr_errdist_hist_forward: the
+ *     windows' segment word is NOT read, everything the call is given is one pool; total = the sum of h * w < 2^32.
+ *   labels  device uint8 [labels_numel] in the GROUND TRUTH's layout, read at the gt offset and pitch of every window, as
+ *     K18 reads valid; labels_numel must equal gt_numel.
+ *   n_classes  1..32.
+ *   valid   K18's plane (device uint8 [valid_numel], valid_numel == gt_numel) or NULL.
+ *   A pooled element i belongs to class c = labels[i] iff c < n_classes and (valid is NULL or valid[i] != 0).  Every other
+ *     element influences nothing whatever the rasters hold there (NaN, inf, -32767, 1e30): it is read behind a select only
+ *     and never multiplied by a mask.  One label plane serves all candidates: every row is scored over the same elements.
+ *   out     device fp32 [n_cand][n_classes][11], K12's columns.  counts  device int64 [n_classes].
+ *   Per class the definitions are K12's and K18's: e = cand - gt, one rounded subtraction; the six bracketing order
+ *     statistics are exact elements of e, |e - Median| and |e|; the ranks and the LE95 weight come from the class count n_c
+ *     through the __host__ __device__ inline K18 uses (host twin: jspsr_summary_ranks), formed on the device; Median = (lo +
+ *     hi) * 0.5f; NMAD and LE95 by K12's expressions; RMSE = sqrt(sum / n_c) with the squares summed in fp64 per fixed run of
+ *     8192 pooled elements (per thread in element order, then K18's fold of a chunk), the runs folded in K12's order and
+ *     the result rounded once; PSNR formed in double.  n_c is the sum of the class's top-digit histogram, exact.
+ *   A class without an element: all 11 columns NaN, count 0; not an error.  A counted NaN makes that class's five scores
+ *     NaN for that candidate and touches no other class or candidate.  An element no window covers, or read outside a
+ *     buffer, is a NaN of class 0 (K12 counts it too).
+ *   Every pass over the pool serves all classes: per-class digit histograms in LDS (n_classes x 256 counters per key kind
+ *     and state), integer adds only, hot counters by ballot-aggregated increments.  16 launches whatever n_classes, n_cand,
+ *     the windows and the data are (census labels strata_prepare / strata_select); a row has the same bits for every n_cand,
+ *     whatever the other classes hold, on every run.  No host synchronisation.  A workgroup's LDS grows with n_classes, up to
+ *     128 KiB at 32.
+ *   JSPSR_EINVAL: a null pointer, n_cand outside 1..8, n_classes outside 1..32, an empty table, total >= 2^32, labels_numel or
+ *     valid_numel != gt_numel.  workspace: jspsr_strata_workspace_bytes(n_cand, n_classes, total) bytes (0 = bad arguments),
+ *     16-byte aligned (JSPSR_EALIGN); rasters and out 4-byte, counts 8-byte aligned.
+ * jspsr_slope_classes: a slope-class label plane from metre rasters in store layout, ONE launch (census label slope_classes).
+ *   z       device fp32 [pixels], the scenes back to back;  scenes  device int64 [n_scenes][3] = {offset, h, w}, offsets
+ *     ascending; a pixel no scene holds, or of a scene that leaves the plane, gets 255.
+ *   thresholds  HOST fp32 [n_thr], n_thr <= 31, >= 0 and ascending: t_k = float32((8 cell tan(edge_k pi / 180))^2), formed by
+ *     the caller in double and rounded once, so the device never evaluates atan.
+ *   valid   device uint8 [valid_numel] (valid_numel == pixels) or NULL;  out  device uint8 [pixels].
+ *   The 3 x 3 taps a b c / d e f / g h i (a b c the row above) are replicate-clamped inside their own scene.  In fp32, every
+ *     operation rounded once, in exactly this order: gx = ((c + 2f) + i) - ((a + 2d) + g); gy = ((g + 2h) + i) - ((a + 2b) +
+ *     c); p = gx*gx + gy*gy.  label = the number of thresholds t_k <= p; 255 where any of the nine clamped taps is invalid
+ *     (valid given and 0 there: K19's rule) or p is NaN.  A numpy float32 restatement reproduces every label bit for bit.
+ *   JSPSR_EINVAL: a null pointer, an empty plane, n_thr outside 0..31, thresholds negative, NaN or descending, valid_numel
+ *     != pixels; JSPSR_EALIGN: z not 4-byte aligned.  No host synchronisation, no workspace. */
+size_t jspsr_strata_workspace_bytes(int n_cand, int n_classes, long long total);
+int jspsr_strata_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
+                         long long gt_numel, const unsigned char* labels, long long labels_numel, int n_classes,
+                         const unsigned char* valid, long long valid_numel, const long long* windows, int n_windows,
+                         long long total, double value_max, float* out, long long* counts, void* workspace,
+                         jspsr_stream_t stream);
+int jspsr_slope_classes(const float* z, long long pixels, const long long* scenes, int n_scenes, const float* thresholds,
+                        int n_thr, const unsigned char* valid, long long valid_numel, unsigned char* out,
+                        jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

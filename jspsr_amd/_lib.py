@@ -109,6 +109,10 @@ SIGNATURES = {
     "jspsr_errdist_hist_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_ll, c_p, c_i, c_ll, ctypes.c_double, ctypes.c_double,
                                          c_p, c_p, c_p]),
     "jspsr_errdist_kde_forward": (c_i, [c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_strata_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_ll]),
+    "jspsr_strata_forward": (c_i, [c_p, c_p, c_i, c_p, c_ll, c_p, c_ll, c_i, c_p, c_ll, c_p, c_i, c_ll, ctypes.c_double,
+                                   c_p, c_p, c_p, c_p]),
+    "jspsr_slope_classes": (c_i, [c_p, c_ll, c_p, c_i, c_p, c_i, c_p, c_ll, c_p, c_p]),
     "jspsr_adamw_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p]),
     "jspsr_adamw_step_dev": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_p, c_p]),
     "jspsr_optim_workspace_bytes": (ctypes.c_size_t, []),

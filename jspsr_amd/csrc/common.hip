@@ -14,7 +14,7 @@ struct Slot {
   std::atomic<const char*> name{nullptr};
   std::atomic<long long> n{0};
 };
-Slot g_slots[128];
+Slot g_slots[192];
 
 void count_launch(const char* what) {
   for (Slot& s : g_slots) {

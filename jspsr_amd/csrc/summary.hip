@@ -36,6 +36,7 @@
 // (not numpy's fp32 pairwise mean); LE95's virtual index in double (numpy 2 forms it in float32 for float32 input); PSNR
 // without the 1e-8 the reference's online form adds for the baselines.
 #include "common.h"
+#include "summary_select.h"
 
 #include <cmath>
 
@@ -53,57 +54,8 @@ constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // segment, h, w, e offset, {offse
 constexpr int SEG_WORDS = 8;                  // e start, n, first chunk, 4 ranks, g (fp64 bits)
 static_assert(CHUNK % (MT * UNROLL) == 0, "a chunk is a whole number of unrolled steps");
 
-// The ranks and the weight every order statistic of n >= 1 elements is read at (jspsr_amd/summary.py: segment_ranks):
-// median (n - 1) / 2 and n / 2; v = 0.95 (n - 1) in double, l = floor(v), LE95 l and min(l + 1, n - 1), g = v - l.  No
-// contraction (this file is built with -ffp-contract=off): v is rounded before floor(v) is taken from it.
-struct Ranks {
-  long long m0, m1, l0, l1;
-  double g;
-};
-__host__ __device__ inline Ranks segment_ranks_of(long long n) {
-  Ranks r;
-  const double v = 0.95 * (double)(n - 1);
-  const double fl = floor(v);
-  r.m0 = (n - 1) / 2;
-  r.m1 = n / 2;
-  r.l0 = (long long)fl;
-  r.l1 = r.l0 + 1 < n - 1 ? r.l0 + 1 : n - 1;
-  r.g = v - fl;
-  return r;
-}
-
-__device__ __forceinline__ unsigned order_key(float f) {      // float -> unsigned key with the same ordering (NaNs last)
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// One wave-instruction's worth of histogram increments (csrc/scores.hip: hist_add).  The top digit of a good
-// prediction's errors falls into a handful of bins, and 64 lanes adding to one LDS address serialise: up to two rounds
-// take the bin of the first pending lane, count its lanes with a ballot and let that lane add the count once.
-// Every lane of the wave must arrive (wave-uniform trip counts at the call sites).
-__device__ __forceinline__ void hist_add(unsigned* __restrict__ hist, bool match, unsigned bin) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const unsigned long long act = __ballot(match);
-    if (act == 0ull) return;                                   // wave-uniform
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned b = (unsigned)__shfl((int)bin, leader, 64);
-    const bool mine = match && bin == b;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&hist[b], (unsigned)__popcll(m));
-    match = match && !mine;
-  }
-  if (match) atomicAdd(&hist[bin], 1u);
-}
+// Ranks / segment_ranks_of, order_key, key_value, wave_sum, hist_add and find_row: summary_select.h (shared with K22,
+// csrc/strata.hip).
 
 // ---- (a) scene assembly --------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ramp_weight(const float* __restrict__ ramp, int p, int w_l_c, int n_x, int pos, int j) {
@@ -179,16 +131,6 @@ struct Mask {                // K18, by value in the kernel arguments; all null 
   unsigned* chunk_n;           // [total_chunks] valid elements per chunk
   long long* counts;           // [n_seg] the output
 };
-
-// last row whose word `col` is <= v (rows ascending in that word; row 0 if none is)
-__device__ __forceinline__ int find_row(const long long* __restrict__ tab, int rows, int words, int col, long long v) {
-  int lo = 0, hi = rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(size_t)mid * words + col] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // The chunk of a segment this workgroup owns: segment, its start in e, the element range [lo, hi) inside the segment.
 __device__ __forceinline__ bool my_chunk(const long long* __restrict__ seg, int n_seg, long long total, int reps, int& s, long long& e_start,

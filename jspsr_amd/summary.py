@@ -28,6 +28,14 @@ float16 as the reference stores them, into one exact integer histogram per candi
 `kde_curves` evaluates the Gaussian kernel density estimate of seaborn's kdeplot from it in fp64; `error_distribution`
 does both for the candidates `summarise` takes.  Only the curves leave the card.
 
+Scores by terrain class (K22, csrc/strata.hip): `summarise_by_class(scenes, predictions, labels, class_names, ...)` breaks
+`summarise`'s pooled table down by the classes of a uint8 label plane in store layout -- land cover made from the store's
+mask with torch operators, or `slope_class_plane(scenes, edges_deg, cell)`, one launch that bins the Sobel slope of the
+ground truth against `slope_thresholds`.  `stratified_rows` is the raw call and `scores_by_class` the form for equal-shape
+tensors.  Every pass over the pool serves all classes at once (per-class digit histograms in LDS): still one call of 16
+launches, whatever the number of classes.  A label of 255 (or any label >= n_classes) belongs to no class.  Not built:
+per-candidate label planes, more than 32 classes, an "online" per-scene form.
+
 Device fp32 tensors go through the HIP kernels; host tensors through the same formulas as numpy / torch operators.
 """
 from __future__ import annotations
@@ -701,3 +709,240 @@ def error_distribution(scenes, predictions, baselines=None, *, border: float = 0
     return {name: {"support": sup[c].copy(), "density": den[c].copy(), "n": int(cnt[c, 0]), "n_in": int(cnt[c, 1]),
                    "n_below": int(cnt[c, 2]), "n_above": int(cnt[c, 3]), "mean": float(st[c, 0]), "std": float(st[c, 1]),
                    "bw": float(st[c, 2])} for c, name in enumerate(names)}
+
+
+# ---- K22: scores by terrain class ------------------------------------------------------------------------------------
+MAX_CLASSES = 32
+MAX_SLOPE_EDGES = 31
+NO_CLASS = 255                # the label of a pixel that belongs to no class
+
+
+def _check_labels(what, labels, gt, n_classes):
+    if not isinstance(n_classes, int) or isinstance(n_classes, bool) or not 1 <= n_classes <= MAX_CLASSES:
+        raise ValueError(f"{what}: n_classes = {n_classes!r}, 1..{MAX_CLASSES} are taken")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 1 or not labels.is_contiguous():
+        raise ValueError(f"{what}: labels must be a flat contiguous uint8 tensor")
+    if labels.numel() != gt.numel():
+        raise ValueError(f"{what}: labels has {labels.numel()} elements, the ground truth {gt.numel()}")
+    if labels.device != gt.device:
+        raise ValueError(f"{what}: labels on {labels.device}, the ground truth on {gt.device}")
+
+
+def stratified_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], labels: torch.Tensor, n_classes: int,
+                    value_max: float, valid: torch.Tensor | None = None):
+    """The raw per-class table call (K22).  cands, gt, windows, valid: as `pooled_rows` takes them; the windows' segment
+    entry is not read -- everything a call is given is one pool.  labels: a flat contiguous uint8 tensor of gt.numel()
+    elements on gt's device, read at gt's offsets and pitches as `valid` is.  A pooled element belongs to class c =
+    labels[i] iff c < n_classes (1..32) and (valid is None or valid[i] != 0); every other element (a label of 255, a label
+    >= n_classes, a masked one) influences nothing, whatever the rasters hold there.
+    -> (rows (n_cand, n_classes, 11) fp32, columns `ROW`; counts (n_classes,) int64) on the buffers' device.  Per class the
+    row is `pooled_rows(..., valid=(labels == c) & valid)`'s: the ranks come from the class count, a class without an element
+    has a NaN row and count 0, a counted NaN makes that class's five scores NaN for that candidate alone.
+    Device: one call of 16 launches whatever n_classes, the candidates, the windows and the data are, every pass over the
+    pool serving all classes; no host synchronisation; the same bits on every run, for every n_cand."""
+    n_cand = len(cands)
+    total = _check_pool("stratified_rows", cands, gt, windows, valid)
+    _check_labels("stratified_rows", labels, gt, n_classes)
+    if not windows:
+        raise ValueError("stratified_rows: no windows")
+    if total >= 2 ** 32:
+        raise ValueError(f"stratified_rows: {total} pooled elements, the rank counters hold fewer than 2^32")
+    if gt.is_cuda:
+        lib = _lib.load()
+        nbytes = lib.jspsr_strata_workspace_bytes(n_cand, n_classes, total)
+        if nbytes == 0:
+            raise ValueError(f"stratified_rows: {n_cand} candidates, {n_classes} classes, {total} pooled elements: not a size K22 takes")
+        tab = np.zeros((len(windows), _WIN_WORDS), dtype=np.int64)
+        e_off = 0
+        for i, (_, h, w, (go, gp), cs) in enumerate(windows):
+            tab[i, :6] = (0, h, w, e_off, go, gp)
+            for c, (co, cp) in enumerate(cs):
+                tab[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
+            e_off += h * w
+        dev = gt.device
+        host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)     # one stream-ordered upload, never written again
+        host.numpy()[...] = tab
+        table = host.to(dev, non_blocking=True)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((n_cand, n_classes, len(ROW)), dtype=torch.float32, device=dev)
+        counts = torch.empty(n_classes, dtype=torch.int64, device=dev)
+        ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
+        numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+        _lib.check(lib.jspsr_strata_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), labels.data_ptr(), labels.numel(), n_classes,
+                                            valid.data_ptr() if valid is not None else None,
+                                            valid.numel() if valid is not None else 0, table.data_ptr(), len(windows), total,
+                                            float(value_max), out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "jspsr_strata_forward")
+        return out, counts
+    g_np, l_np = gt.numpy(), labels.numpy()
+    idx = [go + np.arange(h)[:, None] * gp + np.arange(w)[None, :] for _, h, w, (go, gp), _ in windows]
+    cls = np.concatenate([l_np[i].reshape(-1) for i in idx]).astype(np.int64)
+    if valid is not None:
+        v_np = valid.numpy()
+        cls[np.concatenate([v_np[i].reshape(-1) for i in idx]) == 0] = NO_CLASS
+    out = np.empty((n_cand, n_classes, len(ROW)), dtype=np.float32)
+    for c, cand in enumerate(cands):
+        c_np = cand.numpy()
+        with np.errstate(invalid="ignore"):                     # inf - inf at a pixel of no class
+            e = np.concatenate([(c_np[co + np.arange(h)[:, None] * cp + np.arange(w)[None, :]] - g_np[i]).reshape(-1)
+                                for (_, h, w, _, cs), i in zip(windows, idx) for co, cp in [cs[c]]]).astype(np.float32, copy=False)
+        for k in range(n_classes):
+            ek = e[cls == k]
+            out[c, k] = _row_host(ek, value_max) if ek.size else _nan_row()
+    return torch.from_numpy(out), torch.from_numpy(np.bincount(cls[cls < n_classes], minlength=n_classes).astype(np.int64))
+
+
+def scores_by_class(cands, gt, labels, n_classes: int, value_max: float = 1.0, valid=None):
+    """Per-class pooled scores of equal-shape tensors, `scores_pooled`'s sibling (K22).  cands: a tensor or a list of up to 8,
+    each of gt's shape (..., H, W), fp32 metres; labels: a uint8 tensor of gt's shape on gt's device; valid: a bool or uint8
+    tensor of gt's shape, or None.  -> (rows (n_cand, n_classes, 11), counts (n_classes,)) as `stratified_rows` gives them."""
+    cands = [cands] if isinstance(cands, torch.Tensor) else list(cands)
+    if gt.dim() < 2 or any(c.shape != gt.shape for c in cands):
+        raise ValueError(f"scores_by_class: equal (..., H, W) tensors, got {[tuple(c.shape) for c in cands]} / {tuple(gt.shape)}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.shape != gt.shape:
+        raise ValueError(f"scores_by_class: labels must be a uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
+    if labels.device != gt.device:
+        raise ValueError(f"scores_by_class: labels on {labels.device}, the ground truth on {gt.device}")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != gt.shape:
+            raise ValueError(f"scores_by_class: valid must be a bool or uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
+        if valid.device != gt.device:
+            raise ValueError(f"scores_by_class: valid on {valid.device}, the ground truth on {gt.device}")
+        valid = valid.detach().contiguous().reshape(-1)
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid     # a bool is one byte, 0 or 1
+    H, W = gt.shape[-2:]
+    planes = gt.numel() // (H * W) if H * W else 0
+    windows = [(0, H, W, (p * H * W, W), [(p * H * W, W)] * len(cands)) for p in range(planes)]
+    flat = [t.detach().float().contiguous().reshape(-1) for t in cands]
+    return stratified_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, labels.detach().contiguous().reshape(-1),
+                           n_classes, value_max, valid=valid)
+
+
+def slope_thresholds(edges_deg, cell: float) -> np.ndarray:
+    """The thresholds `slope_class_plane` compares p = gx^2 + gy^2 of the unnormalised 3 x 3 Sobel taps with: a slope of
+    `edge` degrees on a grid of `cell` metres is a rise over run of tan(edge), and the Sobel sums are 8 * cell times the
+    gradient, so t_k = float32((8 * cell * tan(edge_k * pi / 180))^2), evaluated in double and rounded once.  The one place
+    they are formed.  edges_deg: strictly increasing within [0, 90), at most 31; cell > 0; ValueError otherwise."""
+    edges = [float(e) for e in edges_deg]
+    cell = float(cell)
+    if len(edges) > MAX_SLOPE_EDGES:
+        raise ValueError(f"slope_thresholds: {len(edges)} edges, at most {MAX_SLOPE_EDGES} are taken")
+    if any(not 0.0 <= e < 90.0 for e in edges) or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"slope_thresholds: edges_deg = {edges} must be strictly increasing within [0, 90)")
+    if not (cell > 0.0 and math.isfinite(cell)):
+        raise ValueError(f"slope_thresholds: cell = {cell} must be positive")
+    return np.array([(8.0 * cell * math.tan(e * math.pi / 180.0)) ** 2 for e in edges], dtype=np.float64).astype(np.float32)
+
+
+def _slope_labels_host(z: np.ndarray, thr: np.ndarray, valid) -> np.ndarray:
+    """One scene's labels as numpy float32 operators, in the kernel's operation order."""
+    t = np.pad(z.astype(np.float32, copy=False), 1, mode="edge")
+    h, w = z.shape
+    a, b, c = t[0:h, 0:w], t[0:h, 1:w + 1], t[0:h, 2:w + 2]
+    d, f = t[1:h + 1, 0:w], t[1:h + 1, 2:w + 2]
+    g, hh, i = t[2:h + 2, 0:w], t[2:h + 2, 1:w + 1], t[2:h + 2, 2:w + 2]
+    two = np.float32(2.0)
+    with np.errstate(all="ignore"):
+        gx = ((c + two * f) + i) - ((a + two * d) + g)
+        gy = ((g + two * hh) + i) - ((a + two * b) + c)
+        p = gx * gx + gy * gy
+        lab = (thr[:, None, None] <= p[None]).sum(axis=0).astype(np.uint8) if thr.size else np.zeros((h, w), np.uint8)
+    lab[np.isnan(p)] = NO_CLASS
+    if valid is not None:
+        v = np.pad(valid != 0, 1, mode="edge")
+        ok = np.ones((h, w), bool)
+        for dy in range(3):
+            for dx in range(3):
+                ok &= v[dy:dy + h, dx:dx + w]
+        lab[~ok] = NO_CLASS
+    return lab
+
+
+def slope_class_plane(scenes, edges_deg, cell: float, source: str = "hr_dem", valid=None) -> torch.Tensor:
+    """A slope-class label plane for `summarise_by_class`: flat uint8, in store layout on the store's device (K22, one launch).
+    Per pixel of `scenes.store[source]` ("hr_dem" or "lr_dem", metres): the 3 x 3 taps a b c / d e f / g h i, replicate-clamped
+    inside their own scene; in fp32, every operation rounded once, gx = ((c + 2f) + i) - ((a + 2d) + g), gy = ((g + 2h) + i) -
+    ((a + 2b) + c), p = gx*gx + gy*gy; label = the number of `slope_thresholds(edges_deg, cell)` that are <= p, so class k
+    holds the slopes in [edge_{k-1}, edge_k) and len(edges_deg) + 1 classes come out.  255 where p is NaN or, with `valid`
+    (a flat uint8 plane in store layout, or a list of per-scene planes), where any of the nine clamped taps is invalid.
+    cell: the grid spacing in metres.  ValueError for bad edges or cell before any launch."""
+    thr = slope_thresholds(edges_deg, cell)
+    if source not in ("hr_dem", "lr_dem"):
+        raise ValueError(f"slope_class_plane: source {source!r} is not a metre raster of the store ('hr_dem', 'lr_dem')")
+    z = scenes.store[source]
+    numel = sum(h * w for h, w in scenes.shapes)
+    if valid is not None:
+        valid = _valid_layout(scenes, valid, numel, z.device, "slope_class_plane")
+    if z.is_cuda:
+        out = torch.empty(numel, dtype=torch.uint8, device=z.device)
+        t = (ctypes.c_float * max(len(thr), 1))(*[float(v) for v in thr])
+        _lib.check(_lib.load().jspsr_slope_classes(z.data_ptr(), numel, scenes.scene_table.data_ptr(), len(scenes), t, len(thr),
+                                                   valid.data_ptr() if valid is not None else None,
+                                                   valid.numel() if valid is not None else 0, out.data_ptr(),
+                                                   torch.cuda.current_stream(z.device).cuda_stream), "jspsr_slope_classes")
+        return out
+    z_np, v_np, off, flat = z.numpy(), None if valid is None else valid.numpy(), 0, []
+    for h, w in scenes.shapes:
+        flat.append(_slope_labels_host(z_np[off:off + h * w].reshape(h, w), thr,
+                                       None if v_np is None else v_np[off:off + h * w].reshape(h, w)).reshape(-1))
+        off += h * w
+    return torch.from_numpy(np.concatenate(flat))
+
+
+def _labels_layout(scenes, labels, numel, device, what):
+    """`summarise_by_class`'s labels -> the flat uint8 plane in store layout on the store's device."""
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1:
+        if labels.numel() != numel or labels.dtype != torch.uint8 or labels.device != device:
+            raise ValueError(f"{what}: a flat labels tensor must be uint8 with the store's layout ({numel} elements) and device")
+        return labels.contiguous()
+    if len(labels) != len(scenes):
+        raise ValueError(f"{what}: labels has {len(labels)} planes, the store {len(scenes)} scenes")
+    flat = []
+    for i, v in enumerate(labels):
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        a = a.reshape(a.shape[:2]) if a.ndim == 3 and a.shape[2] == 1 else a
+        if a.dtype != np.uint8 or tuple(a.shape) != tuple(scenes.shapes[i]):
+            raise ValueError(f"{what}: labels[{i}] is {a.dtype} {a.shape}, expected a uint8 plane of {tuple(scenes.shapes[i])}")
+        flat.append(np.ascontiguousarray(a).reshape(-1))
+    return torch.from_numpy(np.concatenate(flat)).to(device)
+
+
+def summarise_by_class(scenes, predictions, labels, class_names, baselines=None, *, value_max: float, border: float = 0.0,
+                       patch_size: int, valid=None):
+    """`summarise`'s pooled table broken down by terrain class (K22).
+
+    scenes, predictions, baselines, value_max, border, patch_size, valid: as `summarise` takes them -- the candidates, the
+    windows and the crop are exactly its own.  labels: a flat uint8 device plane in store layout (`slope_class_plane`, or
+    made from the store's land-cover mask, see below), or a list of per-scene (h, w) uint8 arrays, uploaded once; class c
+    is named class_names[c], n_classes = len(class_names) (1..32); a label >= n_classes (255 by convention) belongs to no
+    class.  One plane for all candidates.
+    -> {candidate: {class name: {"RMSE", "Median", "NMAD", "LE95", "PSNR", "N", "share"}}}: N the pixels scored, share = N /
+    the sum of N over the classes (NaN when no pixel has a class); a class without a pixel has NaN scores.
+    One K22 call and one device-to-host copy (the counts ride behind the rows), no other synchronisation.
+
+    Land-cover labels from a store's one-hot mask with torch operators (the first set channel, else 255; not hot):
+
+        m = scenes.store["mask"].view(-1, C)                     # (pixels, C) uint8, store layout
+        on = m.ne(0)
+        labels = torch.where(on.any(1), on.to(torch.uint8).argmax(1), 255).to(torch.uint8)
+    """
+    class_names = [str(n) for n in class_names]
+    if not 1 <= len(class_names) <= MAX_CLASSES or len(set(class_names)) != len(class_names):
+        raise ValueError(f"summarise_by_class: {len(class_names)} class names, 1..{MAX_CLASSES} distinct ones are taken")
+    names, cands, gt, windows, valid = _assemble("summarise_by_class", scenes, predictions, baselines, border, patch_size, valid)
+    labels = _labels_layout(scenes, labels, gt.numel(), gt.device, "summarise_by_class")
+    n_classes = len(class_names)
+    rows, counts = stratified_rows(cands, gt, windows, labels, n_classes, value_max, valid=valid)
+    both = torch.cat((rows.double().reshape(-1), counts.double())).cpu().numpy()      # the one copy (counts: exact below 2^53)
+    host = both[:rows.numel()].reshape(tuple(rows.shape))
+    count = [int(v) for v in both[rows.numel():]]
+    n_all = sum(count)
+    table = {}
+    for c, name in enumerate(names):
+        table[name] = {}
+        for k, cname in enumerate(class_names):
+            d = {col: float(host[c, k, j]) for j, col in enumerate(COLUMNS)}
+            d["N"] = count[k]
+            d["share"] = count[k] / n_all if n_all else float("nan")
+            table[name][cname] = d
+    return table
