@@ -522,6 +522,39 @@ int jspsr_loss_menu_valid_forward(const float* pred, const float* gt, const unsi
 int jspsr_loss_menu_valid_backward(const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
                                    int H, int W, const double* slot_weight, const float* grad_total, float* grad_pred,
                                    const void* workspace, jspsr_stream_t stream);
+/* K23: the K19 menu entries with SSIM over the plane under the "window" rule (ssim_rule = 1; anything else is
+ * JSPSR_EINVAL): an element of the valid (H-10) x (W-10) SSIM map counts iff all 121 pixels under its window are valid;
+ * with N_s the counted elements of the whole call, SSIM = 1 - sum_counted S / N_s.  N_s = 0 gives value 0 and gradient 0.
+ * pred and gt are staged as 0 at invalid pixels behind a select, so a masked pixel has no influence whatever they hold
+ * there, and its gradient stays the caller's +0.0; a NaN at a valid pixel poisons the result as in the unmasked call.  N_s
+ * is counted as an integer by the forward (one launch, census label ssim_valid_forward), folded by the combine kernel and
+ * kept in the workspace, where the backward (one launch, ssim_valid_backward) forms (float)(w / (double)N_s): no host
+ * synchronisation.  An all-ones plane gives the bits of jspsr_loss_menu_forward / _backward.  Every other argument and
+ * every other term as in jspsr_loss_menu_valid_*, whose launches and bits these are without the SSIM bit.  SSIM needs
+ * H, W >= 11 (JSPSR_EINVAL, workspace query 0).  The jspsr_loss_menu_valid_* entries themselves keep refusing the bit. */
+size_t jspsr_loss_menu_valid_ssim_workspace_bytes(int terms, int planes, int H, int W, int ssim_rule);
+int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
+                                       int H, int W, int ssim_rule, int n_keys, const int* key_slot,
+                                       const double* key_weight, const float* base_losses, float* out, void* workspace,
+                                       jspsr_stream_t stream);
+int jspsr_loss_menu_valid_ssim_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                        int planes, int H, int W, int ssim_rule, const double* slot_weight,
+                                        const float* grad_total, float* grad_pred, const void* workspace,
+                                        jspsr_stream_t stream);
+/* K23: SSIM of every tile of a batch for the meters.  pred, gt: UNCROPPED fp32 [B][H][W]; the crop of `border` (a
+ * fraction in [0, 0.5): int(H * border) rows and int(W * border) columns on every side, in double) is index arithmetic.
+ * valid: [B][H][W] bytes, nonzero = valid, or NULL = every pixel.  same / window11 as jspsr_ssim_forward (same = 0: the
+ * valid map, all of whose windows lie inside the crop; same = 1: the map of the crop with zero padding 5, where a tap
+ * outside the crop is padding, not a void).  out[b] (device) = the mean of S over tile b's counted map elements, NaN
+ * where there is none; counts[b] (device int32) = their number.  Two launches whatever B is (ssim_tiles_forward,
+ * ssim_tiles_finalize); tile b's partials are folded in the order jspsr_ssim_forward folds a one-plane call, so with
+ * valid = NULL or all ones out[b] has the bits of jspsr_ssim_forward on the prepared tile b alone.  JSPSR_EINVAL: a null
+ * pointer (valid excepted), B <= 0, a border outside [0, 0.5), nothing left after the crop, same = 0 with fewer than 11
+ * rows or columns left.  workspace: jspsr_ssim_tiles_workspace_bytes() (0 = bad arguments). */
+size_t jspsr_ssim_tiles_workspace_bytes(int B, int H, int W, double border, int same);
+int jspsr_ssim_tiles_forward(const float* pred, const float* gt, const unsigned char* valid, int B, int H, int W,
+                             double border, int same, const float* window11, float* out, int* counts, void* workspace,
+                             jspsr_stream_t stream);
 /* Mean SSIM of prepared [0,1] tiles (MeterSSIM.update, evaluation/metrics.py:275-335), pred clamped to [0,1]:
  * same = 0 is piq.ssim(downsample=False) on the valid map with the Gaussian window (window11 ignored, may be NULL);
  * same = 1 is the local ssim (metrics.py:20-63): H x W map over the zero-padded planes with the 11-tap window11 (host

@@ -88,6 +88,11 @@ SIGNATURES = {
     "jspsr_loss_menu_valid_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "jspsr_loss_menu_valid_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_loss_menu_valid_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_loss_menu_valid_ssim_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
+    "jspsr_loss_menu_valid_ssim_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_loss_menu_valid_ssim_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "jspsr_ssim_tiles_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, ctypes.c_double, c_i]),
+    "jspsr_ssim_tiles_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, ctypes.c_double, c_i, c_p, c_p, c_p, c_p, c_p]),
     "jspsr_ssim_workspace_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "jspsr_ssim_forward": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "jspsr_metrics_workspace_bytes": (ctypes.c_size_t, [c_i, c_i]),

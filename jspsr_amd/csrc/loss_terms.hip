@@ -190,31 +190,57 @@ __global__ __launch_bounds__(PT) void menu_bwd_kernel(const float* __restrict__ 
 // Forward over one ST x ST tile of the map of one plane.  SAME = false: valid map (H-10) x (W-10), map element q reads
 // pixels q .. q+10; SAME = true: H x W map over the zero-padded plane, q reads q-5 .. q+5.  x = clamp(pred, 0, 1).
 // coef (valid mode, may be NULL): alpha, beta, gamma of every map element, three planar maps cplane apart.
-template <bool SAME>
+// MASKED (K23, the "window" rule): the planes are H x W windows of rasters with row stride ld and plane stride ps (the
+// per-tile meter crops by index arithmetic), valid one byte per pixel beside them (NULL = every pixel valid).  The staged
+// patch carries one BIT per pixel, 1 = an in-plane void (a wave's ballot is 64 consecutive pixels of the patch, so the
+// flags cost no LDS traffic to speak of); pred and gt are staged as 0 there, behind a select.  Positions outside the
+// plane are the zero padding, not voids.  "A void under the window" is formed separably, in integers, in the two passes
+// of the moments: 11 bits of a row, then 11 rows of a column; a map element counts iff there is none.  S joins the
+// partial, and alpha, beta, gamma are written, for counted elements only (zeros elsewhere: the backward's adjoint filter
+// reads them); pcnt gets the workgroup's count.  Every float operation of a counted element is the unmasked kernel's.
+template <bool SAME, bool MASKED>
 __global__ __launch_bounds__(SN) void ssim_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                      int H, int W, int Hm, int Wm, int tiles_x, Win11 k,
                                                      float* __restrict__ coef, long long cplane,
-                                                     float* __restrict__ part) {
+                                                     float* __restrict__ part,
+                                                     const unsigned char* __restrict__ valid, int ld, long long ps,
+                                                     unsigned int* __restrict__ pcnt) {
   __shared__ float xs[SH * SH], ys[SH * SH];
   __shared__ float hs[5][SH * ST];
   __shared__ float red[SN / 64];
+  __shared__ unsigned long long vb[MASKED ? (SH * SH + 63) / 64 + 2 : 1];   // void bits of the patch, row-major, zero tail
+  __shared__ unsigned long long hb[MASKED ? SH * ST / 64 : 1];              // "a void in the 11 taps right of (r, c)"
+  __shared__ unsigned int redc[SN / 64];
   const int plane = blockIdx.y, tile = blockIdx.x;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int q0y = ty * ST, q0x = tx * ST;
   const int i0y = q0y - (SAME ? 5 : 0), i0x = q0x - (SAME ? 5 : 0);
-  const float* P = pred + (long long)plane * H * W;
-  const float* G = gt + (long long)plane * H * W;
+  const long long pbase = MASKED ? (long long)plane * ps : (long long)plane * H * W;
+  const int rs = MASKED ? ld : W;
+  const float* P = pred + pbase;
+  const float* G = gt + pbase;
+  if (MASKED && threadIdx.x < 2) vb[(SH * SH + 63) / 64 + threadIdx.x] = 0;
   for (int o = threadIdx.x; o < SH * SH; o += SN) {
     const int r = o / SH, c = o - r * SH;
     const int iy = i0y + r, ix = i0x + c;
     float xv = 0.f, yv = 0.f;
+    bool bad = false;
     if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-      const long long j = (long long)iy * W + ix;
+      const long long j = (long long)iy * rs + ix;
       xv = fminf(fmaxf(P[j], 0.f), 1.f);
       yv = G[j];
+      if (MASKED) {
+        bad = valid && !valid[pbase + j];
+        xv = bad ? 0.f : xv;
+        yv = bad ? 0.f : yv;
+      }
     }
     xs[o] = xv;
     ys[o] = yv;
+    if (MASKED) {                                 // lane 0 of a wave holds o = a multiple of 64 and is active whenever a lane is
+      const unsigned long long m = __ballot(bad);
+      if ((threadIdx.x & 63) == 0) vb[o >> 6] = m;
+    }
   }
   __syncthreads();
   // horizontal: SH rows x ST columns of the five moments
@@ -233,10 +259,25 @@ __global__ __launch_bounds__(SN) void ssim_fwd_kernel(const float* __restrict__ 
       a4 += w * (xv * yv);
     }
     hs[0][o] = a0; hs[1][o] = a1; hs[2][o] = a2; hs[3][o] = a3; hs[4][o] = a4;
+    if (MASKED) {                                 // bits p .. p + 10 of the patch; o = r * 32 + c, so a ballot is two rows of hb
+      const int p = r * SH + c, wd = p >> 6, sh = p & 63;
+      const unsigned long long taps = (vb[wd] >> sh) | (sh ? vb[wd + 1] << (64 - sh) : 0ull);
+      const unsigned long long m = __ballot((taps & 0x7FFull) != 0);
+      if ((threadIdx.x & 63) == 0) hb[o >> 6] = m;
+    }
   }
   __syncthreads();
   // vertical: 4 consecutive rows of one column per thread share 14 staged rows
   const int c = threadIdx.x & (ST - 1), r0 = (threadIdx.x >> 5) * 4;
+  unsigned int voids[4] = {0, 0, 0, 0};         // MASKED: nonzero = a void under the window of the thread's element j
+  if (MASKED) {
+    const unsigned int* hrow = reinterpret_cast<const unsigned int*>(hb);     // 32 columns: one word per row
+    unsigned int col = 0;                       // bit t: a void in the 11 taps of row r0 + t from column c on
+#pragma unroll
+    for (int t = 0; t < 14; ++t) col |= ((hrow[r0 + t] >> c) & 1u) << t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) voids[j] = (col >> j) & 0x7FFu;
+  }
   float mo[5][4];
 #pragma unroll
   for (int m = 0; m < 5; ++m) {
@@ -252,37 +293,69 @@ __global__ __launch_bounds__(SN) void ssim_fwd_kernel(const float* __restrict__ 
     }
   }
   float s_acc = 0.f;
+  unsigned int n_acc = 0;
   const int qx = q0x + c;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int qy = q0y + r0 + j;
     if (qy < Hm && qx < Wm) {
+      // MASKED: the unmasked arithmetic on every element (same code shape, so the same bits under an all-ones plane); an
+      // element with a void under its window is dropped by selects: not summed, not counted, zero coefficients
+      const bool counted = !MASKED || voids[j] == 0;
       const float mx = mo[0][j], my = mo[1][j];
       const float sxx = mo[2][j] - mx * mx, syy = mo[3][j] - my * my, sxy = mo[4][j] - mx * my;
       const float A = 2.f * mx * my + C1, B = mx * mx + my * my + C1, Cc = 2.f * sxy + C2, D = sxx + syy + C2;
       const float S = (A * Cc) / (B * D);
-      s_acc += S;
+      if (MASKED) {
+        s_acc = counted ? s_acc + S : s_acc;
+        n_acc += counted ? 1u : 0u;
+      } else {
+        s_acc += S;
+      }
       if (!SAME && coef) {
         const long long qi = (long long)plane * Hm * Wm + (long long)qy * Wm + qx;
-        coef[qi] = S * (2.f * my / A - 2.f * mx / B - 2.f * my / Cc + 2.f * mx / D);
-        coef[cplane + qi] = -S / D;
-        coef[2 * cplane + qi] = 2.f * S / Cc;
+        const float ca = S * (2.f * my / A - 2.f * mx / B - 2.f * my / Cc + 2.f * mx / D), cb = -S / D, cg = 2.f * S / Cc;
+        coef[qi] = counted ? ca : 0.f;
+        coef[cplane + qi] = counted ? cb : 0.f;
+        coef[2 * cplane + qi] = counted ? cg : 0.f;
       }
     }
   }
+  if (MASKED) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) n_acc += __shfl_xor(n_acc, d, 64);
+    if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = n_acc;
+  }
   s_acc = block_reduce<false>(s_acc, red);
-  if (threadIdx.x == 0) part[(size_t)plane * gridDim.x + tile] = s_acc;
+  if (threadIdx.x == 0) {
+    part[(size_t)plane * gridDim.x + tile] = s_acc;
+    if (MASKED) {
+      unsigned int t = 0;
+      for (int w = 0; w < SN / 64; ++w) t += redc[w];
+      pcnt[(size_t)plane * gridDim.x + tile] = t;
+    }
+  }
 }
 
 // Backward (valid mode) over one ST x ST pixel tile of one plane: the adjoint ("full") window filter of alpha, beta,
 // gamma (zero outside the map), then grad[p] += -(w up / M) [Ka + 2 x Kb + y Kg] where 0 <= pred <= 1 (clamp's mask).
+// MASKED: cw = (float)(wd / (double)N_s) is formed here from the forward's count (nothing counted: return, the caller's
+// zeros stand), and an invalid pixel is skipped -- every window over it has zero coefficients, but pred or gt may hold NaN.
+template <bool MASKED>
 __global__ __launch_bounds__(SN) void ssim_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                      const float* __restrict__ coef, long long cplane, int H, int W,
                                                      int Hm, int Wm, int tiles_x, Win11 k,
                                                      const float* __restrict__ gscale, float cw,
-                                                     float* __restrict__ grad) {
+                                                     float* __restrict__ grad,
+                                                     const unsigned char* __restrict__ valid,
+                                                     const long long* __restrict__ ns, double wd) {
   __shared__ float cs[3][SH * SH];
   __shared__ float hs[3][SH * ST];
+  if (MASKED) {
+    const long long n = ns[0];
+    if (n <= 0) return;
+    cw = (float)(wd / (double)n);
+  }
   const int plane = blockIdx.y, tile = blockIdx.x;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int p0y = ty * ST, p0x = tx * ST;
@@ -338,6 +411,7 @@ __global__ __launch_bounds__(SN) void ssim_bwd_kernel(const float* __restrict__ 
     if (py < H && px < W) {
       const long long i = base + (long long)py * W + px;
       const float x = pred[i], y = gt[i];
+      if (MASKED && !valid[i]) continue;          // the gradient there stays the +0.0 the caller wrote
       if (x >= 0.f && x <= 1.f) grad[i] += s * (kf[0][j] + 2.f * x * kf[1][j] + y * kf[2][j]);
     }
   }
@@ -503,33 +577,53 @@ __global__ __launch_bounds__(PT) void menu_bwd_valid_kernel(const float* __restr
   }
 }
 
-// menu_combine_kernel with the fourth wave folding the integer counts instead of SSIM's partials; nn[0] = N
+// Fixed-order integer fold of `rows` per-workgroup counts by one wave; the sum lands in every lane.
+__device__ long long wave_count(const unsigned int* __restrict__ p, int rows) {
+  const int lane = threadIdx.x & 63;
+  long long s = 0;
+  if (p)
+    for (int r = lane; r < rows; r += 64) s += (long long)p[r];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+// menu_combine_kernel with a wave for the integer counts: nn[0] = N of the pointwise terms (psum / pcnt NULL: none
+// configured) and, with SSIM under the window rule (ssum / scnt, else NULL), a fifth wave folding SSIM's partials in
+// menu_combine_kernel's order and a sixth their counts, ns[0] = N_s, the counted map elements.  COMBINE_VALID_THREADS
+// threads: every fold is a latency-bound walk by one wave, so they run side by side, not one after another
+constexpr int COMBINE_VALID_THREADS = 6 * 64;
 __global__ void menu_combine_valid_kernel(const float* __restrict__ psum, const unsigned int* __restrict__ pcnt, int nb,
                                           const float* __restrict__ base, KeyMap km, float* __restrict__ out,
-                                          long long* __restrict__ nn) {
-  __shared__ double acc[3];
-  __shared__ long long cnt;
+                                          long long* __restrict__ nn, const float* __restrict__ ssum,
+                                          const unsigned int* __restrict__ scnt, int nbs, long long* __restrict__ ns) {
+  __shared__ double acc[4];
+  __shared__ long long cnt, cnt_s;
   const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (q < 3) {
     const double s = wave_fold(psum, nb, 3, q);
     if (lane == 0) acc[q] = s;
-  } else {
-    long long s = 0;
-    for (int r = lane; r < nb; r += 64) s += (long long)pcnt[r];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  } else if (q == 3) {
+    const long long s = wave_count(pcnt, nb);
     if (lane == 0) cnt = s;
+  } else if (q == 4) {
+    const double a = wave_fold(ssum, nbs, 1, 0);
+    if (lane == 0) acc[3] = a;
+  } else {
+    const long long m = wave_count(scnt, nbs);
+    if (lane == 0) cnt_s = m;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
-    const long long n = cnt;
+    const long long n = cnt, m = cnt_s;
     float f[NSLOT];
     for (int i = 0; i < 3; ++i) f[i] = base ? base[i] : 0.f;
     f[S_BERHU] = n > 0 ? (float)(acc[0] / (double)n) : 0.f;
     f[S_BCE] = n > 0 ? (float)(acc[1] / (double)n) : 0.f;
     f[S_NORM] = n > 0 ? (float)(acc[2] / (double)n) : 0.f;
-    f[S_SSIM] = 0.f;
+    f[S_SSIM] = m > 0 ? (float)(1.0 - acc[3] / (double)m) : 0.f;
+    if (ns) ns[0] = m;
     double tot = 0.0;
     for (int i = 0; i < km.n; ++i) {
       const float v = f[km.slot[i]];
@@ -538,6 +632,19 @@ __global__ void menu_combine_valid_kernel(const float* __restrict__ psum, const 
     }
     out[km.n] = (float)tot;
     nn[0] = n;
+  }
+}
+
+// Per-tile form: workgroup b (one wave) folds plane b's `tiles` partials in ssim_finalize_kernel's order for a
+// single-sample call and divides by the plane's own count; a plane with nothing counted is NaN with count 0.
+__global__ void ssim_tiles_finalize_kernel(const float* __restrict__ ssum, const unsigned int* __restrict__ scnt, int tiles,
+                                           float* __restrict__ out, int* __restrict__ counts) {
+  const int b = blockIdx.x;
+  const double s = wave_fold(ssum + (size_t)b * tiles, tiles, 1, 0);
+  const long long m = wave_count(scnt + (size_t)b * tiles, tiles);
+  if (threadIdx.x == 0) {
+    out[b] = m > 0 ? (float)(s / (double)m) : __int_as_float(0x7fc00000);
+    counts[b] = (int)m;
   }
 }
 
@@ -581,9 +688,9 @@ extern "C" int jspsr_loss_menu_forward(const float* pred, const float* gt, int t
     if (int e = check_launch("loss_menu_sum")) return e;
   }
   if (terms & T_SSIM) {
-    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
+    hipLaunchKernelGGL((ssim_fwd_kernel<false, false>), dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
                        L.Hm, L.Wm, L.tiles_x, gaussian_window(), reinterpret_cast<float*>(ws + L.coef), L.cplane,
-                       reinterpret_cast<float*>(ws + L.ssum));
+                       reinterpret_cast<float*>(ws + L.ssum), nullptr, 0, 0ll, nullptr);
     if (int e = check_launch("ssim_forward")) return e;
   }
   hipLaunchKernelGGL(menu_combine_kernel, dim3(1), dim3(256), 0, st, pw ? reinterpret_cast<const float*>(ws + L.psum) : nullptr,
@@ -611,9 +718,9 @@ extern "C" int jspsr_loss_menu_backward(const float* pred, const float* gt, int 
   }
   if (terms & T_SSIM) {
     const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
-    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
+    hipLaunchKernelGGL(ssim_bwd_kernel<false>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
                        reinterpret_cast<const float*>(ws + L.coef), L.cplane, H, W, L.Hm, L.Wm, tx, gaussian_window(),
-                       grad_total, (float)(slot_weight[S_SSIM] / (double)L.cplane), grad_pred);
+                       grad_total, (float)(slot_weight[S_SSIM] / (double)L.cplane), grad_pred, nullptr, nullptr, 0.0);
     if (int e = check_launch("ssim_backward")) return e;
   }
   return JSPSR_OK;
@@ -654,9 +761,9 @@ extern "C" int jspsr_loss_menu_valid_forward(const float* pred, const float* gt,
                      reinterpret_cast<const float*>(ws + L.pmax), L.nbm, reinterpret_cast<float*>(ws),
                      reinterpret_cast<float*>(ws + L.psum), reinterpret_cast<unsigned int*>(ws + L.pcnt));
   if (int e = check_launch("loss_menu_valid_sum")) return e;
-  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const float*>(ws + L.psum),
+  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(COMBINE_VALID_THREADS), 0, st, reinterpret_cast<const float*>(ws + L.psum),
                      reinterpret_cast<const unsigned int*>(ws + L.pcnt), L.nb, base_losses, km, out,
-                     reinterpret_cast<long long*>(ws + L.nn));
+                     reinterpret_cast<long long*>(ws + L.nn), nullptr, nullptr, 0, nullptr);
   return check_launch("loss_menu_valid_combine");
 }
 
@@ -694,12 +801,174 @@ extern "C" int jspsr_ssim_forward(const float* pred, const float* gt, int planes
   float* part = static_cast<float*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (same)
-    hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
-                       nullptr, 0ll, part);
+    hipLaunchKernelGGL((ssim_fwd_kernel<true, false>), dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
+                       nullptr, 0ll, part, nullptr, 0, 0ll, nullptr);
   else
-    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
-                       nullptr, 0ll, part);
+    hipLaunchKernelGGL((ssim_fwd_kernel<false, false>), dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
+                       nullptr, 0ll, part, nullptr, 0, 0ll, nullptr);
   if (int e = check_launch("ssim_forward")) return e;
   hipLaunchKernelGGL(ssim_finalize_kernel, dim3(1), dim3(64), 0, st, part, tx * ty * planes, (long long)planes * Hm * Wm, out);
   return check_launch("ssim_finalize");
+}
+
+// ---- K23: SSIM over a validity plane, the "window" rule -----------------------------------------------------------------
+// The K19 menu entries plus SSIM: a map element counts iff every pixel under its 11x11 window is valid.  ssim_rule 1 =
+// window.  Without the SSIM bit these run exactly the launches of jspsr_loss_menu_valid_* on the same workspace layout.
+namespace {
+
+struct VsLayout {
+  ValidLayout V;
+  int nbs = 0, tiles_x = 0, tiles_y = 0, Hm = 0, Wm = 0;
+  size_t ssum = 0, scnt = 0, ns = 0, coef = 0, bytes = 0;
+  long long cplane = 0;
+};
+
+VsLayout vs_layout(int terms, int planes, int H, int W) {
+  VsLayout L;
+  L.V = valid_layout(planes, H, W);
+  size_t off = L.V.bytes;
+  if (terms & T_SSIM) {
+    L.Hm = H - 10; L.Wm = W - 10;
+    L.tiles_x = (L.Wm + ST - 1) / ST; L.tiles_y = (L.Hm + ST - 1) / ST;
+    L.nbs = L.tiles_x * L.tiles_y * planes;
+    L.ssum = off; off += al16((size_t)L.nbs * 4);
+    L.scnt = off; off += al16((size_t)L.nbs * 4);
+    L.ns = off; off += 16;    // long long N_s
+    L.cplane = (long long)planes * L.Hm * L.Wm;
+    L.coef = off; off += al16((size_t)L.cplane * 3 * 4);
+  }
+  L.bytes = off;
+  return L;
+}
+
+bool vs_args_ok(int terms, int planes, int H, int W, int ssim_rule) {
+  return terms > 0 && !(terms & ~T_ALL) && dims_ok(planes, H, W) && ssim_rule == 1 && !((terms & T_SSIM) && (H < 11 || W < 11));
+}
+
+}  // namespace
+
+extern "C" size_t jspsr_loss_menu_valid_ssim_workspace_bytes(int terms, int planes, int H, int W, int ssim_rule) {
+  if (!vs_args_ok(terms, planes, H, W, ssim_rule)) return 0;
+  return vs_layout(terms, planes, H, W).bytes;
+}
+
+extern "C" int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                                  int planes, int H, int W, int ssim_rule, int n_keys, const int* key_slot,
+                                                  const double* key_weight, const float* base_losses, float* out,
+                                                  void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
+      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
+    return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: bad arguments");
+  if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: SSIM needs H, W >= 11");
+  KeyMap km{};
+  km.n = n_keys;
+  for (int i = 0; i < n_keys; ++i) {
+    const int s = key_slot[i];
+    const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < NSLOT && (terms & (1 << (s - S_BERHU))));
+    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: key %d has slot %d outside the configured terms", i, s);
+    km.slot[i] = s;
+    km.w[i] = key_weight[i];
+  }
+  const VsLayout L = vs_layout(terms, planes, H, W);
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  const bool pw = terms & (T_BERHU | T_BCE | T_NORM), ss = terms & T_SSIM;
+  if (terms & T_BERHU) {
+    hipLaunchKernelGGL(menu_max_valid_kernel, dim3(L.V.nbm), dim3(PT), 0, st, pred, gt, valid, n,
+                       reinterpret_cast<float*>(ws + L.V.pmax));
+    if (int e = check_launch("loss_menu_valid_max")) return e;
+  }
+  if (pw) {
+    hipLaunchKernelGGL(menu_sum_valid_kernel, dim3(L.V.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
+                       reinterpret_cast<const float*>(ws + L.V.pmax), L.V.nbm, reinterpret_cast<float*>(ws),
+                       reinterpret_cast<float*>(ws + L.V.psum), reinterpret_cast<unsigned int*>(ws + L.V.pcnt));
+    if (int e = check_launch("loss_menu_valid_sum")) return e;
+  }
+  if (ss) {
+    hipLaunchKernelGGL((ssim_fwd_kernel<false, true>), dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
+                       L.Hm, L.Wm, L.tiles_x, gaussian_window(), reinterpret_cast<float*>(ws + L.coef), L.cplane,
+                       reinterpret_cast<float*>(ws + L.ssum), valid, W, (long long)H * W,
+                       reinterpret_cast<unsigned int*>(ws + L.scnt));
+    if (int e = check_launch("ssim_valid_forward")) return e;
+  }
+  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(COMBINE_VALID_THREADS), 0, st,
+                     pw ? reinterpret_cast<const float*>(ws + L.V.psum) : nullptr,
+                     pw ? reinterpret_cast<const unsigned int*>(ws + L.V.pcnt) : nullptr, L.V.nb, base_losses, km, out,
+                     reinterpret_cast<long long*>(ws + L.V.nn), ss ? reinterpret_cast<const float*>(ws + L.ssum) : nullptr,
+                     ss ? reinterpret_cast<const unsigned int*>(ws + L.scnt) : nullptr, L.nbs,
+                     ss ? reinterpret_cast<long long*>(ws + L.ns) : nullptr);
+  return check_launch("loss_menu_valid_combine");
+}
+
+extern "C" int jspsr_loss_menu_valid_ssim_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                                   int planes, int H, int W, int ssim_rule, const double* slot_weight,
+                                                   const float* grad_total, float* grad_pred, const void* workspace,
+                                                   jspsr_stream_t stream) {
+  if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
+      !dims_ok(planes, H, W))
+    return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: bad arguments");
+  if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: SSIM needs H, W >= 11");
+  const VsLayout L = vs_layout(terms, planes, H, W);
+  const char* ws = static_cast<const char*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  if (terms & (T_BERHU | T_BCE | T_NORM)) {
+    hipLaunchKernelGGL(menu_bwd_valid_kernel, dim3(L.V.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
+                       reinterpret_cast<const float*>(ws), reinterpret_cast<const long long*>(ws + L.V.nn), grad_total,
+                       slot_weight[S_BERHU], slot_weight[S_BCE], slot_weight[S_NORM], grad_pred);
+    if (int e = check_launch("loss_menu_valid_backward")) return e;
+  }
+  if (terms & T_SSIM) {
+    const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
+    hipLaunchKernelGGL(ssim_bwd_kernel<true>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
+                       reinterpret_cast<const float*>(ws + L.coef), L.cplane, H, W, L.Hm, L.Wm, tx, gaussian_window(),
+                       grad_total, 0.f, grad_pred, valid, reinterpret_cast<const long long*>(ws + L.ns), slot_weight[S_SSIM]);
+    if (int e = check_launch("ssim_valid_backward")) return e;
+  }
+  return JSPSR_OK;
+}
+
+// Per-tile SSIM of a batch of uncropped (B,1,H,W) tiles: the crop of `border` on every side (int(H * border) rows,
+// int(W * border) columns, as metrics.prepare) by index arithmetic, one forward launch over (tiles of the map, B) and a
+// finalize: out[b] = the mean over tile b's counted map elements (NaN where none), counts[b] = their number.
+extern "C" size_t jspsr_ssim_tiles_workspace_bytes(int B, int H, int W, double border, int same) {
+  if (!(border >= 0.0) || border >= 0.5 || !dims_ok(B, H, W)) return 0;
+  const int h = H - 2 * (int)((double)H * border), w = W - 2 * (int)((double)W * border);
+  if (h <= 0 || w <= 0 || (!same && (h < 11 || w < 11))) return 0;
+  const int Hm = same ? h : h - 10, Wm = same ? w : w - 10;
+  return 2 * al16((size_t)((Wm + ST - 1) / ST) * ((Hm + ST - 1) / ST) * B * 4);
+}
+
+extern "C" int jspsr_ssim_tiles_forward(const float* pred, const float* gt, const unsigned char* valid, int B, int H, int W,
+                                        double border, int same, const float* window11, float* out, int* counts,
+                                        void* workspace, jspsr_stream_t stream) {
+  if (!pred || !gt || !out || !counts || !workspace || !dims_ok(B, H, W))
+    return fail(JSPSR_EINVAL, "ssim_tiles_forward: bad arguments");
+  if (!(border >= 0.0) || border >= 0.5) return fail(JSPSR_EINVAL, "ssim_tiles_forward: border must be in [0, 0.5)");
+  const int bh = (int)((double)H * border), bw = (int)((double)W * border);       // int(h * border), metrics.prepare
+  const int h = H - 2 * bh, w = W - 2 * bw;
+  if (h <= 0 || w <= 0) return fail(JSPSR_EINVAL, "ssim_tiles_forward: nothing left after the border crop");
+  if (!same && (h < 11 || w < 11)) return fail(JSPSR_EINVAL, "ssim_tiles_forward: valid mode needs H, W >= 11 after the crop");
+  Win11 k = gaussian_window();
+  if (same && window11)
+    for (int i = 0; i < 11; ++i) k.w[i] = window11[i];
+  const int Hm = same ? h : h - 10, Wm = same ? w : w - 10;
+  const int tx = (Wm + ST - 1) / ST, ty = (Hm + ST - 1) / ST;
+  const size_t half = al16((size_t)tx * ty * B * 4);
+  float* part = static_cast<float*>(workspace);
+  unsigned int* pcnt = reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + half);
+  const long long o = (long long)bh * W + bw;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (same)
+    hipLaunchKernelGGL((ssim_fwd_kernel<true, true>), dim3(tx * ty, B), dim3(SN), 0, st, pred + o, gt + o, h, w, Hm, Wm, tx, k,
+                       nullptr, 0ll, part, valid ? valid + o : nullptr, W, (long long)H * W, pcnt);
+  else
+    hipLaunchKernelGGL((ssim_fwd_kernel<false, true>), dim3(tx * ty, B), dim3(SN), 0, st, pred + o, gt + o, h, w, Hm, Wm, tx, k,
+                       nullptr, 0ll, part, valid ? valid + o : nullptr, W, (long long)H * W, pcnt);
+  if (int e = check_launch("ssim_tiles_forward")) return e;
+  hipLaunchKernelGGL(ssim_tiles_finalize_kernel, dim3(B), dim3(64), 0, st, part, pcnt, tx * ty, out, counts);
+  return check_launch("ssim_tiles_finalize");
 }

@@ -40,9 +40,13 @@ def _sobel_pair(dtype):
     return torch.stack((gx, gy)).unsqueeze(1)
 
 
-def _ssim_torch(p, g, package):
+def _ssim_torch(p, g, package, valid=None):
     """metrics.ssim's two forms as torch operators (CPU tensors): "piq" valid 11x11 Gaussian (sigma 1.5), "local" the
-    reference's own window (metrics.local_window) with zero padding 5."""
+    reference's own window (metrics.local_window) with zero padding 5.
+    valid: a bool plane of p's shape -> (per-tile values (B,) fp32, counts (B,) int32) under the window rule of
+    `metrics.ssim_tiles`: p and g are zeroed at the invalid pixels, a map element counts iff an 11x11 box filter of the
+    invalid plane (the same padding: a padded tap is not a void) is 0 there, the mean is over the counted elements of each
+    tile and over its channels; NaN where the count is 0."""
     if package == "local":
         w, pad = M.local_window(), 5
     else:
@@ -54,10 +58,19 @@ def _ssim_torch(p, g, package):
     def filt(t):
         return F.conv2d(t, win, padding=pad, groups=C)
 
+    if valid is not None:
+        zero = torch.zeros_like(p)
+        p, g = torch.where(valid, p, zero), torch.where(valid, g, zero)
     mx, my = filt(p), filt(g)
     sxx, syy, sxy = filt(p * p) - mx * mx, filt(g * g) - my * my, filt(p * g) - mx * my
     c1, c2 = 0.01 ** 2, 0.03 ** 2
-    return (((2 * mx * my + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))).mean()
+    smap = ((2 * mx * my + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2))
+    if valid is None:
+        return smap.mean()
+    counted = F.conv2d((~valid).to(p.dtype), torch.ones(C, 1, 11, 11, dtype=p.dtype), padding=pad, groups=C) == 0
+    n = counted.sum((1, 2, 3))
+    total = torch.where(counted, smap, torch.zeros_like(smap)).sum((1, 2, 3))
+    return torch.where(n > 0, total / n.clamp_min(1), torch.full_like(total, float("nan"))).float(), n.to(torch.int32)
 
 
 def _masked_row(p, g, v, vmin, vmax, elev_log, sob):
@@ -140,10 +153,18 @@ class PerformanceMeter:
     ride in the same single copy as the rows, bit for bit (int32 viewed as fp32, not converted).  A column whose count is 0
     is NaN; get_score() averages each metric over the tiles whose count FOR THAT COLUMN is positive (as summary's online
     means average the scenes with N > 0) and raises ValueError naming a metric no tile has; worst() skips NaN rows.
-    Masked SSIM is not built: an SSIM entry in a masked meter raises NotImplementedError here.  An unmasked meter refuses
-    `valid=`."""
+    An SSIM entry in a masked meter raises NotImplementedError here unless ssim_valid="window" is given (K23; without
+    masked=True, or with another value, a ValueError): the SSIM column then comes from ONE `metrics.ssim_tiles` call per
+    SSIM entry for the whole batch (CPU tensors: `_ssim_torch(valid=)`), over the map elements whose 11x11 window holds no
+    void; counts() gains one column per SSIM entry after the three of `metrics.COUNT_COLUMNS` -- `count_names` names them
+    all -- in the same single copy, and get_score() averages SSIM over the tiles whose SSIM count is positive.  An
+    unmasked meter refuses `valid=` and keeps its per-sample SSIM calls."""
 
-    def __init__(self, metric_config, value_min, value_max, border=0.05, elev_log=True, masked=False):
+    def __init__(self, metric_config, value_min, value_max, border=0.05, elev_log=True, masked=False, ssim_valid=None):
+        if ssim_valid is not None and ssim_valid != "window":
+            raise ValueError(f"PerformanceMeter: ssim_valid must be None or 'window', got {ssim_valid!r}")
+        if ssim_valid is not None and not masked:
+            raise ValueError("PerformanceMeter: ssim_valid needs masked=True (an unmasked meter takes no validity plane)")
         self.config = {k: dict(v or {}) for k, v in dict(metric_config).items()}
         if not self.config:
             raise ValueError("PerformanceMeter: empty metric config")
@@ -157,16 +178,27 @@ class PerformanceMeter:
             for key, mine in (("border", self.border), ("min", self.vmin), ("max", self.vmax)):
                 if kw.get(key) is not None and float(kw[key]) != mine:
                     raise NotImplementedError(f"PerformanceMeter: metric {name!r} asks for {key} = {kw[key]}, the meter has {mine}")
-            if masked and isinstance(col, str):
+            if masked and isinstance(col, str) and ssim_valid is None:
                 raise NotImplementedError(f"PerformanceMeter: metric {name!r} in a masked meter: masked SSIM is not built")
             self.names.append(name)
             self.columns.append(col)
         self.masked = bool(masked)
+        self.ssim_valid = ssim_valid
+        # the count column each metric divides by: one of metrics.COUNT_COLUMNS, or the SSIM entry's own, appended after them
+        self.count_names = list(M.COUNT_COLUMNS)
+        self._count_col = []
+        for name, col in zip(self.names, self.columns):
+            if isinstance(col, str):
+                self._count_col.append(len(self.count_names))
+                self.count_names.append(f"N_{name}")
+            else:
+                self._count_col.append(M.COUNT_OF_COLUMN[col])
         self.reset()
 
     def clone(self):
         """A fresh meter with the same configuration (the reference builds a second one for the input's score)."""
-        return PerformanceMeter(self.config, self.vmin, self.vmax, self.border, self.elev_log, masked=self.masked)
+        return PerformanceMeter(self.config, self.vmin, self.vmax, self.border, self.elev_log, masked=self.masked,
+                                ssim_valid=self.ssim_valid)
 
     def reset(self):
         self._rows, self._meta, self._host = [], [], None
@@ -192,8 +224,22 @@ class PerformanceMeter:
                 raise ValueError(f"PerformanceMeter.update: valid must be a {tuple(pred.shape)} bool / uint8 plane on {pred.device}")
             score = M.batch_scores if pred.is_cuda else _scores_torch
             full, counts = score(pred, gt, self.vmin, self.vmax, self.border, self.elev_log, valid=valid)
-            self._rows.append(torch.stack([full[:, c] for c in self.columns], dim=1))
-            self._counts.append(counts)
+            cols, extra = [], []
+            for c in self.columns:
+                if isinstance(c, str):        # SSIM (ssim_valid="window"): every tile of the batch from one call
+                    if pred.is_cuda:
+                        vals, cnt = M.ssim_tiles(pred, gt, c, self.border, valid=valid)
+                    else:
+                        H, W = pred.shape[-2:]
+                        bh, bw = int(H * self.border), int(W * self.border)
+                        pp, gg = M.prepare(pred.float(), gt.float(), self.border)
+                        vals, cnt = _ssim_torch(pp, gg, c, valid=valid[..., bh:H - bh, bw:W - bw] != 0)
+                    cols.append(vals)
+                    extra.append(cnt)
+                else:
+                    cols.append(full[:, c])
+            self._rows.append(torch.stack(cols, dim=1))
+            self._counts.append(torch.cat([counts] + [e.reshape(-1, 1) for e in extra], dim=1) if extra else counts)
             self._meta.extend(meta if meta is not None else [None] * B)
             self._host = self._host_counts = None
             return
@@ -226,9 +272,9 @@ class PerformanceMeter:
         return self._rows[0]
 
     def _device_counts(self):
-        """(N, 3) int32 on the device the rows were made on (masked meters); no host synchronisation."""
+        """(N, len(count_names)) int32 on the device the rows were made on (masked meters); no host synchronisation."""
         if not self._counts:
-            return torch.empty((0, 3), dtype=torch.int32)
+            return torch.empty((0, len(self.count_names)), dtype=torch.int32)
         if len(self._counts) > 1:
             self._counts = [torch.cat(self._counts)]
         return self._counts[0]
@@ -238,8 +284,8 @@ class PerformanceMeter:
             _fetch([self], None)
 
     def counts(self):
-        """(N_tiles, 3) int32 numpy array, columns `metrics.COUNT_COLUMNS`, of a masked meter: the same single copy as the
-        table's."""
+        """(N_tiles, len(count_names)) int32 numpy array of a masked meter, columns `count_names`: the three of
+        `metrics.COUNT_COLUMNS`, then one per SSIM entry (ssim_valid="window"); the same single copy as the table's."""
         if not self.masked:
             raise ValueError("PerformanceMeter.counts: the meter was not built with masked=True")
         self._fetch_own()
@@ -263,7 +309,7 @@ class PerformanceMeter:
             return {name: sum(float(v) for v in t[:, j]) / t.shape[0] for j, name in enumerate(self.names)}
         counts, out = self.counts(), {}
         for j, name in enumerate(self.names):
-            keep = counts[:, M.COUNT_OF_COLUMN[self.columns[j]]] > 0
+            keep = counts[:, self._count_col[j]] > 0
             if not keep.any():
                 raise ValueError(f"PerformanceMeter.get_score: no tile has a valid pixel for metric {name!r}")
             out[name] = sum(float(v) for v in t[keep, j]) / int(keep.sum())

@@ -149,10 +149,17 @@ def _slot(name):
     return s
 
 
-class _Spec:
-    """Host-side plan of one criterion: keys in config order, their slots and weights, the per-slot weight sums."""
+SSIM_RULES = {"window": 1}      # ssim_valid -> ssim_rule of jspsr_loss_menu_valid_ssim_*
 
-    def __init__(self, weights):
+
+class _Spec:
+    """Host-side plan of one criterion: keys in config order, their slots and weights, the per-slot weight sums, and the
+    rule SSIM follows over a validity plane (None: not accepted)."""
+
+    def __init__(self, weights, ssim_valid=None):
+        if ssim_valid is not None and ssim_valid not in SSIM_RULES:
+            raise ValueError(f"loss: ssim_valid must be None or one of {sorted(SSIM_RULES)}, got {ssim_valid!r}")
+        self.ssim_valid = ssim_valid
         self.keys = list(weights)
         self.slots = [_slot(k) for k in self.keys]
         self.weights = [float(weights[k]) for k in self.keys]
@@ -227,7 +234,7 @@ class _MenuLoss(torch.autograd.Function):
 
 class _MenuLossValid(torch.autograd.Function):
     """_MenuLoss over the elements `valid` keeps (jspsr_loss_valid_* for the L1 / L2 / Grad part, jspsr_loss_menu_valid_*
-    for the rest, K19)."""
+    for the rest, K19; jspsr_loss_menu_valid_ssim_* when SSIM is among the terms, K23)."""
 
     @staticmethod
     def forward(ctx, pred, gt, valid, spec):
@@ -242,12 +249,21 @@ class _MenuLossValid(torch.autograd.Function):
             _lib.check(lib.jspsr_loss_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), *spec.base_w,
                                                     base.data_ptr(), bws.data_ptr(), P, H, W, _stream()),
                        "jspsr_loss_valid_forward")
-        ws = torch.empty(lib.jspsr_loss_menu_valid_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
         out = torch.empty(len(spec.keys) + 1, dtype=torch.float32, device=pred.device)
-        _lib.check(lib.jspsr_loss_menu_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
-                                                     len(spec.keys), spec.c_slots, spec.c_weights,
-                                                     base.data_ptr() if base is not None else None, out.data_ptr(),
-                                                     ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_forward")
+        if 6 in spec.slots:
+            rule = SSIM_RULES[spec.ssim_valid]
+            ws = torch.empty(lib.jspsr_loss_menu_valid_ssim_workspace_bytes(spec.terms, P, H, W, rule), dtype=torch.uint8,
+                             device=pred.device)
+            _lib.check(lib.jspsr_loss_menu_valid_ssim_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P,
+                                                              H, W, rule, len(spec.keys), spec.c_slots, spec.c_weights,
+                                                              base.data_ptr() if base is not None else None, out.data_ptr(),
+                                                              ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_ssim_forward")
+        else:
+            ws = torch.empty(lib.jspsr_loss_menu_valid_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
+            _lib.check(lib.jspsr_loss_menu_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
+                                                         len(spec.keys), spec.c_slots, spec.c_weights,
+                                                         base.data_ptr() if base is not None else None, out.data_ptr(),
+                                                         ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_forward")
         ctx.save_for_backward(pred_c, gt_c, valid, ws, bws)
         ctx.spec = spec
         ctx.mark_non_differentiable(gt)
@@ -269,9 +285,15 @@ class _MenuLossValid(torch.autograd.Function):
                        "jspsr_loss_valid_backward")
         else:
             gp = torch.zeros_like(pred)
-        _lib.check(lib.jspsr_loss_menu_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
-                                                      spec.c_slot_w, g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
-                   "jspsr_loss_menu_valid_backward")
+        if 6 in spec.slots:
+            _lib.check(lib.jspsr_loss_menu_valid_ssim_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H,
+                                                               W, SSIM_RULES[spec.ssim_valid], spec.c_slot_w, g.data_ptr(),
+                                                               gp.data_ptr(), ws.data_ptr(), _stream()),
+                       "jspsr_loss_menu_valid_ssim_backward")
+        else:
+            _lib.check(lib.jspsr_loss_menu_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
+                                                          spec.c_slot_w, g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
+                       "jspsr_loss_menu_valid_backward")
         return gp, None, None, None
 
 
@@ -281,7 +303,7 @@ def _evaluate(spec, pred, gt, valid=None):
     spec.check(pred, gt)
     n = len(spec.keys)
     if valid is not None:
-        if 6 in spec.slots:
+        if 6 in spec.slots and spec.ssim_valid is None:
             raise NotImplementedError("loss SSIM: a validity plane is not built (an 11x11-window validity rule is a feature "
                                       "of its own); drop SSIM from the criterion or pass valid=None")
         valid = _plane(pred, valid)
@@ -295,10 +317,10 @@ def _evaluate(spec, pred, gt, valid=None):
 class LossTerm(torch.nn.Module):
     """One term of the menu on its own, like the module the reference's get_loss returns: (pred, gt) -> 0-d tensor."""
 
-    def __init__(self, name):
+    def __init__(self, name, ssim_valid=None):
         super().__init__()
         self.name = str(name)
-        self.spec = _Spec({self.name: 1.0})
+        self.spec = _Spec({self.name: 1.0}, ssim_valid)
 
     def forward(self, pred, gt, valid=None):
         return _evaluate(self.spec, pred, gt, valid)[1]
@@ -307,7 +329,7 @@ class LossTerm(torch.nn.Module):
         return f"{self.__class__.__name__}({self.name}), fused HIP"
 
 
-def get_loss(name):
+def get_loss(name, ssim_valid=None):
     """The reference's get_loss (losses/loss_schemes.py:6-33) on the device: l1, l2 / mse, vanilla / bce, edge / grad,
     berhu, norm, ssim, case-insensitively.
 
@@ -323,9 +345,10 @@ def get_loss(name):
         piq's public source, UNPINNED against piq itself (not installed here): valid 11x11 Gaussian window (sigma 1.5),
         c1 = 0.01^2, c2 = 0.03^2, the mean of the map over every element of every plane.  piq's input-range assertion
         (a host sync) is not reproduced.  ValueError for H or W < 11.
-    Unknown names raise NotImplementedError("Undefined loss: <name>")."""
+    Unknown names raise NotImplementedError("Undefined loss: <name>").
+    ssim_valid: the rule SSIM follows when the call is given a validity plane (see `Criterion`); None refuses one."""
     _slot(name)
-    return LossTerm(name)
+    return LossTerm(name, ssim_valid)
 
 
 class Criterion(torch.nn.Module):
@@ -339,14 +362,18 @@ class Criterion(torch.nn.Module):
     whole call: L1, L2, BerHu (th = 0.6 max_valid |d|), BCE and Norm sum over the valid elements and divide by N; a Sobel
     output counts iff its nine replicate-clamped taps are valid, Grad = sum_counted (|gx| + |gy|) / (2 N_g).  N = 0 or N_g =
     0 gives value and gradient 0, not NaN.  N and N_g stay on the device, so the masked pair captures in a graph as well.
-    An all-ones plane gives the bits of valid=None.  SSIM with a plane raises NotImplementedError before any launch."""
+    An all-ones plane gives the bits of valid=None.  SSIM with a plane raises NotImplementedError before any launch,
+    unless the criterion was built with ssim_valid="window" (K23; any other value but None is a ValueError here): an
+    element of the (H-10) x (W-10) SSIM map then counts iff all 121 pixels under its window are valid, SSIM = 1 -
+    sum_counted S / N_s over the counted elements of the whole call, 0 (and gradient 0) when N_s = 0; N_s stays on the
+    device as well, and the all-ones plane still gives the bits of valid=None.  ssim_valid changes nothing without a plane."""
 
-    def __init__(self, weights, single=False):
+    def __init__(self, weights, single=False, ssim_valid=None):
         super().__init__()
         if not weights:
             raise ValueError("get_criterion: empty loss config")
         self.single = single
-        self.spec = _Spec(weights)
+        self.spec = _Spec(weights, ssim_valid)
         self.out = {}
 
     def forward(self, pred, gt, valid=None):
@@ -365,12 +392,13 @@ class Criterion(torch.nn.Module):
         return f"MultiLoss:: {self.spec.keys}, {self.spec.weights}, fused HIP (jspsr_loss_menu_forward/backward)"
 
 
-def get_criterion(config):
+def get_criterion(config, ssim_valid=None):
     """utils/common_config.py:209-233: one key -> that term alone with weight 1 (whatever the configured weight),
     returning {name: v, "Total": v}; several keys -> the weighted sum, {keys in config order..., "Total"}.
-    The default {"L1": 1, "L2": 1, "Grad": 0.1} runs exactly MultiLoss(1, 1, 0.1)'s fused pair."""
+    The default {"L1": 1, "L2": 1, "Grad": 0.1} runs exactly MultiLoss(1, 1, 0.1)'s fused pair.
+    ssim_valid: passed to `Criterion` ("window": SSIM accepts a validity plane)."""
     config = dict(config)
     if len(config) == 1:
         (name, _), = config.items()
-        return Criterion({name: 1.0}, single=True)
-    return Criterion(config)
+        return Criterion({name: 1.0}, single=True, ssim_valid=ssim_valid)
+    return Criterion(config, ssim_valid=ssim_valid)

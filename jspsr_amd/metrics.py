@@ -197,6 +197,55 @@ def ssim(pred, gt, package="piq"):
     return out[0]
 
 
+def ssim_tiles(pred, gt, package="piq", border=0.0, valid=None):
+    """SSIM of every tile of a batch of UNCROPPED (B,1,H,W) GPU tiles in one call (K23, jspsr_ssim_tiles_forward: two
+    launches whatever B is) -> (B,) fp32 device tensor: row b is ``ssim(*prepare(pred[b:b+1], gt[b:b+1], border),
+    package)``, bit for bit; the crop is index arithmetic, nothing is copied.  No host synchronisation.
+
+    valid: a (B,1,H,W) bool or uint8 plane on pred's device (nonzero = valid) -> (values, counts): a map element counts iff
+    every pixel of its 11x11 window that lies inside the cropped tile is valid ("piq": the whole window lies inside;
+    "local": taps in the zero padding are padding, not voids); values[b] is the mean of the SSIM map over tile b's counted
+    elements, whatever pred and gt hold at the invalid pixels (they are read as 0 behind a select), NaN where the (B,)
+    int32 device tensor `counts` is 0.  An all-ones plane gives the bits of valid=None."""
+    global _LOCAL_WINDOW
+    if package not in ("piq", "local"):
+        raise NotImplementedError(f"ssim_tiles: package {package!r} (supported: 'piq', 'local')")
+    if not pred.is_cuda or pred.shape != gt.shape or pred.dim() != 4 or pred.shape[1] != 1:
+        raise ValueError(f"ssim_tiles: equal (B,1,H,W) GPU tensors, got {tuple(pred.shape)} {tuple(gt.shape)}")
+    B, _, H, W = pred.shape
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.shape != pred.shape or valid.dtype not in (torch.bool, torch.uint8) or \
+                valid.device != pred.device:
+            raise ValueError(f"ssim_tiles: valid must be a {tuple(pred.shape)} bool / uint8 plane on {pred.device}, got "
+                             f"{tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} "
+                             f"{getattr(valid, 'dtype', None)} on {getattr(valid, 'device', None)}")
+    same = package == "local"
+    border = float(border)
+    if not 0.0 <= border < 0.5:
+        raise ValueError(f"ssim_tiles: border must be in [0, 0.5), got {border}")
+    h, w = H - 2 * int(H * border), W - 2 * int(W * border)
+    if not same and (h < 11 or w < 11):
+        raise ValueError(f"ssim_tiles (piq): needs H, W >= 11 after the crop, got {(h, w)}")
+    win = None
+    if same:
+        if _LOCAL_WINDOW is None:
+            _LOCAL_WINDOW = (ctypes.c_float * 11)(*local_window().tolist())
+        win = _LOCAL_WINDOW
+    p, g = pred.float().contiguous(), gt.float().contiguous()
+    v = None
+    if valid is not None:
+        v = valid.contiguous()
+        v = v.view(torch.uint8) if v.dtype == torch.bool else v
+    lib = _lib.load()
+    ws = torch.empty(max(lib.jspsr_ssim_tiles_workspace_bytes(B, H, W, border, int(same)), 16), dtype=torch.uint8, device=pred.device)
+    out = torch.empty(B, dtype=torch.float32, device=pred.device)
+    counts = torch.empty(B, dtype=torch.int32, device=pred.device)
+    _lib.check(lib.jspsr_ssim_tiles_forward(p.data_ptr(), g.data_ptr(), v.data_ptr() if v is not None else None, B, H, W, border,
+                                            int(same), win, out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), "jspsr_ssim_tiles_forward")
+    return (out, counts) if valid is not None else out
+
+
 class Meter:
     """Running per-sample averages of all five scores (what PerformanceMeter.get_score reports,
     evaluation/evaluate_utils.py:26-47).  Accumulates on the device; one host sync in ``scores()``.
