@@ -646,7 +646,7 @@ int jspsr_summary_forward(const float* const* cands, const long long* cand_numel
                           int n_segments, long long total, long long total_chunks, double value_max, float* out,
                           void* workspace, jspsr_stream_t stream);
 
-/* ---- K13 (ABI v23): whole-scene inference, the steps either side of the forward (csrc/scene.hip) ----------
+/* ---- K13 (ABI v23): whole-scene inference, the steps either side of the forward (csrc/scene_prepare.hip, scene.hip)
  * What upscale_dem does around the model call (utils/utils.py:1556-1654): add_padding (:1501-1520) and ToTensor
  * (data/data_utils.py:217-312) before it, remove_padding (:1523-1531) after it -- and, for metres, the clip, descale_data
  * and + base of save_prediction_to_disk (evaluation/evaluate_utils.py:242-271) -- each side ONE launch for a batch of B
@@ -682,7 +682,7 @@ int jspsr_scene_prepare(const void* const* src, const long long* src_bytes, floa
 int jspsr_scene_finish(int dtype, const void* pred, float* out, const int* samples, int B, int Hp, int Wp, int top, int left,
                        int H, int W, int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
 
-/* ---- K14 (ABI v24): whole-scene self-ensemble over the flips and quarter turns (csrc/scene_tta.hip) --------
+/* ---- K14 (ABI v24): whole-scene self-ensemble over the flips and quarter turns (csrc/scene_prepare.hip, scene_tta.hip)
  * The reference has no self-ensemble.  What these two replace is the host work a user of K13 needs for one: np.rot90 /
  * fliplr / flipud of every decoded raster (the order of RandomFlipRotate90, data/data_utils.py:26-28), a store and a
  * jspsr_scene_prepare + jspsr_scene_finish pair per orientation, and the inverse transforms and the mean in numpy.
@@ -726,7 +726,7 @@ int jspsr_scene_prepare_d4(const void* const* src, const long long* src_bytes, f
 int jspsr_scene_finish_mean(const jspsr_tta_variant* variants, int K, float* out, const int* samples, int B, int H, int W,
                             int metres, int elev_log, double elev_min, double elev_max, jspsr_stream_t stream);
 
-/* ---- K15 (ABI v25): tiled whole-scene inference, scenes of any size (csrc/scene_tiles.hip) ------------------
+/* ---- K15 (ABI v25): tiled whole-scene inference, scenes of any size (csrc/scene_prepare.hip, scene_tiles.hip)
  * The reference's evaluation protocol -- tiles of the training size, linear ramps in the overlaps (TileCrop,
  * data/data_utils.py:87-194; gen_weight_row / col + merge_dem, utils/utils.py:802-967) -- for a cover of any H x W scene by
  * n_y x n_x tiles of kh x kw (jspsr_amd/infer.py: plan_cover makes the origins and the weights).  What these two replace
@@ -769,7 +769,7 @@ int jspsr_scene_merge_windows(int dtype, const void* tiles, const float* wy, con
                               int kw, int H, int W, int metres, int elev_log, double elev_min, double elev_max,
                               jspsr_stream_t stream);
 
-/* ---- K16 (ABI v25, additive): the self-ensemble per window of a tiled scene (csrc/scene_tiles_tta.hip) --------
+/* ---- K16 (ABI v25, additive): the self-ensemble per window of a tiled scene (csrc/scene_prepare.hip) ----------
  * jspsr_scene_prepare_windows_d4: jspsr_scene_prepare_windows composed with K14's D4 map, a window and a code per sample.
  *   What it replaces is jspsr_scene_prepare_windows followed by a flip / rot90 of every input tensor of every sample.
  *   samples device int32 [B][5] = {scene, base elevation (fp32 bit pattern), y0, x0, code}, code = rot90 * 4 + flip_lr * 2 +

@@ -50,7 +50,7 @@ __device__ __forceinline__ void d4_source(int code, int k, int i, int j, int& sy
   }
 }
 
-// ToTensor, per kind (data_utils.py:217-312): scale_dem / transform of totensor.h, shared with K13 (scene.hip)
+// ToTensor, per kind (data_utils.py:217-312): scale_dem / transform of totensor.h, shared with K13-K16 (scene_prepare.hip)
 
 __global__ __launch_bounds__(256) void batch_kernel(BatchArgs a, int tiles_x) {
   __shared__ unsigned int lds[kTile * kPitch];

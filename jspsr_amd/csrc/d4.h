@@ -1,4 +1,4 @@
-// The D4 index maps of K14 (scene_tta.hip) and K16 (scene_tiles_tta.hip): code = rot90 * 4 + flip_lr * 2 + flip_ud, the
+// The D4 index maps of K14 and K16 (scene_prepare.hip, scene_tta.hip): code = rot90 * 4 + flip_lr * 2 + flip_ud, the
 // transformed raster flipud?(fliplr?(rot90(m, rot90))), W x H for an odd rot90.  Integers only: the same map in every
 // translation unit that includes this.
 #pragma once

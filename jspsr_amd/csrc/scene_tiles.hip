@@ -1,96 +1,22 @@
-// K15 -- tiled whole-scene inference, the steps either side of the forwards (jspsr_amd/infer.py: plan_cover, predict_scenes):
-//   jspsr_scene_prepare_windows   kh x kw windows of the raw HWC scene store -> the model's NCHW inputs (ToTensor per kind),
-//                                 the windows of a batch from any scenes of the store, ONE launch
+// K15 -- tiled whole-scene inference, the step after the forwards (jspsr_amd/infer.py: plan_cover, predict_scenes; the step
+// before them, jspsr_scene_prepare_windows, is in scene_prepare.hip):
 //   jspsr_scene_merge_windows     the predictions of the cover of S equally shaped scenes -> S metre rasters: per tile
 //                                 clamp -> descale_data -> + base, then the feather merge with the cover's ramp weights
 //                                 (TileCrop / merge_dem's protocol, utils/utils.py:802-967, for any cover), ONE launch
-// Both are HBM streaming with K13's access pattern (csrc/scene.hip): no LDS, a thread makes four consecutive pixels of a
-// row, a wave writes 1 KiB runs (16-byte stores when the row length is a multiple of 4 and the plane is 16-byte aligned).
-// prepare reads 22 B per window pixel and writes 76 B (image + mask); merge reads 4 B (2 B for bf16) per covered tile
-// pixel -- one tile inside, two in a seam, four at a seam crossing -- and writes 4 B.  The merge is a gather: every output
-// pixel sums its own tiles in row-major order, no atomics, the same bits on every run.
+// HBM streaming with jspsr_scene_finish's access pattern (csrc/scene.hip): no LDS, a thread makes four consecutive pixels of
+// a row, a wave writes 1 KiB runs (16-byte stores when the row length is a multiple of 4 and the output is 16-byte aligned).
+// It reads 4 B (2 B for bf16) per covered tile pixel -- one tile inside, two in a seam, four at a seam crossing -- and
+// writes 4 B.  The merge is a gather: every output pixel sums its own tiles in row-major order, no atomics, the same bits on
+// every run.
 //
-// All offsets into the store, the tile buffer and the outputs are 64-bit: a 37 000 x 37 000 scene's image plane passes
-// 2^31 bytes, and so does its cover.
-#include "common.h"
-#include "totensor.h"
+// All offsets into the tile buffer and the output are 64-bit: the cover of a 37 000 x 37 000 scene passes 2^31 bytes.
+#include "scene_prepare.h"
 
 #include <cmath>
 
 namespace {
 
 using namespace jspsr;
-
-struct KindDesc {
-  const unsigned char* src;   // scene store of this kind (HWC, C channels of 1 or 4 bytes); NULL for COORD
-  long long src_bytes;
-  float* out;                 // [B][cpitch][kh][kw]; this kind's channels start at coff
-  int kind, C, coff, cpitch;
-  int vec;                    // 16-byte stores: kw % 4 == 0 and out 16-byte aligned
-};
-
-struct WindowArgs {
-  KindDesc d[kKinds];         // the present kinds, packed (gridDim.y of them)
-  const long long* scenes;    // [n_scenes][3] {pixel offset, H, W}
-  const int* samples;         // [B][4] {scene, base (fp32 bits), y0, x0}
-  int n_scenes, B, kh, kw, flags, mask_div;
-  float lo, span;             // fp32(elev_min), fp32(elev_max - elev_min)
-  double log_span;            // log(elev_max - elev_min)
-};
-
-int blocks_for(long long n) {
-  long long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
-__global__ __launch_bounds__(256) void scene_prepare_windows_kernel(WindowArgs a) {
-  const KindDesc& d = a.d[blockIdx.y];
-  const int Wq = (a.kw + 3) >> 2;                                     // quads of a window row
-  const long long total = (long long)a.B * a.kh * Wq;
-  const int es = d.kind == LR_DEM ? 4 : 1;                            // bytes per channel value
-  const int pxb = d.C * es;                                           // bytes per pixel
-  const size_t plane = (size_t)a.kh * a.kw;
-  const float nan = __int_as_float(0x7fc00000);
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int x = (int)(i % Wq) * 4;
-    const long long r = i / Wq;
-    const int y = (int)(r % a.kh), b = (int)(r / a.kh);
-    const int n = min(4, a.kw - x);
-    const int scene = a.samples[4 * b];
-    const float base = __int_as_float(a.samples[4 * b + 1]);
-    const long long sy = (long long)a.samples[4 * b + 2] + y;         // source row; 64-bit: y0 is the caller's
-    const long long sx0 = (long long)a.samples[4 * b + 3] + x;
-    long long off = 0, H = 0, W = 0;
-    bool ok = scene >= 0 && scene < a.n_scenes;
-    if (ok) {
-      off = a.scenes[scene * 3]; H = a.scenes[scene * 3 + 1]; W = a.scenes[scene * 3 + 2];
-      ok = off >= 0 && H > 0 && W > 0 && (d.kind == COORD ? H > 1 && W > 1 : (off + H * W) * pxb <= d.src_bytes);
-    }
-    ok = ok && sy >= 0 && sy < H;
-    bool okp[4];
-    const unsigned char* p[4];
-    for (int q = 0; q < 4; ++q) {
-      const long long sx = sx0 + q;
-      okp[q] = ok && sx >= 0 && sx < W;
-      p[q] = okp[q] && d.kind != COORD ? d.src + (off + sy * W + sx) * pxb : nullptr;
-    }
-    float* o = d.out + ((size_t)b * d.cpitch + d.coff) * plane + (size_t)y * a.kw + x;
-    for (int c = 0; c < d.C; ++c, o += plane) {
-      float v[4];
-      for (int q = 0; q < 4; ++q) v[q] = okp[q] ? transform(d.kind, c, p[q] + c * es, base, (int)sy, (int)(sx0 + q), H, W, a) : nan;
-      if (d.vec) {
-        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-        for (int q = 0; q < n; ++q) o[q] = v[q];
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float load_pred(const void* p, size_t i, int bf16) {
-  if (bf16) return __uint_as_float((unsigned int)static_cast<const unsigned short*>(p)[i] << 16);
-  return static_cast<const float*>(p)[i];
-}
 
 struct MergeArgs {
   const void* tiles;          // [S][n_y * n_x][kh][kw], fp32 or bf16
@@ -107,7 +33,7 @@ struct MergeArgs {
 };
 
 // out[s][y][x] = sum over the (at most 2 x 2) tiles with non-zero weights there, row-major, of (m * wx) * wy; m the tile
-// value in metres -- scene_finish_kernel's expressions (csrc/scene.hip) -- or as it is.  The sum is scenes_assemble_kernel's
+// value in metres (to_metres) or as it is.  The sum is scenes_assemble_kernel's
 // (csrc/summary.hip): acc starts at 0, every product and sum rounded on its own.
 __global__ __launch_bounds__(256) void scene_merge_windows_kernel(MergeArgs a) {
   const int Wq = (a.W + 3) >> 2;
@@ -153,11 +79,7 @@ __global__ __launch_bounds__(256) void scene_merge_windows_kernel(MergeArgs a) {
           if (jx[w] < 0 || wx[w] == 0.f) continue;                     // a tile of weight zero is not read
           const size_t t = ((size_t)s * a.n_y + (ty0 + u)) * a.n_x + (tx0 + w);
           float m = load_pred(a.tiles, t * tile + (size_t)jy[u] * a.kw + jx[w], a.bf16);
-          if (a.metres) {
-            m = m < 0.f ? 0.f : (m > 1.f ? 1.f : m);
-            m = a.elev_log ? __fadd_rn(expf(__fmul_rn(m, a.log_span)), a.lo) : __fadd_rn(__fmul_rn(m, a.span), a.lo);
-            m = __fadd_rn(m, base);
-          }
+          if (a.metres) m = to_metres(m, a.elev_log, a.lo, a.span, a.log_span, base);
           acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(m, wx[w]), wy[u]));
         }
       }
@@ -173,53 +95,6 @@ __global__ __launch_bounds__(256) void scene_merge_windows_kernel(MergeArgs a) {
 }
 
 }  // namespace
-
-extern "C" int jspsr_scene_prepare_windows(const void* const* src, const long long* src_bytes, float* const* out,
-                                           const int* channels, const int* coff, const int* cpitch, const long long* scenes,
-                                           int n_scenes, const int* samples, int B, int kh, int kw, int flags, double elev_min,
-                                           double elev_max, int mask_div, jspsr_stream_t stream) {
-  if (!src || !src_bytes || !out || !channels || !coff || !cpitch || !scenes || !samples || n_scenes <= 0 || B <= 0 || kh <= 0 ||
-      kw <= 0 || !(elev_max > elev_min) || mask_div <= 0 || (flags & ~JSPSR_BATCH_FLAGS))
-    return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: bad arguments");
-  if ((flags & JSPSR_BATCH_IMAGE_11) && (flags & JSPSR_BATCH_IMAGE_255))
-    return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: image range [-1, 1] and [0, 255] together");
-  if (out[HR_DEM]) return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: kind 1 (hr_dem) is not an input of the model");
-  if (!jspsr::aligned4(samples) || (reinterpret_cast<uintptr_t>(scenes) & 7u))
-    return jspsr::fail(JSPSR_EALIGN, "scene_prepare_windows: tables not aligned to their element size");
-  WindowArgs a{};
-  int nk = 0;
-  for (int kind = 0; kind < kKinds; ++kind) {
-    if (!out[kind]) continue;
-    const int C = channels[kind];
-    const int need = kind == COORD ? 2 : (kind == IMAGE || kind == MASK) ? -1 : 1;
-    if (C <= 0 || C > kMaxC || (need > 0 && C != need) || coff[kind] < 0 || cpitch[kind] < coff[kind] + C)
-      return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: kind %d: bad channels (%d, offset %d, pitch %d)", kind, C, coff[kind],
-                         cpitch[kind]);
-    if (!jspsr::aligned4(out[kind])) return jspsr::fail(JSPSR_EALIGN, "scene_prepare_windows: kind %d: output not 4-byte aligned", kind);
-    if (kind != COORD) {
-      if (!src[kind] || src_bytes[kind] <= 0)
-        return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: kind %d: null or empty store", kind);
-      if (!jspsr::aligned4(src[kind])) return jspsr::fail(JSPSR_EALIGN, "scene_prepare_windows: kind %d: store not 4-byte aligned", kind);
-    }
-    a.d[nk++] = KindDesc{static_cast<const unsigned char*>(kind == COORD ? nullptr : src[kind]), kind == COORD ? 0 : src_bytes[kind],
-                         out[kind], kind, C, coff[kind], cpitch[kind], (kw & 3) == 0 && jspsr::aligned16(out[kind])};
-  }
-  if (nk == 0) return jspsr::fail(JSPSR_EINVAL, "scene_prepare_windows: no output");
-  a.scenes = scenes;
-  a.samples = samples;
-  a.n_scenes = n_scenes;
-  a.B = B;
-  a.kh = kh;
-  a.kw = kw;
-  a.flags = flags;
-  a.mask_div = mask_div;
-  a.lo = (float)elev_min;                                   // the Python numbers, as numpy casts them against fp32 arrays
-  a.span = (float)(elev_max - elev_min);
-  a.log_span = log(elev_max - elev_min);
-  const long long items = (long long)B * kh * ((kw + 3) / 4);
-  hipLaunchKernelGGL(scene_prepare_windows_kernel, dim3(blocks_for(items), nk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return jspsr::check_launch("scene_prepare_windows");
-}
 
 extern "C" int jspsr_scene_merge_windows(int dtype, const void* tiles, const float* wy, const float* wx, const int* lo_y,
                                          const int* lo_x, const int* oy, const int* ox, const int* samples, float* out, int S,

@@ -1,4 +1,4 @@
-// ToTensor's per-kind arithmetic (data/data_utils.py:217-312), shared by K9 (batch.hip) and K13 (scene.hip) so that both
+// ToTensor's per-kind arithmetic (data/data_utils.py:217-312), shared by K9 (batch.hip) and K13-K16 (scene_prepare.hip) so that all
 // give the same bits.  Every operation is rounded on its own: the translation units that include this are built with
 // -ffp-contract=off (csrc/Makefile).
 //

@@ -1,4 +1,4 @@
-"""Whole-scene inference on the device (K13, csrc/scene.hip): raw rasters in, metres out.
+"""Whole-scene inference on the device (K13, csrc/scene_prepare.hip, scene.hip): raw rasters in, metres out.
 
 The reference's `upscale_dem` (utils/utils.py:1556-1654) pads a decoded scene to a power of two with a mirrored border
 (`cal_pad` / `add_padding`, :1501-1553), runs `ToTensor` (data/data_utils.py:217-312) on every raster, calls the model and
@@ -16,12 +16,12 @@ and nothing else: all policy is host code.  `finish` reads the window back and, 
 `metrics.descale_data` -> `+ base`, the bits of `summary.compose_scene` on a single uncropped tile.  `upscale_dem` keeps
 the reference's own contract on top of the two.
 
-Self-ensemble (K14, csrc/scene_tta.hip): `predict_scenes(..., tta="d4")` averages the predictions over the four quarter
+Self-ensemble (K14, csrc/scene_prepare.hip, scene_tta.hip): `predict_scenes(..., tta="d4")` averages the predictions over the four quarter
 turns and their mirror images.  `prepare_d4` transforms every raster of a sample on the device BEFORE the padding (the
 mirror border is not symmetric), one launch per rot90 parity; `finish_mean` carries up to eight predictions back, averages
 them in fp32 in a fixed order and converts to metres, one launch.
 
-Tiled inference (K15, csrc/scene_tiles.hip): `predict_scenes(..., tile=512, overlap=64, trim=16)` covers every scene that
+Tiled inference (K15, csrc/scene_prepare.hip, scene_tiles.hip): `predict_scenes(..., tile=512, overlap=64, trim=16)` covers every scene that
 is larger than the tile with equal windows (`cover.plan_cover`), gathers them straight from the store (`prepare_windows`,
 windows of different scenes share a batch), and merges the predictions with the cover's ramp weights in metres
 (`merge_windows`, one launch per group of equally shaped scenes).  Activation memory then follows batch_size x tile^2, not
@@ -29,7 +29,7 @@ the scene.  This is the reference's validation protocol -- per-tile channel-gate
 linear ramps over the overlaps -- continued to any scene; it is not an exact decomposition of the monolithic forward
 (`tiling.py` is).
 
-Tiled self-ensemble (K16, csrc/scene_tiles_tta.hip): `predict_scenes(..., tile=512, window_tta="d4")` keeps the upright cover
+Tiled self-ensemble (K16, csrc/scene_prepare.hip): `predict_scenes(..., tile=512, window_tta="d4")` keeps the upright cover
 and runs every WINDOW in each orientation: `prepare_windows_d4` gathers and transforms in one launch per rot90 parity,
 `mean_windows` (K14's finish_mean, the tile as its scene) carries the predictions back and averages them in fp32, and
 `merge_windows` feathers the mean tiles in metres.
@@ -107,17 +107,32 @@ class _Uploaded:
         return self.tensors
 
 
+def _cached(cache, key, device, build):
+    """The entry `key` of a cache of uploads: on its first use build() -> (int32 host arrays, anything to keep beside
+    them) is uploaded (`_Uploaded`), a full cache being emptied first.  -> (the device tensors, ordered for the current
+    stream; what was kept)."""
+    if key not in cache:
+        hosts, kept = build()
+        if len(cache) >= _CACHE_LIMIT:
+            cache.clear()
+        cache[key] = (_Uploaded(hosts, torch.device(device)), kept)
+    uploaded, kept = cache[key]
+    return uploaded.on_current_stream(), kept
+
+
+def _store_table(scenes, key, build):
+    """`_cached` for the one-array tables kept with a store (`scenes._infer_tables`) -> (device table, what was kept)."""
+    tensors, kept = _cached(scenes.__dict__.setdefault("_infer_tables", {}), key, scenes.device, build)
+    return tensors[0], kept
+
+
 def _device_maps(H, W, pad, multiple, device):
     """-> (rows, cols, frame): the device copies of `frame_maps`, cached per geometry and device, ordered for the current
     stream."""
-    key = (H, W, pad, multiple, str(device))
-    if key not in _MAPS:
+    def build():
         rows, cols, top, left = frame_maps(H, W, pad, multiple)
-        if len(_MAPS) >= _CACHE_LIMIT:
-            _MAPS.clear()
-        _MAPS[key] = (_Uploaded((rows, cols), torch.device(device)), Frame(len(rows), len(cols), top, left, H, W))
-    maps, frame = _MAPS[key]
-    rows, cols = maps.on_current_stream()
+        return (rows, cols), Frame(len(rows), len(cols), top, left, H, W)
+    (rows, cols), frame = _cached(_MAPS, (H, W, pad, multiple, str(device)), device, build)
     return rows, cols, frame
 
 
@@ -165,13 +180,8 @@ def _rows_of(scenes, indices) -> np.ndarray:
 def _table(scenes, indices) -> torch.Tensor:
     """The device copy of `_rows_of`, kept with the store per index list and ordered for the current stream: a repeated call
     uploads nothing."""
-    cache = scenes.__dict__.setdefault("_infer_tables", {})
     key = tuple(int(s) for s in indices)
-    if key not in cache:
-        if len(cache) >= _CACHE_LIMIT:
-            cache.clear()
-        cache[key] = _Uploaded((_rows_of(scenes, key),), scenes.device)
-    return cache[key].on_current_stream()[0]
+    return _store_table(scenes, key, lambda: ((_rows_of(scenes, key),), None))[0]
 
 
 def _one_shape(scenes, indices):
@@ -183,36 +193,48 @@ def _one_shape(scenes, indices):
     return shapes.pop()
 
 
+def _inputs(scenes, B, h, w, concat):
+    """The fp32 (B, C, h, w) input tensors of a forward, one per kind in `_input_kinds`' order -- concat: one tensor
+    [lr_dem | image | ...] --, and outs(lo, hi): kind -> (the samples lo:hi of its tensor, its first channel there), as the
+    prepare calls take them."""
+    kinds = _input_kinds(scenes)
+    C = [scenes.channels[k] for k in kinds]
+    kw = dict(dtype=torch.float32, device=scenes.device)
+    inputs = [torch.empty((B, sum(C), h, w), **kw)] if concat else [torch.empty((B, c, h, w), **kw) for c in C]
+
+    def outs(lo=0, hi=B):
+        return {k: (inputs[0 if concat else j][lo:hi], sum(C[:j]) if concat else 0) for j, k in enumerate(kinds)}
+    return inputs, outs
+
+
+def _launch(entry, scenes, table, outs, codes, *geometry):
+    """jspsr_scene_prepare*: the arguments the four entries share, around the host codes (the D4 entries; a ctypes int
+    array or a sequence), the sample count and `geometry` -- the maps and the frame's sides, or the tile's sides."""
+    import ctypes
+    count = (table.shape[0],)
+    if codes is not None:
+        if not isinstance(codes, ctypes.Array):
+            codes = (ctypes.c_int * len(codes))(*[int(c) for c in codes])
+        if len(codes) != table.shape[0]:
+            raise ValueError(f"{entry[len('jspsr_scene_'):]}: {len(codes)} codes for {table.shape[0]} samples")
+        count = (codes, table.shape[0])
+    _lib.check(getattr(_lib.load(), entry)(*ctypes_arrays(scenes, outs), scenes.scene_table.data_ptr(), len(scenes), table.data_ptr(),
+                                           *count, *geometry, scenes.flags, float(scenes.elev_min), float(scenes.elev_max),
+                                           len(scenes.mask_channel) + 1, torch.cuda.current_stream(scenes.device).cuda_stream),
+               entry)
+
+
 def _prepare(scenes, table, H, W, pad, multiple, concat):
     rows, cols, frame = _device_maps(H, W, int(pad), int(multiple), scenes.device)
-    B = table.shape[0]
-    kinds = _input_kinds(scenes)
-    kw = dict(dtype=torch.float32, device=scenes.device)
-    outs = {}
-    if concat:
-        images = torch.empty((B, sum(scenes.channels[k] for k in kinds), frame.Hp, frame.Wp), **kw)
-        c0 = 0
-        for k in kinds:
-            outs[k] = (images, c0)
-            c0 += scenes.channels[k]
-        inputs = [images]
-    else:
-        for k in kinds:
-            outs[k] = (torch.empty((B, scenes.channels[k], frame.Hp, frame.Wp), **kw), 0)
-        inputs = [outs[k][0] for k in kinds]
-    launch_prepare(scenes, table, rows, cols, frame.Hp, frame.Wp, outs)
+    inputs, outs = _inputs(scenes, table.shape[0], frame.Hp, frame.Wp, concat)
+    launch_prepare(scenes, table, rows, cols, frame.Hp, frame.Wp, outs())
     return inputs, frame
 
 
 def launch_prepare(scenes, table, rows, cols, Hp, Wp, outs: dict):
     """The raw call: table (B, 2) int32, rows (Hp,) and cols (Wp,) int32 on the device; outs kind -> (tensor of
     (B, cpitch, Hp, Wp) fp32, first channel), as `DeviceScenes.make` takes them."""
-    P = ctypes_arrays(scenes, outs)
-    _lib.check(_lib.load().jspsr_scene_prepare(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
-                                               table.data_ptr(), table.shape[0], rows.data_ptr(), cols.data_ptr(), Hp, Wp,
-                                               scenes.flags, float(scenes.elev_min), float(scenes.elev_max),
-                                               len(scenes.mask_channel) + 1, torch.cuda.current_stream(scenes.device).cuda_stream),
-               "jspsr_scene_prepare")
+    _launch("jspsr_scene_prepare", scenes, table, outs, None, rows.data_ptr(), cols.data_ptr(), Hp, Wp)
 
 
 def prepare(scenes, indices: Sequence[int], pad: int = 0, multiple: int = 8, concat: bool = False):
@@ -250,7 +272,7 @@ def finish(pred: torch.Tensor, scenes, indices: Sequence[int], frame: Frame, met
     return _finish(pred, _table(scenes, indices), scenes, frame, metres, out)
 
 
-# ---- K14 (csrc/scene_tta.hip): the self-ensemble over the flips and quarter turns ----------------------------------------------
+# ---- K14 (csrc/scene_prepare.hip, scene_tta.hip): the self-ensemble over the flips and quarter turns -----------------------
 def _element(e):
     """-> (rot90, flip_lr, flip_ud) from a triple or from K9's code rot90 * 4 + flip_lr * 2 + flip_ud."""
     if isinstance(e, (int, np.integer)) and not isinstance(e, (bool, np.bool_)):
@@ -333,65 +355,57 @@ def _frame_d4(scenes, H, W, parity, pad, multiple, element):
 def _table_d4(scenes, indices, codes):
     """(device table (len(codes) * B, 3) int32 {scene, base as fp32 bits, code}, element-major; the host codes), kept with
     the store per (index list, codes) as `_table` keeps its tables."""
-    import ctypes
-    cache = scenes.__dict__.setdefault("_infer_tables", {})
     key = ("d4", tuple(int(s) for s in indices), tuple(int(c) for c in codes))
-    if key not in cache:
-        if len(cache) >= _CACHE_LIMIT:
-            cache.clear()
-        base = _rows_of(scenes, key[1])
-        rows = np.concatenate([np.concatenate([base, np.full((len(base), 1), c, dtype=np.int32)], axis=1) for c in key[2]])
-        cache[key] = (_Uploaded((rows,), scenes.device), (ctypes.c_int * len(rows))(*rows[:, 2].tolist()))
-    uploaded, host = cache[key]
-    return uploaded.on_current_stream()[0], host
+    return _store_table(scenes, key, lambda: _coded(_rows_of(scenes, key[1]), key[2]))
+
+
+def _coded(rows, codes):
+    """A sample table once per code, element-major, the code as one more column -> ((the table,), the ctypes copy of that
+    column): what `_store_table` uploads and keeps for a D4 entry."""
+    import ctypes
+    rows = np.concatenate([np.concatenate([rows, np.full((len(rows), 1), c, dtype=np.int32)], axis=1) for c in codes])
+    return (rows,), (ctypes.c_int * len(rows))(*rows[:, -1].tolist())
 
 
 def launch_prepare_d4(scenes, table, codes, rows, cols, Hp, Wp, outs: dict):
     """The raw call: table (B, 3) int32 on the device, codes its third column on the host (a ctypes int array or a
     sequence); the rest as `launch_prepare`, the maps those of the transformed shape."""
-    import ctypes
-    if not isinstance(codes, ctypes.Array):
-        codes = (ctypes.c_int * len(codes))(*[int(c) for c in codes])
-    if len(codes) != table.shape[0]:
-        raise ValueError(f"prepare_d4: {len(codes)} codes for {table.shape[0]} samples")
-    P = ctypes_arrays(scenes, outs)
-    _lib.check(_lib.load().jspsr_scene_prepare_d4(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
-                                                  table.data_ptr(), codes, table.shape[0], rows.data_ptr(), cols.data_ptr(), Hp,
-                                                  Wp, scenes.flags, float(scenes.elev_min), float(scenes.elev_max),
-                                                  len(scenes.mask_channel) + 1,
-                                                  torch.cuda.current_stream(scenes.device).cuda_stream), "jspsr_scene_prepare_d4")
+    _launch("jspsr_scene_prepare_d4", scenes, table, outs, codes, rows.data_ptr(), cols.data_ptr(), Hp, Wp)
+
+
+def _parity_order(elements):
+    return [e for e in elements if e[0] % 2 == 0] + [e for e in elements if e[0] % 2 == 1]
+
+
+def _run(scenes, nb, order, h, w, concat, launch):
+    """One forward's inputs for the samples (element, one of nb scenes or windows), element-major, `order` being
+    `_parity_order`'s and of one output shape h x w: launch(parity, codes, outs) per rot90 parity present, the even one
+    first, into batch slices of the same tensors."""
+    inputs, outs = _inputs(scenes, len(order) * nb, h, w, concat)
+    at = 0
+    for p in (0, 1):
+        codes = [d4_code(e) for e in order if e[0] % 2 == p]
+        if codes:
+            launch(p, codes, outs(at, at + len(codes) * nb))
+            at += len(codes) * nb
+    return inputs
 
 
 def _prepare_run(scenes, idx, elements, H, W, pad, multiple, concat):
     """The samples (element, scene), element-major, of one forward: `elements` must share a frame shape (one rot90 parity,
     or a square scene).  One launch per parity into batch slices of the same tensors, the even elements first.
     -> (inputs, {parity: Frame}, the elements in batch order)."""
-    order = [e for e in elements if e[0] % 2 == 0] + [e for e in elements if e[0] % 2 == 1]
+    order = _parity_order(elements)
     maps = {p: _frame_d4(scenes, H, W, p, pad, multiple, next(e for e in order if e[0] % 2 == p)) for p in {e[0] % 2 for e in order}}
     shapes = {(f.Hp, f.Wp) for _, _, f in maps.values()}
     if len(shapes) != 1:
         raise ValueError(f"elements {order} of a {H} x {W} scene have frames {sorted(shapes)}: one rot90 parity per forward")
     Hp, Wp = shapes.pop()
-    nb = len(idx)
-    kinds = _input_kinds(scenes)
-    kw = dict(dtype=torch.float32, device=scenes.device)
-    if concat:
-        inputs = [torch.empty((len(order) * nb, sum(scenes.channels[k] for k in kinds), Hp, Wp), **kw)]
-    else:
-        inputs = [torch.empty((len(order) * nb, scenes.channels[k], Hp, Wp), **kw) for k in kinds]
-    at = 0
-    for p in sorted(maps):
-        rows, cols, _ = maps[p]
-        codes = [d4_code(e) for e in order if e[0] % 2 == p]
+
+    def launch(p, codes, outs):
         table, host = _table_d4(scenes, idx, codes)
-        n = len(codes) * nb
-        outs, c0 = {}, 0
-        for j, k in enumerate(kinds):
-            outs[k] = (inputs[0][at:at + n], c0) if concat else (inputs[j][at:at + n], 0)
-            c0 += scenes.channels[k] if concat else 0
-        launch_prepare_d4(scenes, table, host, rows, cols, Hp, Wp, outs)
-        at += n
-    return inputs, {p: f for p, (_, _, f) in maps.items()}, order
+        launch_prepare_d4(scenes, table, host, maps[p][0], maps[p][1], Hp, Wp, outs)
+    return _run(scenes, len(idx), order, Hp, Wp, concat, launch), {p: f for p, (_, _, f) in maps.items()}, order
 
 
 def prepare_d4(scenes, indices: Sequence[int], elements="d4", pad=0, multiple: int = 8, concat: bool = False) -> dict:
@@ -412,7 +426,9 @@ def prepare_d4(scenes, indices: Sequence[int], elements="d4", pad=0, multiple: i
     return out
 
 
-def _finish_mean(preds, table, scenes, frames, elements, H, W, metres, out):
+def _mean(who, preds, frames, elements, table, out, H, W, metres, elev_log, elev_min, elev_max, device, elsewhere):
+    """jspsr_scene_finish_mean: preds[k] (B, 1, Hp_k, Wp_k) on `device`, the prediction of element elements[k] with its H x W
+    scene (or tile) at frames[k]; the messages start with `who` and name the other device as `elsewhere`."""
     B = table.shape[0]
     variants = (_lib.TtaVariant * max(len(preds), 1))()
     keep = []
@@ -420,21 +436,25 @@ def _finish_mean(preds, table, scenes, frames, elements, H, W, metres, out):
         if pred.dim() == 3:
             pred = pred[:, None]
         if tuple(pred.shape) != (B, 1, frame.Hp, frame.Wp):
-            raise ValueError(f"finish_mean: predictions {tuple(pred.shape)} of element {e}, expected {(B, 1, frame.Hp, frame.Wp)}")
+            raise ValueError(f"{who}: predictions {tuple(pred.shape)} of element {e}, expected {(B, 1, frame.Hp, frame.Wp)}")
         if pred.dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"finish_mean: fp32 or bf16 predictions, got {pred.dtype}")
-        if pred.device != scenes.device:
-            raise ValueError(f"finish_mean: predictions on {pred.device}, the scenes on {scenes.device}")
+            raise ValueError(f"{who}: fp32 or bf16 predictions, got {pred.dtype}")
+        if pred.device != device:
+            raise ValueError(f"{who}: predictions on {pred.device}{elsewhere}")
         pred = pred.detach().contiguous()
         keep.append(pred)
         if k < len(variants):
             variants[k] = _lib.TtaVariant(pred.data_ptr(), int(pred.dtype == torch.bfloat16), d4_code(e), frame.Hp, frame.Wp,
                                           frame.top, frame.left, frame.H, frame.W)
     _lib.check(_lib.load().jspsr_scene_finish_mean(variants, len(preds), out.data_ptr(), table.data_ptr(), B, H, W,
-                                                   int(bool(metres)), int(bool(scenes.elev_log)), float(scenes.elev_min),
-                                                   float(scenes.elev_max), torch.cuda.current_stream(scenes.device).cuda_stream),
-               "jspsr_scene_finish_mean")
+                                                   int(bool(metres)), int(bool(elev_log)), float(elev_min), float(elev_max),
+                                                   torch.cuda.current_stream(device).cuda_stream), "jspsr_scene_finish_mean")
     return out
+
+
+def _finish_mean(preds, table, scenes, frames, elements, H, W, metres, out):
+    return _mean("finish_mean", preds, frames, elements, table, out, H, W, metres, scenes.elev_log, scenes.elev_min, scenes.elev_max,
+                 scenes.device, f", the scenes on {scenes.device}")
 
 
 def finish_mean(preds: Sequence[torch.Tensor], scenes, indices: Sequence[int], frames, elements, metres: bool = True) -> torch.Tensor:
@@ -454,33 +474,40 @@ def finish_mean(preds: Sequence[torch.Tensor], scenes, indices: Sequence[int], f
     return _finish_mean(list(preds), _table(scenes, indices), scenes, frames, elements, H, W, metres, out)
 
 
+def _ensemble_chunks(elements, square, batch_size):
+    """How an ensemble rides the batch dimension -> (nb, runs): chunks of nb scenes (or windows), and per chunk one forward
+    per run of elements, nb * len(run) <= batch_size samples where that leaves room for one.  The elements of a square shape
+    share one output shape; a rectangle's rot90 parities have one each, the even one first."""
+    even, odd = [e for e in elements if e[0] % 2 == 0], [e for e in elements if e[0] % 2 == 1]
+    sets = [even + odd] if square else [s for s in (even, odd) if s]
+    nb = max(1, batch_size // max(len(s) for s in sets))
+    per = max(1, batch_size // nb)                                         # elements per forward
+    return nb, [s[e0:e0 + per] for s in sets for e0 in range(0, len(s), per)]
+
+
 def _predict_tta(model, scenes, indices, elements, groups, offsets, buffer, batch_size, pad, multiple, concat, take, metres):
     """predict_scenes' pass with a self-ensemble: per group of equally shaped scenes, chunks of scenes whose variants ride
     the batch dimension, at most `batch_size` samples per forward; a square scene's elements share one frame shape, a
     rectangular scene's rot90 parities have one each."""
     for (h, w), members in groups.items():
-        even, odd = [e for e in elements if e[0] % 2 == 0], [e for e in elements if e[0] % 2 == 1]
-        sets = [even + odd] if h == w else [s for s in (even, odd) if s]
-        nb = max(1, batch_size // max(len(s) for s in sets))               # scenes per chunk
-        per = max(1, batch_size // nb)                                     # elements per forward
+        nb, runs = _ensemble_chunks(elements, h == w, batch_size)
         for lo in range(0, len(members), nb):
             idx = [indices[pos] for pos in members[lo:lo + nb]]
             preds, frames = {}, {}
-            for s in sets:
-                for e0 in range(0, len(s), per):
-                    inputs, fr, order = _prepare_run(scenes, idx, s[e0:e0 + per], h, w, pad, multiple, concat)
-                    pred = model(*[inputs[i] for i in take])
-                    if pred.shape[0] != len(order) * len(idx):
-                        raise ValueError(f"predict_scenes: {len(order) * len(idx)} samples in, {pred.shape[0]} predictions out")
-                    pred = pred.detach().contiguous()
-                    for j, e in enumerate(order):
-                        preds[e], frames[e] = pred[j * len(idx):(j + 1) * len(idx)], fr[e[0] % 2]
+            for run in runs:
+                inputs, fr, order = _prepare_run(scenes, idx, run, h, w, pad, multiple, concat)
+                pred = model(*[inputs[i] for i in take])
+                if pred.shape[0] != len(order) * len(idx):
+                    raise ValueError(f"predict_scenes: {len(order) * len(idx)} samples in, {pred.shape[0]} predictions out")
+                pred = pred.detach().contiguous()
+                for j, e in enumerate(order):
+                    preds[e], frames[e] = pred[j * len(idx):(j + 1) * len(idx)], fr[e[0] % 2]
             o = offsets[members[lo]]
             _finish_mean([preds[e] for e in elements], _table(scenes, idx), scenes, [frames[e] for e in elements], elements, h, w,
                          metres, buffer[o:o + len(idx) * h * w])
 
 
-# ---- K15 (csrc/scene_tiles.hip): scenes of any size through tiles of one size ------------------------------------------------
+# ---- K15 (csrc/scene_prepare.hip, scene_tiles.hip): scenes of any size through tiles of one size -------------------------
 _COVERS = {}                                          # (Cover.key, device) -> _Uploaded((oy, ox, lo_y, lo_x, wy bits, wx bits))
 
 
@@ -500,14 +527,10 @@ def _tile_sides(tile):
 def _device_cover(cover: Cover, device):
     """-> (oy, ox, lo_y, lo_x, wy, wx) on the device (the weights as their int32 bit patterns), cached per cover and device
     and ordered for the current stream, as `_device_maps`."""
-    key = (cover.key, str(device))
-    if key not in _COVERS:
-        if len(_COVERS) >= _CACHE_LIMIT:
-            _COVERS.clear()
-        hosts = (cover.oy, cover.ox, cover.lo_y, cover.lo_x, np.ascontiguousarray(cover.wy, np.float32).view(np.int32),
-                 np.ascontiguousarray(cover.wx, np.float32).view(np.int32))
-        _COVERS[key] = _Uploaded(hosts, torch.device(device))
-    return _COVERS[key].on_current_stream()
+    def hosts():
+        return (cover.oy, cover.ox, cover.lo_y, cover.lo_x, np.ascontiguousarray(cover.wy, np.float32).view(np.int32),
+                np.ascontiguousarray(cover.wx, np.float32).view(np.int32)), None
+    return _cached(_COVERS, (cover.key, str(device)), device, hosts)[0]
 
 
 def _window_rows(scenes, windows) -> np.ndarray:
@@ -522,42 +545,18 @@ def _window_rows(scenes, windows) -> np.ndarray:
 
 def _window_table(scenes, windows) -> torch.Tensor:
     """The device copy of `_window_rows`, kept with the store per window list as `_table` keeps its tables."""
-    cache = scenes.__dict__.setdefault("_infer_tables", {})
     key = ("windows", tuple((int(s), int(y), int(x)) for s, y, x in windows))
-    if key not in cache:
-        if len(cache) >= _CACHE_LIMIT:
-            cache.clear()
-        cache[key] = _Uploaded((_window_rows(scenes, key[1]),), scenes.device)
-    return cache[key].on_current_stream()[0]
+    return _store_table(scenes, key, lambda: ((_window_rows(scenes, key[1]),), None))[0]
 
 
 def launch_prepare_windows(scenes, table, kh, kw, outs: dict):
     """The raw call: table (B, 4) int32 on the device; outs kind -> (tensor of (B, cpitch, kh, kw) fp32, first channel)."""
-    P = ctypes_arrays(scenes, outs)
-    _lib.check(_lib.load().jspsr_scene_prepare_windows(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(), len(scenes),
-                                                       table.data_ptr(), table.shape[0], kh, kw, scenes.flags,
-                                                       float(scenes.elev_min), float(scenes.elev_max), len(scenes.mask_channel) + 1,
-                                                       torch.cuda.current_stream(scenes.device).cuda_stream),
-               "jspsr_scene_prepare_windows")
+    _launch("jspsr_scene_prepare_windows", scenes, table, outs, None, kh, kw)
 
 
 def _prepare_windows(scenes, table, kh, kw, concat):
-    B = table.shape[0]
-    kinds = _input_kinds(scenes)
-    kw_ = dict(dtype=torch.float32, device=scenes.device)
-    outs = {}
-    if concat:
-        images = torch.empty((B, sum(scenes.channels[k] for k in kinds), kh, kw), **kw_)
-        c0 = 0
-        for k in kinds:
-            outs[k] = (images, c0)
-            c0 += scenes.channels[k]
-        inputs = [images]
-    else:
-        for k in kinds:
-            outs[k] = (torch.empty((B, scenes.channels[k], kh, kw), **kw_), 0)
-        inputs = [outs[k][0] for k in kinds]
-    launch_prepare_windows(scenes, table, kh, kw, outs)
+    inputs, outs = _inputs(scenes, table.shape[0], kh, kw, concat)
+    launch_prepare_windows(scenes, table, kh, kw, outs())
     return inputs
 
 
@@ -602,13 +601,12 @@ def merge_windows(pred_tiles: torch.Tensor, scenes, indices: Sequence[int], cove
     return _merge_windows(pred_tiles, _table(scenes, indices), scenes, cover, metres, out)
 
 
-def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffer, batch_size, concat, take, metres):
-    """predict_scenes' pass over the scenes larger than the tile (`tiled`: their positions in `indices`, ascending; `covers`:
-    shape -> Cover, all of one tile).  The windows are listed in scene order, row-major, and cut into forwards of
-    `batch_size`; the predictions land in one tile buffer laid out group by group, so that one merge launch per shape group
-    writes the result."""
+def _tile_plan(scenes, indices, tiled, groups, covers):
+    """-> (kh, kw, slot, windows, slots): the tile; position -> first tile of the scene in a tile buffer laid out group by
+    group; the windows (scene, y0, x0) of the scenes `tiled` in scene order, row-major; and each window's tile in the
+    buffer."""
     kh, kw = next((c.kh, c.kw) for c in covers.values())
-    slot, at = {}, 0                                              # position -> first tile of the scene in the tile buffer
+    slot, at = {}, 0
     for shape, members in groups.items():
         for pos in members:
             slot[pos] = at
@@ -618,6 +616,36 @@ def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffe
         cover = covers[tuple(scenes.shapes[indices[pos]])]
         windows += [(indices[pos], y0, x0) for y0, x0 in cover.windows()]
         slots += range(slot[pos], slot[pos] + cover.n)
+    return kh, kw, slot, windows, slots
+
+
+def _to_slots(tiles, slots, src):
+    """tiles[slots[j]] = src[j], one copy per run of consecutive slots: the windows of one scene."""
+    j = 0
+    while j < len(slots):
+        e = j + 1
+        while e < len(slots) and slots[e] == slots[e - 1] + 1:
+            e += 1
+        tiles[slots[j]:slots[j] + e - j].copy_(src[j:e])
+        j = e
+
+
+def _merge_groups(tiles, slot, scenes, indices, groups, covers, offsets, buffer, metres):
+    """One merge launch per shape group, from the tile buffer into the result."""
+    for shape, members in groups.items():
+        idx = [indices[pos] for pos in members]
+        h, w = shape
+        o, t0 = offsets[members[0]], slot[members[0]]
+        _merge_windows(tiles[t0:t0 + len(idx) * covers[shape].n], _table(scenes, idx), scenes, covers[shape], metres,
+                       buffer[o:o + len(idx) * h * w])
+
+
+def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffer, batch_size, concat, take, metres):
+    """predict_scenes' pass over the scenes larger than the tile (`tiled`: their positions in `indices`, ascending; `covers`:
+    shape -> Cover, all of one tile).  The windows are listed in scene order, row-major, and cut into forwards of
+    `batch_size`; the predictions land in one tile buffer laid out group by group, so that one merge launch per shape group
+    writes the result."""
+    kh, kw, slot, windows, slots = _tile_plan(scenes, indices, tiled, groups, covers)
     table = _window_table(scenes, windows)
     tiles = None
     for lo in range(0, len(windows), batch_size):
@@ -630,86 +658,39 @@ def _predict_tiled(model, scenes, indices, tiled, groups, covers, offsets, buffe
             raise ValueError(f"predict_scenes: {B} windows of {kh} x {kw} in, predictions {tuple(pred.shape)} out")
         if tiles is None:
             tiles = torch.empty((len(windows), 1, kh, kw), dtype=pred.dtype, device=scenes.device)
-        j = 0
-        while j < B:                                              # runs of consecutive slots: the windows of one scene
-            e = j + 1
-            while e < B and slots[lo + e] == slots[lo + e - 1] + 1:
-                e += 1
-            tiles[slots[lo + j]:slots[lo + j] + e - j].copy_(pred[j:e])
-            j = e
-    for shape, members in groups.items():
-        idx = [indices[pos] for pos in members]
-        h, w = shape
-        o, t0 = offsets[members[0]], slot[members[0]]
-        _merge_windows(tiles[t0:t0 + len(idx) * covers[shape].n], _table(scenes, idx), scenes, covers[shape], metres,
-                       buffer[o:o + len(idx) * h * w])
+        _to_slots(tiles, slots[lo:lo + B], pred)
+    _merge_groups(tiles, slot, scenes, indices, groups, covers, offsets, buffer, metres)
 
 
-# ---- K16 (csrc/scene_tiles_tta.hip): the self-ensemble per window of a tiled scene -------------------------------------------
+# ---- K16 (csrc/scene_prepare.hip): the self-ensemble per window of a tiled scene -------------------------------------------
 def _window_table_d4(scenes, windows, codes):
     """(device table (len(codes) * B, 5) int32 {scene, base as fp32 bits, y0, x0, code}, element-major; the host codes), kept
     with the store per (window list, codes) as `_window_table` keeps its tables."""
-    import ctypes
-    cache = scenes.__dict__.setdefault("_infer_tables", {})
     key = ("windows_d4", tuple((int(s), int(y), int(x)) for s, y, x in windows), tuple(int(c) for c in codes))
-    if key not in cache:
-        if len(cache) >= _CACHE_LIMIT:
-            cache.clear()
-        base = _window_rows(scenes, key[1])
-        rows = np.concatenate([np.concatenate([base, np.full((len(base), 1), c, dtype=np.int32)], axis=1) for c in key[2]])
-        cache[key] = (_Uploaded((rows,), scenes.device), (ctypes.c_int * len(rows))(*rows[:, 4].tolist()))
-    uploaded, host = cache[key]
-    return uploaded.on_current_stream()[0], host
+    return _store_table(scenes, key, lambda: _coded(_window_rows(scenes, key[1]), key[2]))
 
 
 def launch_prepare_windows_d4(scenes, table, codes, kh, kw, outs: dict):
     """The raw call: table (B, 5) int32 on the device, codes its fifth column on the host (a ctypes int array or a sequence),
     all of one rot90 parity; outs kind -> (tensor of (B, cpitch, kh, kw) fp32 -- (B, cpitch, kw, kh) for an odd rot90 --,
     first channel)."""
-    import ctypes
-    if not isinstance(codes, ctypes.Array):
-        codes = (ctypes.c_int * len(codes))(*[int(c) for c in codes])
-    if len(codes) != table.shape[0]:
-        raise ValueError(f"prepare_windows_d4: {len(codes)} codes for {table.shape[0]} samples")
-    P = ctypes_arrays(scenes, outs)
-    _lib.check(_lib.load().jspsr_scene_prepare_windows_d4(P[0], P[1], P[2], P[3], P[4], P[5], scenes.scene_table.data_ptr(),
-                                                          len(scenes), table.data_ptr(), codes, table.shape[0], kh, kw, scenes.flags,
-                                                          float(scenes.elev_min), float(scenes.elev_max),
-                                                          len(scenes.mask_channel) + 1,
-                                                          torch.cuda.current_stream(scenes.device).cuda_stream),
-               "jspsr_scene_prepare_windows_d4")
+    _launch("jspsr_scene_prepare_windows_d4", scenes, table, outs, codes, kh, kw)
 
 
 def _prepare_windows_run(scenes, windows, elements, kh, kw, concat):
     """The samples (element, window), element-major, of one forward: `elements` must share an output shape (one rot90 parity,
     or a square tile).  One launch per parity into batch slices of the same tensors, the even elements first.
     -> (inputs, the elements in batch order)."""
-    order = [e for e in elements if e[0] % 2 == 0] + [e for e in elements if e[0] % 2 == 1]
+    order = _parity_order(elements)
     shapes = {(kw, kh) if e[0] % 2 else (kh, kw) for e in order}
     if len(shapes) != 1:
         raise ValueError(f"elements {order} of a {kh} x {kw} window have shapes {sorted(shapes)}: one rot90 parity per forward")
     oh, ow = shapes.pop()
-    nb = len(windows)
-    kinds = _input_kinds(scenes)
-    kw_ = dict(dtype=torch.float32, device=scenes.device)
-    if concat:
-        inputs = [torch.empty((len(order) * nb, sum(scenes.channels[k] for k in kinds), oh, ow), **kw_)]
-    else:
-        inputs = [torch.empty((len(order) * nb, scenes.channels[k], oh, ow), **kw_) for k in kinds]
-    at = 0
-    for p in (0, 1):
-        codes = [d4_code(e) for e in order if e[0] % 2 == p]
-        if not codes:
-            continue
+
+    def launch(p, codes, outs):
         table, host = _window_table_d4(scenes, windows, codes)
-        n = len(codes) * nb
-        outs, c0 = {}, 0
-        for j, k in enumerate(kinds):
-            outs[k] = (inputs[0][at:at + n], c0) if concat else (inputs[j][at:at + n], 0)
-            c0 += scenes.channels[k] if concat else 0
         launch_prepare_windows_d4(scenes, table, host, kh, kw, outs)
-        at += n
-    return inputs, order
+    return _run(scenes, len(windows), order, oh, ow, concat, launch), order
 
 
 def prepare_windows_d4(scenes, windows: Sequence, tile, elements="d4", concat: bool = False) -> dict:
@@ -736,26 +717,8 @@ def prepare_windows_d4(scenes, windows: Sequence, tile, elements="d4", concat: b
 def _mean_windows(preds, elements, kh, kw, table, out):
     """jspsr_scene_finish_mean with the tile as its scene: preds[k] (N, 1, kh, kw) -- (N, 1, kw, kh) for an odd rot90 -- of
     element elements[k]; table a device (N, 2) int32 table (read, not used: metres = 0); out (N, 1, kh, kw) fp32."""
-    N = table.shape[0]
-    variants = (_lib.TtaVariant * max(len(preds), 1))()
-    keep = []
-    for k, (pred, e) in enumerate(zip(preds, elements)):
-        oh, ow = (kw, kh) if e[0] % 2 else (kh, kw)
-        if pred.dim() == 3:
-            pred = pred[:, None]
-        if tuple(pred.shape) != (N, 1, oh, ow):
-            raise ValueError(f"mean_windows: predictions {tuple(pred.shape)} of element {e}, expected {(N, 1, oh, ow)}")
-        if pred.dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"mean_windows: fp32 or bf16 predictions, got {pred.dtype}")
-        if pred.device != out.device:
-            raise ValueError(f"mean_windows: predictions on {pred.device} and on {out.device}")
-        pred = pred.detach().contiguous()
-        keep.append(pred)
-        if k < len(variants):
-            variants[k] = _lib.TtaVariant(pred.data_ptr(), int(pred.dtype == torch.bfloat16), d4_code(e), oh, ow, 0, 0, oh, ow)
-    _lib.check(_lib.load().jspsr_scene_finish_mean(variants, len(preds), out.data_ptr(), table.data_ptr(), N, kh, kw, 0, 0, 0.0, 1.0,
-                                                   torch.cuda.current_stream(out.device).cuda_stream), "jspsr_scene_finish_mean")
-    return out
+    frames = [Frame(kw, kh, 0, 0, kw, kh) if e[0] % 2 else Frame(kh, kw, 0, 0, kh, kw) for e in elements]
+    return _mean("mean_windows", preds, frames, elements, table, out, kh, kw, 0, 0, 0.0, 1.0, out.device, f" and on {out.device}")
 
 
 def mean_windows(preds: Sequence[torch.Tensor], elements, tile) -> torch.Tensor:
@@ -782,55 +745,31 @@ def _predict_tiled_tta(model, scenes, indices, tiled, groups, covers, offsets, b
     variants ride the batch dimension, at most `batch_size` samples per forward (`_predict_tta`'s rule, the tile in the place
     of the scene: a square tile's elements share one shape, a rectangular tile's rot90 parities have one each).  Per chunk
     one finish_mean launch writes the fp32 mean tiles into the tile buffer; then `_predict_tiled`'s merge."""
-    kh, kw = next((c.kh, c.kw) for c in covers.values())
-    slot, at = {}, 0                                              # position -> first tile of the scene in the tile buffer
-    for shape, members in groups.items():
-        for pos in members:
-            slot[pos] = at
-            at += covers[shape].n
-    windows, slots = [], []
-    for pos in tiled:
-        cover = covers[tuple(scenes.shapes[indices[pos]])]
-        windows += [(indices[pos], y0, x0) for y0, x0 in cover.windows()]
-        slots += range(slot[pos], slot[pos] + cover.n)
-    even, odd = [e for e in elements if e[0] % 2 == 0], [e for e in elements if e[0] % 2 == 1]
-    sets = [even + odd] if kh == kw else [s for s in (even, odd) if s]
-    nb = max(1, batch_size // max(len(s) for s in sets))              # windows per chunk
-    per = max(1, batch_size // nb)                                    # elements per forward
+    kh, kw, slot, windows, slots = _tile_plan(scenes, indices, tiled, groups, covers)
+    nb, runs = _ensemble_chunks(elements, kh == kw, batch_size)
     tiles = torch.empty((len(windows), 1, kh, kw), dtype=torch.float32, device=scenes.device)
     for lo in range(0, len(windows), nb):
         chunk = windows[lo:lo + nb]
         B = len(chunk)
         preds = {}
-        for s in sets:
-            for e0 in range(0, len(s), per):
-                inputs, order = _prepare_windows_run(scenes, chunk, s[e0:e0 + per], kh, kw, concat)
-                pred = model(*[inputs[i] for i in take])
-                if pred.dim() == 3:
-                    pred = pred[:, None]
-                if tuple(pred.shape) != (len(order) * B, 1) + tuple(inputs[0].shape[2:]):
-                    raise ValueError(f"predict_scenes: {len(order) * B} windows of {tuple(inputs[0].shape[2:])} in, predictions "
-                                     f"{tuple(pred.shape)} out")
-                pred = pred.detach().contiguous()
-                for j, e in enumerate(order):
-                    preds[e] = pred[j * B:(j + 1) * B]
+        for run in runs:
+            inputs, order = _prepare_windows_run(scenes, chunk, run, kh, kw, concat)
+            pred = model(*[inputs[i] for i in take])
+            if pred.dim() == 3:
+                pred = pred[:, None]
+            if tuple(pred.shape) != (len(order) * B, 1) + tuple(inputs[0].shape[2:]):
+                raise ValueError(f"predict_scenes: {len(order) * B} windows of {tuple(inputs[0].shape[2:])} in, predictions "
+                                 f"{tuple(pred.shape)} out")
+            pred = pred.detach().contiguous()
+            for j, e in enumerate(order):
+                preds[e] = pred[j * B:(j + 1) * B]
         table = _table(scenes, [w[0] for w in chunk])
-        one_run = all(slots[lo + j] == slots[lo] + j for j in range(B))
+        one_run = all(slots[lo + j] == slots[lo] + j for j in range(B))    # the chunk's tiles are neighbours: no copy
         out = tiles[slots[lo]:slots[lo] + B] if one_run else torch.empty((B, 1, kh, kw), dtype=torch.float32, device=scenes.device)
         _mean_windows([preds[e] for e in elements], elements, kh, kw, table, out)
-        j = 0
-        while not one_run and j < B:                                  # runs of consecutive slots: the windows of one scene
-            e = j + 1
-            while e < B and slots[lo + e] == slots[lo + e - 1] + 1:
-                e += 1
-            tiles[slots[lo + j]:slots[lo + j] + e - j].copy_(out[j:e])
-            j = e
-    for shape, members in groups.items():
-        idx = [indices[pos] for pos in members]
-        h, w = shape
-        o, t0 = offsets[members[0]], slot[members[0]]
-        _merge_windows(tiles[t0:t0 + len(idx) * covers[shape].n], _table(scenes, idx), scenes, covers[shape], metres,
-                       buffer[o:o + len(idx) * h * w])
+        if not one_run:
+            _to_slots(tiles, slots[lo:lo + B], out)
+    _merge_groups(tiles, slot, scenes, indices, groups, covers, offsets, buffer, metres)
 
 
 # ---- K17 (csrc/scene_voids.hip): voids -- the nearest-seed transform, the fill and the output mask ------------------------------
@@ -937,16 +876,14 @@ def mask_out(out: torch.Tensor, void_out: torch.Tensor, rows: torch.Tensor, noda
 def _mask_rows(scenes, indices, offsets) -> torch.Tensor:
     """The device table of `mask_out` for a predict_scenes call, kept with the store per index list (the offsets follow
     from it) as `_table` keeps its tables: int64 rows uploaded as pairs of int32."""
-    cache = scenes.__dict__.setdefault("_infer_tables", {})
     key = ("mask_out", tuple(int(s) for s in indices))
-    if key not in cache:
-        if len(cache) >= _CACHE_LIMIT:
-            cache.clear()
+
+    def build():
         starts = np.concatenate([[0], np.cumsum([h * w for h, w in scenes.shapes])])
         rows = np.array([[offsets[pos], starts[s], scenes.shapes[s][0] * scenes.shapes[s][1]] for pos, s in enumerate(key[1])],
                         dtype=np.int64)
-        cache[key] = _Uploaded((rows.view(np.int32),), scenes.device)
-    return cache[key].on_current_stream()[0].view(torch.int64)
+        return (rows.view(np.int32),), None
+    return _store_table(scenes, key, build)[0].view(torch.int64)
 
 
 def _result(scenes, indices, offsets, buffer, mask_voids) -> "SceneRasters":

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY -- numpy restatement of K16 (csrc/scene_tiles_tta.hip, jspsr_amd/infer.py: prepare_windows_d4,
+"""TEST INFRASTRUCTURE ONLY -- numpy restatement of K16 (csrc/scene_prepare.hip, jspsr_amd/infer.py: prepare_windows_d4,
 mean_windows): the transform of a window, the index map behind it, and the mean of a window's predictions."""
 import numpy as np
 

@@ -1,8 +1,8 @@
-// The argument checks of the two K14 entry points (csrc/scene_tta.hip) from a stand-alone program: null and invalid
+// The argument checks of the two K14 entry points (csrc/scene_prepare.hip, scene_tta.hip) from a stand-alone program: null and invalid
 // arguments, every call must come back with its code and message before a launch.  It needs no GPU and is meant for a host
 // sanitizer build, from jspsr_amd/csrc:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//         scene_tta.hip common.hip ../../tools/tta_args_check.cpp -o /tmp/tta_args_check && /tmp/tta_args_check
+//         scene_prepare.hip scene_tta.hip common.hip ../../tools/tta_args_check.cpp -o /tmp/tta_args_check && /tmp/tta_args_check
 #include <cstdio>
 #include <cstring>
 #include "../include/jspsr_hip.h"
