@@ -6,16 +6,17 @@
 // Gaussian KDE over n points with repeated values is the same sum over the distinct values weighted by their counts.
 // (a) jspsr_errdist_hist_forward: ONE launch.  Candidate c is walked by gridDim.x workgroups (blockIdx.y = c), the grid
 //     sized so that all candidates together fill the chip once; a workgroup owns one contiguous range of the pooled
-//     elements, read through K12's window table (find_row, a 32-bit division on the usual path), and counts them into an
+//     elements, read through the window table by csrc/pooled_read.h's pooled_fetch (a bisection when the window changes,
+//     a 32-bit division on the usual path), and counts them into an
 //     LDS image of up to LDS_BINS bins (147 456 B of dynamic LDS, raised with hipFuncSetAttribute: one workgroup per CU, 16
 //     waves to hide the reads; it cannot be double-buffered).  A range with more bins than one image holds is walked once
 //     per image of LDS_BINS bins (at most twice: float16 has 63 488 finite values), inside the same launch.  The image is
 //     flushed with one 64-bit global add per occupied bin.  Integer adds only: a histogram has the same bits whatever
 //     candidates share the call, whatever the grid is, on every run.
 //     Contention: a baseline that equals the ground truth over water puts most of a wave's 64 increments into the two
-//     bins of 0, a good model's errors spread over thousands of bins.  bin_add takes up to ROUNDS (2) times the bin of the
-//     first pending lane, counts its lanes with a ballot and lets that lane add the count once (csrc/scores.hip's
-//     hist_add with v_readlane in place of the LDS permute); what is left adds one by one.  JSPSR_ERRDIST_ROUNDS = 0 / 1 / 2
+//     bins of 0, a good model's errors spread over thousands of bins.  hist_add<ROUNDS, true> (summary_select.h) takes up
+//     to ROUNDS (2) times the bin of the first pending lane, counts its lanes with a ballot and lets that lane add the
+//     count once, the leader's bin by v_readlane; what is left adds one by one.  JSPSR_ERRDIST_ROUNDS = 0 / 1 / 2
 //     selects the instance, for measurements only (profiles/r22_error_distribution_bench.txt).
 // (b) jspsr_errdist_kde_forward: two launches, fp64.  stats: a workgroup per candidate folds n, the mean, the variance
 //     (ddof 1, about the mean), Scott's bandwidth and numpy's linspace over the occupied support; density: a workgroup per
@@ -25,6 +26,8 @@
 // kernel's own arithmetic and the wave's FP16 denormal mode cannot matter.  Built with -ffp-contract=off: linspace is
 // start + i * step with two roundings, as numpy forms it.
 #include "common.h"
+#include "pooled_read.h"
+#include "summary_select.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -38,8 +41,6 @@ constexpr int UNROLL = 4;
 constexpr int STEP = HT * UNROLL;
 constexpr int LDS_BINS = 36864;               // bins of one LDS image: 147 456 B (the default range needs 35 330)
 constexpr int N_CU = 256;                     // MI355X
-constexpr int MAXC = 8;
-constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // K12's window row: segment (not read), h, w, e offset, {offset, pitch} of gt, cand 0..7
 constexpr int KT = 256;                       // threads of the curve kernels
 constexpr int WS_WORDS = 8;                   // doubles per candidate between the two curve kernels
 
@@ -99,41 +100,6 @@ __host__ __device__ inline int classify(float e, const Range& r) {
   return e < r.lo ? -1 : (e > r.hi ? -2 : -3);
 }
 
-struct Buffers {             // by value in the kernel arguments
-  const float* cand[MAXC];
-  long long cand_numel[MAXC];
-  const float* gt;
-  long long gt_numel;
-};
-
-// last row whose word `col` is <= v (csrc/summary.hip)
-__device__ __forceinline__ int find_row(const long long* __restrict__ tab, int rows, int words, int col, long long v) {
-  int lo = 0, hi = rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[(size_t)mid * words + col] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// One wave-instruction's worth of increments.  Every lane of the wave must arrive (wave-uniform trip counts at the call site).
-template <int ROUNDS>
-__device__ __forceinline__ void bin_add(unsigned* __restrict__ hist, bool match, unsigned bin) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int it = 0; it < ROUNDS; ++it) {
-    const unsigned long long act = __ballot(match);
-    if (act == 0ull) return;                                     // wave-uniform
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)bin, leader);
-    const bool mine = match && bin == b;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&hist[b], (unsigned)__popcll(m));
-    match = match && !mine;
-  }
-  if (match) atomicAdd(&hist[bin], 1u);
-}
-
 template <bool MASKED, int ROUNDS>
 __global__ __launch_bounds__(HT) void errdist_hist_kernel(Buffers B, const unsigned char* __restrict__ plane, const long long* __restrict__ win,
                                                          int n_win, long long total, long long per_wg, Range R,
@@ -144,16 +110,12 @@ __global__ __launch_bounds__(HT) void errdist_hist_kernel(Buffers B, const unsig
   const long long lo = (long long)blockIdx.x * per_wg;
   const long long hi = lo + per_wg < total ? lo + per_wg : total;
   if (lo >= hi) return;                                          // workgroup-uniform
-  const float* __restrict__ cp = B.cand[c];
-  const float* __restrict__ gp = B.gt;
-  const long long cn = B.cand_numel[c], gn = B.gt_numel;
   unsigned n_scored = 0u, n_in = 0u, n_below = 0u, n_above = 0u;   // this thread's; fewer than 2^32 elements per call
   for (int first = 0; first < R.K; first += LDS_BINS) {          // one walk per image; kernel-uniform
     const int bins = R.K - first < LDS_BINS ? R.K - first : LDS_BINS;
     for (int b = tid; b < bins; b += HT) image[b] = 0u;
     __syncthreads();
-    long long w_lo = 0, w_hi = 0, w_w = 1, goff = 0, gpitch = 0, coff = 0, cpitch = 0;   // the window of the last element
-    bool w_ok = false;
+    WindowCursor W(B, c);
     for (long long base = lo; base < hi; base += STEP) {
       int bin[UNROLL];
 #pragma unroll
@@ -161,29 +123,11 @@ __global__ __launch_bounds__(HT) void errdist_hist_kernel(Buffers B, const unsig
         const long long p = base + u * HT + tid;
         bin[u] = -4;                                             // not scored
         if (p >= hi) continue;
-        if (p < w_lo || p >= w_hi) {
-          const long long* wr = win + (size_t)find_row(win, n_win, WIN_WORDS, 3, p) * WIN_WORDS;
-          w_w = wr[2];
-          w_lo = wr[3];
-          w_hi = w_lo + wr[1] * w_w;
-          w_ok = wr[1] > 0 && w_w > 0;
-          goff = wr[4]; gpitch = wr[5];
-          coff = wr[6 + 2 * c]; cpitch = wr[7 + 2 * c];
-        }
-        float v = __builtin_nanf("");                           // an element no window covers, or a read outside a buffer: scored, a NaN
+        float v;                                                 // a NaN, scored: an element no window covers, or a read outside a buffer
         bool keep = true;
-        if (w_ok && p >= w_lo && p < w_hi) {
-          const long long local = p - w_lo;
-          long long y;
-          if (local < 0x100000000ll && w_w < 0x100000000ll) y = (long long)((unsigned)local / (unsigned)w_w);   // the usual case
-          else y = local / w_w;
-          const long long x = local - y * w_w;
-          const long long jc = coff + y * cpitch + x, jg = goff + y * gpitch + x;
-          if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) {
-            v = __fsub_rn(cp[jc], gp[jg]);
-            if constexpr (MASKED) keep = plane[jg] != 0;          // the plane has gt's numel (checked by the entry)
-          }
-        }
+        pooled_fetch(W, win, n_win, p, v, [&](long long jg) {
+          if constexpr (MASKED) keep = plane[jg] != 0;            // the plane has gt's numel (checked by the entry)
+        });
         if (keep) bin[u] = classify(v, R);                        // a masked element's v is looked at nowhere
       }
       if (first == 0) {
@@ -198,7 +142,7 @@ __global__ __launch_bounds__(HT) void errdist_hist_kernel(Buffers B, const unsig
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
         const int b = bin[u] - first;
-        bin_add<ROUNDS>(image, bin[u] >= 0 && b >= 0 && b < bins, (unsigned)b);
+        hist_add<ROUNDS, true>(image, bin[u] >= 0 && b >= 0 && b < bins, (unsigned)b);
       }
     }
     __syncthreads();
@@ -386,14 +330,7 @@ extern "C" int jspsr_errdist_hist_forward(const float* const* cands, const long 
   Range R;
   if (!make_range(lo, hi, R)) return fail(JSPSR_EINVAL, "%s: lo = %g, hi = %g (lo <= hi, both finite, magnitudes <= 65504)", name, lo, hi);
   Buffers B;
-  for (int c = 0; c < MAXC; ++c) {
-    B.cand[c] = c < n_cand ? cands[c] : nullptr;
-    B.cand_numel[c] = c < n_cand ? cand_numel[c] : 0;
-    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "%s: candidate %d is null or empty", name, c);
-    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "%s: candidate %d not 4-byte aligned", name, c);
-  }
-  B.gt = gt;
-  B.gt_numel = gt_numel;
+  if (int err = pack_buffers(name, cands, cand_numel, n_cand, gt, gt_numel, B)) return err;
   if (!aligned4(gt)) return fail(JSPSR_EALIGN, "%s: ground truth not 4-byte aligned", name);
   if ((reinterpret_cast<uintptr_t>(hist) & 7u) || (reinterpret_cast<uintptr_t>(counts) & 7u))
     return fail(JSPSR_EALIGN, "%s: hist and counts must be 8-byte aligned", name);

@@ -11,6 +11,7 @@
 // one-workgroup scans per statistic): exact -- the selected value is an element of the array, bit for bit what a sort
 // would give -- and O(n) instead of the sort behind torch.median / torch.kthvalue.
 #include "common.h"
+#include "summary_select.h"
 
 #include <cmath>
 
@@ -19,15 +20,6 @@ namespace {
 using namespace jspsr;
 
 constexpr int MT = 256;
-
-// float -> unsigned key with the same ordering (NaNs sort above +inf)
-__device__ __forceinline__ unsigned order_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 struct SelState {          // one per statistic, in device memory
   unsigned prefix;         // key bits fixed so far (high bits)
@@ -100,11 +92,6 @@ __global__ __launch_bounds__(MT) void metrics_reduce_kernel(const float* __restr
     st[2] = SelState{0u, k95, 0.f, 0.f};     // k-th of |dh|
   }
   for (int i = threadIdx.x; i < 256; i += MT) hist[i] = 0u;
-}
-
-// mode 0: x; 1: |x - center|; 2: |x|
-__device__ __forceinline__ float sel_transform(float x, int mode, float center) {
-  return mode == 0 ? x : (mode == 1 ? fabsf(x - center) : fabsf(x));
 }
 
 // histogram of byte `pass` (3 = most significant) of the keys whose higher bytes equal the state's prefix

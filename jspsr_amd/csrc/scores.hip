@@ -34,6 +34,7 @@
 //   * every lane still reaches hist_add; a masked element passes match = false.
 //   * launches: 1 (LDS path) or 27 (streaming path) whatever B and the mask are, labels scores_batch_valid (lds | stream).
 #include "common.h"
+#include "summary_select.h"
 
 #include <cmath>
 
@@ -51,17 +52,6 @@ constexpr size_t LDS_TOTAL = 163840;          // what one workgroup may declare 
 constexpr size_t LDS_STATIC = 1664;           // hist 1024 + red 4*16*8 = 512 + select state 16, rounded up
 constexpr long long LDS_MAX_N = (long long)((LDS_TOTAL - LDS_STATIC) / 8);
 
-__device__ __forceinline__ unsigned order_key(float f) {      // float -> unsigned key with the same ordering
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-// mode 0: x; 1: |x - center|; 2: |x|
-__device__ __forceinline__ float sel_transform(float x, int mode, float center) {
-  return mode == 0 ? x : (mode == 1 ? fabsf(x - center) : fabsf(x));
-}
 __device__ __forceinline__ float descale(float v, float vmin, float vmax, float lg, int elev_log) {
   return elev_log ? expf(v * lg) + vmin : v * (vmax - vmin) + vmin;
 }
@@ -73,11 +63,6 @@ __device__ __forceinline__ unsigned wave_count(unsigned v) {
 // K20's in-band mask: P of a masked pixel is this NaN; P of a counted pixel is finite
 __device__ __forceinline__ float masked_flag() { return __uint_as_float(0x7fc00000u); }
 __device__ __forceinline__ bool is_masked(float p) { return (__float_as_uint(p) & 0x7fffffffu) > 0x7f800000u; }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // The two Sobel terms of output pixel (y, x) of an h x w pair of de-scaled rasters (row stride w).
 //   local:  valid positions only (1 <= y < h-1, 1 <= x < w-1), (|grad P| - |grad G|)^2 with the unnormalised kernels
@@ -143,25 +128,6 @@ __device__ __forceinline__ unsigned rank_median(long long n) { return (unsigned)
 __device__ __forceinline__ unsigned rank_le95(long long n) { return (unsigned)llrint(0.95 * (double)(n - 1)); }       // 1 + round(0.95 (n-1)), 0-based
 
 // ---- LDS-resident path ---------------------------------------------------------------------------------------------
-// One wave-instruction's worth of histogram increments.  The top byte of the keys of a tile's elevation differences
-// falls into a handful of bins, and 64 lanes adding to one LDS address serialise: up to two rounds take the bin of the
-// first pending lane, count its lanes with a ballot and let that lane add the count once; what is left adds singly.
-__device__ __forceinline__ void hist_add(unsigned* __restrict__ hist, bool match, unsigned bin) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const unsigned long long act = __ballot(match);
-    if (act == 0ull) return;                                   // wave-uniform
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned b = (unsigned)__shfl((int)bin, leader, 64);
-    const bool mine = match && bin == b;
-    const unsigned long long m = __ballot(mine);
-    if (lane == leader) atomicAdd(&hist[b], (unsigned)__popcll(m));
-    match = match && !mine;
-  }
-  if (match) atomicAdd(&hist[bin], 1u);
-}
-
 template <bool MASKED>
 __global__ __launch_bounds__(ST) void scores_lds_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                        const unsigned char* __restrict__ valid, int H, int W,
@@ -518,7 +484,6 @@ int stream_blocks(long long n) {
   long long b = (n + MT * 8 - 1) / (MT * 8);
   return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 size_t workspace_bytes(bool masked, int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;

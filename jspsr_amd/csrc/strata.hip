@@ -10,9 +10,12 @@
 //       select    8 bits per pass, every pass serving ALL classes at once: n_classes x {4, 2} x 256 LDS counters (the two
 //                 ranks of a statistic are two states whose prefixes may diverge), the class of an element picks the
 //                 histogram and the prefixes it is compared with (kept in LDS, read per lane);
-//       scan      a workgroup per (candidate, class), K18's scan.  The class count n_c is the sum of the class's top-digit
-//                 histogram of e (integers, exact), so the ranks, the LE95 weight and the divisor of the sum are formed
-//                 there by segment_ranks_of (summary_select.h), the inline K18 uses.
+//       scan      a workgroup per (candidate, class): rank_scan (summary_select.h), the scan K12 and K18 run, behind an
+//                 init block of its own.  The class count n_c is the sum of the class's top-digit histogram of e
+//                 (integers, exact), so the ranks, the LE95 weight and the divisor of the sum are formed there by
+//                 segment_ranks_of, the inline K18 uses.
+//     The window reader (pooled_fetch), the candidates' Buffers and their check are csrc/pooled_read.h's; the labels and
+//     the validity plane are this kernel's own arguments, read at the ground truth's index the reader hands over.
 //     16 launches whatever n_classes, n_cand, the windows and the data are.  Integer adds only in the histograms, and every
 //     fp64 sum is folded in an order the pool's size alone fixes: a row has the same bits for every n_cand, whatever the
 //     other classes hold, on every run.  Hot counters take hist_add's ballot-aggregated increments: one class routinely
@@ -23,6 +26,7 @@
 //     scene table; the nine taps are replicate-clamped inside that scene; Sobel in single roundings (explicit __f*_rn and
 //     -ffp-contract=off), p = gx^2 + gy^2 compared with the caller's thresholds: no atan on the device.
 #include "common.h"
+#include "pooled_read.h"
 #include "summary_select.h"
 
 #include <cmath>
@@ -31,41 +35,21 @@ namespace {
 
 using namespace jspsr;
 
-constexpr int MT = 256;
+constexpr int MT = SCAN_MT;
 constexpr int UNROLL = 4;
 constexpr int RUN = 8192;                     // pooled elements per workgroup and per fp64 partial sum (jspsr_amd/summary.py: CHUNK)
-constexpr int NSTATE = 6;                     // ranks: median lo, hi | LE95 lo, hi | MAD lo, hi
-constexpr int NOUT = 11;
-constexpr int MAXC = 8;
 constexpr int MAXK = 32;                      // classes
 constexpr int NONE = 255;                     // the class byte of an element that belongs to no class
-constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // K12's window row: segment (not read), h, w, e offset, {offset, pitch} of gt, cand 0..7
 constexpr int MAXT = 31;                      // slope thresholds
 static_assert(RUN % (MT * UNROLL) == 0, "a run is a whole number of unrolled steps");
 
-struct RowState {            // one per (candidate, class), in device memory; 64 bytes (csrc/summary.hip's)
-  unsigned prefix[NSTATE];   // key bits fixed so far (high bits)
-  unsigned k[NSTATE];        // rank still to find inside the current prefix class (0-based)
-  float center;              // the median, for |e - median|
-  unsigned has_nan;          // bit 0: the fp64 sum is NaN; bit 1: the class is empty
-  unsigned g[2];             // the bits of the LE95 weight
-};
-static_assert(sizeof(RowState) == 64, "RowState layout");
-
-struct Buffers {             // by value in the kernel arguments
-  const float* cand[MAXC];
-  long long cand_numel[MAXC];
-  const float* gt;
-  long long gt_numel;
-  const unsigned char* labels;   // gt's layout and numel
-  const unsigned char* valid;    // gt's layout and numel, or null
-};
-
+// labels, valid: planes in gt's layout and numel (checked by the entry); valid may be null
 // LDS of prepare: n_classes x { 2 x 256 counters, 256 doubles }; of select: n_classes x slots x 256 counters
-__global__ __launch_bounds__(MT) void strata_prepare_kernel(Buffers B, const long long* __restrict__ win, int n_win, long long total,
-                                                           long long n_runs, int n_classes, int reps, float* __restrict__ e_all,
-                                                           unsigned char* __restrict__ cls_all, double* __restrict__ partial,
-                                                           unsigned* __restrict__ hist) {
+__global__ __launch_bounds__(MT) void strata_prepare_kernel(Buffers B, const unsigned char* __restrict__ labels,
+                                                           const unsigned char* __restrict__ valid, const long long* __restrict__ win,
+                                                           int n_win, long long total, long long n_runs, int n_classes, int reps,
+                                                           float* __restrict__ e_all, unsigned char* __restrict__ cls_all,
+                                                           double* __restrict__ partial, unsigned* __restrict__ hist) {
   extern __shared__ double dyn[];
   __shared__ double red[MAXK][MT / 64];
   double* __restrict__ sums = dyn;                                            // [n_classes][MT]
@@ -76,12 +60,8 @@ __global__ __launch_bounds__(MT) void strata_prepare_kernel(Buffers B, const lon
   __syncthreads();
   const long long lo = (long long)blockIdx.x * RUN;
   const long long hi = lo + RUN < total ? lo + RUN : total;                   // lo < total: the grid is n_runs wide
-  const float* __restrict__ cp = B.cand[c];
-  const float* __restrict__ gp = B.gt;
-  const long long cn = B.cand_numel[c], gn = B.gt_numel;
   float* __restrict__ e = e_all + (size_t)c * total;
-  long long w_lo = 0, w_hi = 0, w_w = 1, goff = 0, gpitch = 0, coff = 0, cpitch = 0;   // the window of the last element
-  bool w_ok = false;
+  WindowCursor W(B, c);
   for (long long base = lo; base < hi; base += MT * UNROLL) {
     float err[UNROLL];
     int cls[UNROLL];
@@ -91,31 +71,13 @@ __global__ __launch_bounds__(MT) void strata_prepare_kernel(Buffers B, const lon
       cls[u] = NONE;
       err[u] = 0.f;
       if (p >= hi) continue;
-      if (p < w_lo || p >= w_hi) {
-        const long long* wr = win + (size_t)find_row(win, n_win, WIN_WORDS, 3, p) * WIN_WORDS;
-        w_w = wr[2];
-        w_lo = wr[3];
-        w_hi = w_lo + wr[1] * w_w;
-        w_ok = wr[1] > 0 && w_w > 0;
-        goff = wr[4]; gpitch = wr[5];
-        coff = wr[6 + 2 * c]; cpitch = wr[7 + 2 * c];
-      }
-      float v = __builtin_nanf("");                             // an element no window covers, or a read outside a buffer:
-      int k = 0;                                                // a NaN of class 0, so that a bad table shows (K12 does the same)
-      if (w_ok && p >= w_lo && p < w_hi) {
-        const long long local = p - w_lo;
-        long long y;
-        if (local < 0x100000000ll && w_w < 0x100000000ll) y = (long long)((unsigned)local / (unsigned)w_w);   // the usual case
-        else y = local / w_w;
-        const long long x = local - y * w_w;
-        const long long jc = coff + y * cpitch + x, jg = goff + y * gpitch + x;
-        if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) {
-          v = __fsub_rn(cp[jc], gp[jg]);
-          k = B.labels[jg];                                       // the planes have gt's numel (checked by the entry)
-          if (k >= n_classes) k = NONE;
-          if (B.valid != nullptr && B.valid[jg] == 0) k = NONE;
-        }
-      }
+      float v;                                                  // a NaN: an element no window covers, or a read outside a buffer:
+      int k = 0;                                                // ... of class 0, so that a bad table shows (K12 does the same)
+      pooled_fetch(W, win, n_win, p, v, [&](long long jg) {
+        k = labels[jg];
+        if (k >= n_classes) k = NONE;
+        if (valid != nullptr && valid[jg] == 0) k = NONE;
+      });
       if (k == NONE) v = 0.f;                                     // whatever cand and gt hold there: it is never looked at again
       cls[u] = k;
       err[u] = v;
@@ -218,8 +180,9 @@ __global__ __launch_bounds__(MT) void strata_select_kernel(const float* __restri
   }
 }
 
-// One workgroup per (candidate, class), a wave per state: csrc/summary.hip's masked scan with the count taken from the
-// class's top-digit histogram of e.  init: the first scan of a call -- n_c, the ranks, RMSE / PSNR from the run sums.
+// One workgroup per (candidate, class): rank_scan (summary_select.h) behind this kernel's own init block.  init: the
+// first scan of a call -- n_c from the class's top-digit histogram of e, the ranks formed from it, RMSE / PSNR from the
+// run sums.
 __global__ __launch_bounds__(MT) void strata_scan_kernel(const double* __restrict__ partial, long long n_runs, int n_classes, int reps,
                                                         int group, int pass, int init, double value_max, RowState* __restrict__ st,
                                                         unsigned* __restrict__ hist, float* __restrict__ out,
@@ -275,83 +238,7 @@ __global__ __launch_bounds__(MT) void strata_scan_kernel(const double* __restric
     cur.has_nan = ((t != t) ? 1u : 0u) | (n_v < 1 ? 2u : 0u);
   }
   if (init) __syncthreads();                                     // kernel-uniform: the ranks were written after the barrier above
-  // a wave per state
-  const int q = (group ? 4 : 0) + wave, ql = q & ~1;
-  const bool active = group ? wave < 2 : true;
-  const int shift = pass * 8;
-  const unsigned himask = pass == 3 ? 0u : (0xffffffffu << (shift + 8));
-  unsigned new_prefix = 0u, new_k = 0u;
-  bool found = false;
-  if (active) {
-    const unsigned prefix = cur.prefix[q], k = cur.k[q];
-    const bool same = ((prefix ^ cur.prefix[ql]) & himask) == 0u;       // counted once, under the pair's lower state
-    const unsigned* h = hrow + (same ? ql : q) * 256 + 4 * lane;         // lane l owns bins 4l .. 4l+3
-    unsigned c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u;
-    for (int r = 0; r < reps; ++r) {
-      const uint4 v = *reinterpret_cast<const uint4*>(h + (size_t)r * NSTATE * 256);
-      c0 += v.x; c1 += v.y; c2 += v.z; c3 += v.w;
-    }
-    const unsigned own = c0 + c1 + c2 + c3;
-    unsigned incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned up = (unsigned)__shfl_up((int)incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    const unsigned excl = incl - own;
-    if (k >= excl && k < incl) {                                 // exactly one lane: the counts sum to more than k (none: an empty class)
-      unsigned run = excl;
-      int b = 0;
-      if (k >= run + c0) { run += c0; b = 1;
-        if (k >= run + c1) { run += c1; b = 2;
-          if (k >= run + c2) { run += c2; b = 3; } } }
-      new_k = k - run;
-      new_prefix = prefix | ((unsigned)(4 * lane + b) << shift);
-      found = true;
-    }
-  }
-  __syncthreads();                                               // every wave has read the states and its histogram
-  if (found) { cur.prefix[q] = new_prefix; cur.k[q] = new_k; }
-  {                                                              // clear what this group's passes count into: states 0..3 or 4, 5
-    const int first = group ? 4 : 0, quads = (group ? 2 : 4) * 64; // uint4 per replica
-    for (int i = tid; i < reps * quads; i += MT)
-      reinterpret_cast<uint4*>(hrow + ((size_t)(i / quads) * NSTATE + first) * 256)[i % quads] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  if (pass == 0 && tid == 0) {
-    const float nanv = __builtin_nanf("");
-    const bool bad = cur.has_nan != 0u, empty = (cur.has_nan & 2u) != 0u;
-    if (!group) {
-      const float m0 = key_value(cur.prefix[0]), m1 = key_value(cur.prefix[1]);
-      const float l0 = key_value(cur.prefix[2]), l1 = key_value(cur.prefix[3]);
-      const float med = __fmul_rn(__fadd_rn(m0, m1), 0.5f);      // np.median of a float32 array: mean of the two middle elements
-      double g;
-      __builtin_memcpy(&g, cur.g, 8);
-      const float le = (float)((double)l0 + ((double)l1 - (double)l0) * g);
-      cur.center = med;
-      o[1] = bad ? nanv : med;
-      o[3] = bad ? nanv : le;
-      o[5] = empty ? nanv : m0; o[6] = empty ? nanv : m1; o[9] = empty ? nanv : l0; o[10] = empty ? nanv : l1;
-      if (bad) { o[0] = nanv; o[4] = nanv; }
-    } else {
-      const float d0 = key_value(cur.prefix[4]), d1 = key_value(cur.prefix[5]);
-      const float mad = __fmul_rn(__fadd_rn(d0, d1), 0.5f);
-      o[2] = bad ? nanv : (float)(1.4826 * (double)mad);
-      o[7] = empty ? nanv : d0; o[8] = empty ? nanv : d1;
-    }
-  }
-  __syncthreads();
-  if (tid < (int)(sizeof(RowState) / 4)) reinterpret_cast<unsigned*>(st + row)[tid] = reinterpret_cast<const unsigned*>(&cur)[tid];
-}
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// Replicas of a row's histograms (csrc/summary.hip: hist_replicas): run r adds to replica r % reps, the scan sums them.  A
-// power of two, at most 16, one per 64 runs of the pool.
-int hist_replicas(long long n_runs) {
-  int r = 1;
-  while (r < 16 && (long long)r * 64 < n_runs) r *= 2;
-  return r;
+  rank_scan(cur, cur.g, hrow, reps, group, pass, o, st + row);
 }
 
 bool sizes_ok(int n_cand, int n_classes, long long total) {
@@ -408,7 +295,7 @@ extern "C" size_t jspsr_strata_workspace_bytes(int n_cand, int n_classes, long l
   const long long n_runs = (total + RUN - 1) / RUN;
   const size_t rows = (size_t)n_cand * n_classes;
   return up16((size_t)n_cand * total * sizeof(float)) + up16((size_t)n_cand * n_runs * n_classes * sizeof(double)) +
-         rows * hist_replicas(n_runs) * NSTATE * 256 * sizeof(unsigned) + rows * sizeof(RowState) + 64 + up16((size_t)total);
+         rows * hist_replicas(rows, n_runs) * NSTATE * 256 * sizeof(unsigned) + rows * sizeof(RowState) + 64 + up16((size_t)total);
 }
 
 extern "C" int jspsr_strata_forward(const float* const* cands, const long long* cand_numel, int n_cand, const float* gt,
@@ -427,22 +314,13 @@ extern "C" int jspsr_strata_forward(const float* const* cands, const long long* 
     return fail(JSPSR_EINVAL, "%s: the validity plane has %lld elements, the ground truth %lld", name, valid_numel, gt_numel);
   if (total >= 0x100000000ll) return fail(JSPSR_EINVAL, "%s: %lld pooled elements, the rank counters hold fewer than 2^32", name, total);
   Buffers B;
-  for (int c = 0; c < MAXC; ++c) {
-    B.cand[c] = c < n_cand ? cands[c] : nullptr;
-    B.cand_numel[c] = c < n_cand ? cand_numel[c] : 0;
-    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "%s: candidate %d is null or empty", name, c);
-    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "%s: candidate %d not 4-byte aligned", name, c);
-  }
-  B.gt = gt;
-  B.gt_numel = gt_numel;
-  B.labels = labels;
-  B.valid = valid;
+  if (int err = pack_buffers(name, cands, cand_numel, n_cand, gt, gt_numel, B)) return err;
   if (!aligned4(gt) || !aligned4(out)) return fail(JSPSR_EALIGN, "%s: tensors not 4-byte aligned", name);
   if (reinterpret_cast<uintptr_t>(counts) & 7u) return fail(JSPSR_EALIGN, "%s: counts not 8-byte aligned", name);
   if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", name);
   const long long n_runs = (total + RUN - 1) / RUN;
   const size_t rows = (size_t)n_cand * n_classes;
-  const int reps = hist_replicas(n_runs);
+  const int reps = hist_replicas(rows, n_runs);
   char* ws = static_cast<char*>(workspace);
   float* e = reinterpret_cast<float*>(ws);
   size_t off = up16((size_t)n_cand * total * sizeof(float));
@@ -468,8 +346,8 @@ extern "C" int jspsr_strata_forward(const float* const* cands, const long long* 
   if (hipMemsetAsync(hist, 0, hist_bytes, s) != hipSuccess)
     return fail(JSPSR_EINVAL, "%s: clearing the histograms failed: %s", name, hipGetErrorString(hipGetLastError()));
   const dim3 grid((unsigned)n_runs, n_cand);
-  hipLaunchKernelGGL(strata_prepare_kernel, grid, dim3(MT), lds_prepare, s, B, windows, n_windows, total, n_runs, n_classes, reps, e, cls,
-                     partial, hist);
+  hipLaunchKernelGGL(strata_prepare_kernel, grid, dim3(MT), lds_prepare, s, B, labels, valid, windows, n_windows, total, n_runs, n_classes,
+                     reps, e, cls, partial, hist);
   if (int err = check_launch("strata_prepare")) return err;
   for (int group = 0; group < 2; ++group) {
     for (int pass = 3; pass >= 0; --pass) {

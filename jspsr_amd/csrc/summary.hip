@@ -10,17 +10,19 @@
 //     clamp -> descale_data -> + base -> merge_tiles run scene by scene.
 // (b) jspsr_summary_forward: pooled scores of n_cand candidates against one ground truth over a table of pitched
 //     windows grouped into segments.  A streaming selection:
-//       prepare   reads the candidate and the ground truth through the window table, writes e = cand - gt once
-//                 (candidate-major, a segment's windows back to back), folds sum e^2 in double per CHUNK of a segment and
-//                 counts the top digit of the keys of e and |e|;
-//       select    8 bits per pass on the order-preserving keys of csrc/metrics.hip.  Both ranks of a statistic are
+//       prepare   reads the candidate and the ground truth through the window table (pooled_read.h: the reader K21 and
+//                 K22 use too), writes e = cand - gt once (candidate-major, a segment's windows back to back), folds
+//                 sum e^2 in double per CHUNK of a segment and counts the top digit of the keys of e and |e|;
+//       select    8 bits per pass on the order-preserving keys of summary_select.h.  Both ranks of a statistic are
 //                 carried as two states whose prefixes may diverge (while they agree, one histogram serves both); the
 //                 median and the LE95 select share each read of e; the |e - median| select follows.
 //     16 launches whatever the number of windows, segments and candidates is: prepare, 4 scans + 3 reads of e for the
 //     median / LE95 digits, 4 + 4 for the MAD.  A workgroup owns one CHUNK of one segment, so every sum is folded in an
 //     order that depends on the segment's own size only: a row has the same bits for every n_cand, for every set of
 //     other segments in the call, on every run.  The workgroups of a row flush their LDS counts into one of up to 16
-//     replicas of the row's counters (hist_replicas): global adds to one address serialise.
+//     replicas of the row's counters (hist_replicas): global adds to one address serialise.  The scan kernel is its
+//     own init block (where the count and the fp64 sum come from) in front of rank_scan (summary_select.h), the part
+//     K22's scan shares: the rank search, the clear of the replicas, the scores, the state write-back.
 // (c) jspsr_summary_valid_forward (K18): (b) over the elements a validity plane in the ground truth's layout keeps.  The
 //     three kernels are templates on MASKED; the unmasked instances are (b) as it was.  prepare reads the plane through
 //     the window table, keeps a validity byte per pooled element (written once, by the workgroups of candidate 0, read
@@ -36,6 +38,7 @@
 // (not numpy's fp32 pairwise mean); LE95's virtual index in double (numpy 2 forms it in float32 for float32 input); PSNR
 // without the 1e-8 the reference's online form adds for the baselines.
 #include "common.h"
+#include "pooled_read.h"
 #include "summary_select.h"
 
 #include <cmath>
@@ -44,18 +47,11 @@ namespace {
 
 using namespace jspsr;
 
-constexpr int MT = 256;
+constexpr int MT = SCAN_MT;
 constexpr int UNROLL = 4;
 constexpr int CHUNK = 8192;                   // elements of a segment per workgroup (jspsr_amd/summary.py: CHUNK)
-constexpr int NSTATE = 6;                     // ranks: median lo, hi | LE95 lo, hi | MAD lo, hi
-constexpr int NOUT = 11;                      // RMSE, Median, NMAD, LE95, PSNR, med lo, hi, mad lo, hi, le lo, hi
-constexpr int MAXC = 8;
-constexpr int WIN_WORDS = 4 + 2 * (1 + MAXC); // segment, h, w, e offset, {offset, pitch} of gt, cand 0..7
 constexpr int SEG_WORDS = 8;                  // e start, n, first chunk, 4 ranks, g (fp64 bits)
 static_assert(CHUNK % (MT * UNROLL) == 0, "a chunk is a whole number of unrolled steps");
-
-// Ranks / segment_ranks_of, order_key, key_value, wave_sum, hist_add and find_row: summary_select.h (shared with K22,
-// csrc/strata.hip).
 
 // ---- (a) scene assembly --------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ramp_weight(const float* __restrict__ ramp, int p, int w_l_c, int n_x, int pos, int j) {
@@ -109,22 +105,6 @@ __global__ __launch_bounds__(256) void scenes_assemble_kernel(const float* __res
 }
 
 // ---- (b) pooled scores ---------------------------------------------------------------------------------------------
-struct RowState {            // one per (candidate, segment), in device memory; 64 bytes
-  unsigned prefix[NSTATE];   // key bits fixed so far (high bits)
-  unsigned k[NSTATE];        // rank still to find inside the current prefix class (0-based)
-  float center;              // the median, for |e - median|
-  unsigned has_nan;          // bit 0: the fp64 sum is NaN, a NaN among the errors; bit 1 (K18): no valid element
-  unsigned pad[2];           // K18: the bits of the LE95 weight g (the unmasked form reads it from the segment table)
-};
-static_assert(sizeof(RowState) == 64, "RowState layout");
-
-struct Buffers {             // by value in the kernel arguments
-  const float* cand[MAXC];
-  long long cand_numel[MAXC];
-  const float* gt;
-  long long gt_numel;
-};
-
 struct Mask {                // K18, by value in the kernel arguments; all null in the unmasked instances, never read there
   const unsigned char* plane;  // the validity plane, the ground truth's layout and numel
   unsigned char* keep;         // [total] a byte per pooled element, the layout of one candidate's e
@@ -162,12 +142,8 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, Mask K, 
   long long e_start, lo, hi;
   if (!my_chunk(seg, n_seg, total, reps, s, e_start, lo, hi, rep)) return;      // workgroup-uniform
   __syncthreads();
-  const float* __restrict__ cp = B.cand[c];
-  const float* __restrict__ gp = B.gt;
-  const long long cn = B.cand_numel[c], gn = B.gt_numel;
   float* __restrict__ e = e_all + (size_t)c * total;
-  long long w_lo = 0, w_hi = 0, w_w = 1, goff = 0, gpitch = 0, coff = 0, cpitch = 0;   // the window of the last element
-  bool w_ok = false;
+  WindowCursor W(B, c);
   double sum = 0.0;
   unsigned kept = 0u;                                           // MASKED: valid elements this thread has seen
   for (long long base = lo; base < hi; base += MT * UNROLL) {
@@ -180,29 +156,11 @@ __global__ __launch_bounds__(MT) void summary_prepare_kernel(Buffers B, Mask K, 
       err[u] = 0.f;
       if (!valid[u]) continue;
       const long long p = e_start + i;
-      if (p < w_lo || p >= w_hi) {
-        const long long* wr = win + (size_t)find_row(win, n_win, WIN_WORDS, 3, p) * WIN_WORDS;
-        w_w = wr[2];
-        w_lo = wr[3];
-        w_hi = w_lo + wr[1] * w_w;
-        w_ok = wr[0] == s && wr[1] > 0 && w_w > 0;
-        goff = wr[4]; gpitch = wr[5];
-        coff = wr[6 + 2 * c]; cpitch = wr[7 + 2 * c];
-      }
-      float v = __builtin_nanf("");                             // an element no window covers, or a read outside a buffer
+      float v;                                                  // a NaN: an element no window of segment s covers, or a read outside a buffer
       bool keep = true;                                         // ... counts as valid: the row turns NaN, as without a mask
-      if (w_ok && p >= w_lo && p < w_hi) {
-        const long long local = p - w_lo;
-        long long y;
-        if (local < 0x100000000ll && w_w < 0x100000000ll) y = (long long)((unsigned)local / (unsigned)w_w);   // the usual case: a 32-bit division
-        else y = local / w_w;
-        const long long x = local - y * w_w;
-        const long long jc = coff + y * cpitch + x, jg = goff + y * gpitch + x;
-        if (jc >= 0 && jc < cn && jg >= 0 && jg < gn) {
-          v = __fsub_rn(cp[jc], gp[jg]);
-          if constexpr (MASKED) keep = K.plane[jg] != 0;          // the plane has gt's numel (checked by the entry)
-        }
-      }
+      pooled_fetch(W, win, n_win, p, v, [&](long long jg) {
+        if constexpr (MASKED) keep = K.plane[jg] != 0;            // the plane has gt's numel (checked by the entry)
+      }, s);
       if constexpr (MASKED) {
         if (!keep) v = 0.f;                                     // whatever cand and gt hold there: it is never looked at again
         if (c == 0) K.keep[p] = keep ? 1 : 0;
@@ -300,9 +258,9 @@ __global__ __launch_bounds__(MT) void summary_select_kernel(const float* __restr
     if (lh[q][tid]) atomicAdd(&hrow[(q0 + q) * 256 + tid], lh[q][tid]);
 }
 
-// One workgroup per (candidate, segment), a wave per state: find the bin holding the state's rank, fix its byte, reduce
-// the rank; clear the row's histograms.  init: the first scan of a call -- the states come from the segment table and
-// RMSE / PSNR from the chunk sums, folded in chunk order.  After byte 0 the keys are complete: the scores are written.
+// One workgroup per (candidate, segment): rank_scan (summary_select.h) behind this kernel's own init block.  init: the
+// first scan of a call -- RMSE / PSNR from the chunk sums, folded in chunk order; the count, the ranks and the LE95 weight
+// from the segment table, or (MASKED) the count from the chunk counts and the ranks formed here from it.
 template <bool MASKED>
 __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restrict__ partial, Mask K, long long total_chunks,
                                                          const long long* __restrict__ seg, int n_seg, int reps, int group,
@@ -329,7 +287,7 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
       }
       cur.center = 0.f;
       cur.has_nan = 0u;
-      cur.pad[0] = cur.pad[1] = 0u;
+      cur.g[0] = cur.g[1] = 0u;
     }
     const long long nchunks = (n + CHUNK - 1) / CHUNK;
     const double* src = partial + (size_t)c * total_chunks + sg[2];
@@ -365,7 +323,7 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
         cur.k[1] = cur.k[5] = (unsigned)r.m1;
         cur.k[2] = (unsigned)r.l0;
         cur.k[3] = (unsigned)r.l1;
-        __builtin_memcpy(cur.pad, &r.g, 8);
+        __builtin_memcpy(cur.g, &r.g, 8);
       } else {                                                   // every histogram of the row stays empty: no lane finds a rank
         for (int q = 0; q < NSTATE; ++q) cur.k[q] = 0u;
       }
@@ -379,96 +337,7 @@ __global__ __launch_bounds__(MT) void summary_scan_kernel(const double* __restri
   if constexpr (MASKED) {
     if (init) __syncthreads();                                   // kernel-uniform: the ranks were written after the barrier above
   }
-  // a wave per state
-  const int q = (group ? 4 : 0) + wave, ql = q & ~1;
-  const bool active = group ? wave < 2 : true;
-  const int shift = pass * 8;
-  const unsigned himask = pass == 3 ? 0u : (0xffffffffu << (shift + 8));
-  unsigned new_prefix = 0u, new_k = 0u;
-  bool found = false;
-  if (active) {
-    const unsigned prefix = cur.prefix[q], k = cur.k[q];
-    const bool same = ((prefix ^ cur.prefix[ql]) & himask) == 0u;       // counted once, under the pair's lower state
-    const unsigned* h = hrow + (same ? ql : q) * 256 + 4 * lane;         // lane l owns bins 4l .. 4l+3
-    unsigned c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u;
-    for (int r = 0; r < reps; ++r) {
-      const uint4 v = *reinterpret_cast<const uint4*>(h + (size_t)r * NSTATE * 256);
-      c0 += v.x; c1 += v.y; c2 += v.z; c3 += v.w;
-    }
-    const unsigned own = c0 + c1 + c2 + c3;
-    unsigned incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned up = (unsigned)__shfl_up((int)incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    const unsigned excl = incl - own;
-    if (k >= excl && k < incl) {                                 // exactly one lane: the counts sum to more than k (none: n_v = 0)
-      unsigned run = excl;
-      int b = 0;
-      if (k >= run + c0) { run += c0; b = 1;
-        if (k >= run + c1) { run += c1; b = 2;
-          if (k >= run + c2) { run += c2; b = 3; } } }
-      new_k = k - run;
-      new_prefix = prefix | ((unsigned)(4 * lane + b) << shift);
-      found = true;
-    }
-  }
-  __syncthreads();                                               // every wave has read the states and its histogram
-  if (found) { cur.prefix[q] = new_prefix; cur.k[q] = new_k; }
-  {                                                              // clear what this group's passes count into: states 0..3 or 4, 5
-    const int first = group ? 4 : 0, quads = (group ? 2 : 4) * 64; // uint4 per replica
-    for (int i = tid; i < reps * quads; i += MT)
-      reinterpret_cast<uint4*>(hrow + ((size_t)(i / quads) * NSTATE + first) * 256)[i % quads] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  if (pass == 0 && tid == 0) {
-    const float nanv = __builtin_nanf("");
-    const bool bad = cur.has_nan != 0u;
-    if (!group) {
-      const float m0 = key_value(cur.prefix[0]), m1 = key_value(cur.prefix[1]);
-      const float l0 = key_value(cur.prefix[2]), l1 = key_value(cur.prefix[3]);
-      const float med = __fmul_rn(__fadd_rn(m0, m1), 0.5f);      // np.median of a float32 array: mean of the two middle elements
-      double g;
-      if constexpr (MASKED) {
-        __builtin_memcpy(&g, cur.pad, 8);
-      } else {
-        const long long gb = sg[7];
-        __builtin_memcpy(&g, &gb, 8);
-      }
-      const float le = (float)((double)l0 + ((double)l1 - (double)l0) * g);
-      cur.center = med;
-      o[1] = bad ? nanv : med;
-      o[3] = bad ? nanv : le;
-      o[5] = m0; o[6] = m1; o[9] = l0; o[10] = l1;
-      if (bad) { o[0] = nanv; o[4] = nanv; }
-      if constexpr (MASKED) {
-        if (cur.has_nan & 2u) { o[5] = nanv; o[6] = nanv; o[9] = nanv; o[10] = nanv; }
-      }
-    } else {
-      const float d0 = key_value(cur.prefix[4]), d1 = key_value(cur.prefix[5]);
-      const float mad = __fmul_rn(__fadd_rn(d0, d1), 0.5f);
-      o[2] = bad ? nanv : (float)(1.4826 * (double)mad);
-      o[7] = d0; o[8] = d1;
-      if constexpr (MASKED) {
-        if (cur.has_nan & 2u) { o[7] = nanv; o[8] = nanv; }
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < (int)(sizeof(RowState) / 4)) reinterpret_cast<unsigned*>(st + row)[tid] = reinterpret_cast<const unsigned*>(&cur)[tid];
-}
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// Replicas of a row's histograms.  Every workgroup of a row ends in global adds to the row's 256 counters per state; to one
-// address they serialise, and a 4096 x 4096 segment has 2048 workgroups.  Chunk c of a segment adds to replica c % reps,
-// the scan sums the replicas: integer counts, so the result does not depend on reps.  A power of two, at most 16, one per
-// 64 chunks of the call, and at most 64 MiB of counters.
-int hist_replicas(size_t rows, long long total_chunks) {
-  int r = 1;
-  while (r < 16 && (long long)r * 64 < total_chunks && rows * (size_t)(2 * r) * NSTATE * 256 * sizeof(unsigned) <= ((size_t)64 << 20)) r *= 2;
-  return r;
+  rank_scan(cur, MASKED ? static_cast<const void*>(cur.g) : static_cast<const void*>(sg + 7), hrow, reps, group, pass, o, st + row);
 }
 
 bool sizes_ok(int n_cand, int n_segments, long long total, long long total_chunks) {
@@ -535,14 +404,7 @@ int summary_run(const char* name, const float* const* cands, const long long* ca
                 n_segments, total, total_chunks);
   if ((long long)n_cand * n_segments > 0x7fffffffll) return fail(JSPSR_EINVAL, "%s: too many rows", name);
   Buffers B;
-  for (int c = 0; c < MAXC; ++c) {
-    B.cand[c] = c < n_cand ? cands[c] : nullptr;
-    B.cand_numel[c] = c < n_cand ? cand_numel[c] : 0;
-    if (c < n_cand && (!cands[c] || cand_numel[c] <= 0)) return fail(JSPSR_EINVAL, "%s: candidate %d is null or empty", name, c);
-    if (c < n_cand && !aligned4(cands[c])) return fail(JSPSR_EALIGN, "%s: candidate %d not 4-byte aligned", name, c);
-  }
-  B.gt = gt;
-  B.gt_numel = gt_numel;
+  if (int err = pack_buffers(name, cands, cand_numel, n_cand, gt, gt_numel, B)) return err;
   if (!aligned4(gt) || !aligned4(out)) return fail(JSPSR_EALIGN, "%s: tensors not 4-byte aligned", name);
   if (MASKED && (reinterpret_cast<uintptr_t>(counts) & 7u)) return fail(JSPSR_EALIGN, "%s: counts not 8-byte aligned", name);
   if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", name);

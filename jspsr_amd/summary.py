@@ -128,6 +128,50 @@ def _check_pool(what, cands, gt, windows, valid):
     return total
 
 
+def _window_table(windows, keep_segment: bool) -> np.ndarray:
+    """The (n, _WIN_WORDS) int64 window rows the pooled kernels read (csrc/pooled_read.h): segment (0 unless keep_segment),
+    h, w, the running offset of the window's first element in e, {offset, pitch} of gt and of each candidate; the slots of
+    candidates not given stay 0."""
+    tab = np.zeros((len(windows), _WIN_WORDS), dtype=np.int64)
+    e_off = 0
+    for i, (sg, h, w, (go, gp), cs) in enumerate(windows):
+        tab[i, :6] = (sg if keep_segment else 0, h, w, e_off, go, gp)
+        for c, (co, cp) in enumerate(cs):
+            tab[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
+        e_off += h * w
+    return tab
+
+
+def _upload(tab: np.ndarray, dev) -> torch.Tensor:
+    """One stream-ordered upload from a pinned buffer that is never written again."""
+    host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)
+    host.numpy()[...] = tab
+    return host.to(dev, non_blocking=True)
+
+
+def _cand_arrays(cands):
+    """-> the candidates' (pointer array, numel array) as the C entries take them."""
+    n = len(cands)
+    return (ctypes.c_void_p * n)(*[c.data_ptr() for c in cands]), (ctypes.c_longlong * n)(*[c.numel() for c in cands])
+
+
+def _window_index(h, w, off, pitch):
+    return off + np.arange(h)[:, None] * pitch + np.arange(w)[None, :]
+
+
+def _gather_plane(plane: np.ndarray, windows):
+    """A plane in gt's layout through a window list -> one flat array per window."""
+    return [plane[_window_index(h, w, go, gp)].reshape(-1) for _, h, w, (go, gp), _ in windows]
+
+
+def _gather_errors(c_np: np.ndarray, g_np: np.ndarray, windows, c: int):
+    """Candidate c's cand - gt through a window list -> one flat array per window (the fp32 subtraction; the callers
+    concatenate and then `astype(np.float32, copy=False)`)."""
+    with np.errstate(invalid="ignore"):                         # inf - inf at an element that is not scored
+        return [(c_np[_window_index(h, w, *cs[c])] - g_np[_window_index(h, w, go, gp)]).reshape(-1)
+                for _, h, w, (go, gp), cs in windows]
+
+
 def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequence[tuple], n_segments: int, value_max: float,
                 valid: torch.Tensor | None = None):
     """The raw table call.  cands: 1..8 flat fp32 buffers, gt one, all on one device; windows: (segment, h, w, (gt offset,
@@ -151,30 +195,23 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
     if min(seg_n) == 0:
         raise ValueError("pooled_rows: a segment without windows")
     total = sum(seg_n)
+    windows = [windows[i] for i in order]                         # a segment's windows back to back
     if gt.is_cuda:
-        return _pooled_device(cands, gt, [windows[i] for i in order], seg_n, total, value_max, valid)
+        return _pooled_device(cands, gt, windows, seg_n, total, value_max, valid)
     out = np.empty((n_cand, n_segments, len(ROW)), dtype=np.float32)
     g_np = gt.numpy()
+    ends = np.cumsum(np.bincount([wdw[0] for wdw in windows], minlength=n_segments))
+
+    def per_segment(parts):                                       # one flat array per window -> one per segment
+        return [np.concatenate(parts[a:b]) for a, b in zip([0] + list(ends[:-1]), ends)]
+
     keep = None
     if valid is not None:
-        v_np = valid.numpy()
-        keep = [[] for _ in range(n_segments)]
-        for i in order:
-            sg, h, w, (go, gp), _ = windows[i]
-            keep[sg].append(v_np[go + np.arange(h)[:, None] * gp + np.arange(w)[None, :]].reshape(-1) != 0)
-        keep = [np.concatenate(k) for k in keep]
+        keep = [k != 0 for k in per_segment(_gather_plane(valid.numpy(), windows))]
     for c, cand in enumerate(cands):
-        c_np = cand.numpy()
-        parts = [[] for _ in range(n_segments)]
-        for i in order:
-            sg, h, w, (go, gp), cs = windows[i]
-            co, cp = cs[c]
-            rows = np.arange(h)[:, None]
-            cols = np.arange(w)[None, :]
-            with np.errstate(invalid="ignore"):                 # inf - inf under a mask
-                parts[sg].append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
+        parts = per_segment(_gather_errors(cand.numpy(), g_np, windows, c))
         for sg in range(n_segments):
-            e = np.concatenate(parts[sg]).astype(np.float32, copy=False)
+            e = parts[sg].astype(np.float32, copy=False)
             if keep is not None:
                 e = e[keep[sg]]
             out[c, sg] = _row_host(e, value_max) if e.size else _nan_row()
@@ -185,15 +222,7 @@ def pooled_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Sequen
 
 def _pooled_device(cands, gt, windows, seg_n, total, value_max, valid=None):
     n_cand, n_seg, n_win = len(cands), len(seg_n), len(windows)
-    tab = np.zeros(n_win * _WIN_WORDS + n_seg * _SEG_WORDS, dtype=np.int64)
-    win = tab[:n_win * _WIN_WORDS].reshape(n_win, _WIN_WORDS)
-    seg = tab[n_win * _WIN_WORDS:].reshape(n_seg, _SEG_WORDS)
-    e_off = 0
-    for i, (sg, h, w, (go, gp), cs) in enumerate(windows):
-        win[i, :6] = (sg, h, w, e_off, go, gp)
-        for c, (co, cp) in enumerate(cs):
-            win[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
-        e_off += h * w
+    seg = np.zeros((n_seg, _SEG_WORDS), dtype=np.int64)
     start = chunk = 0
     for sg, n in enumerate(seg_n):
         m0, m1, l0, l1, g = segment_ranks(n)
@@ -207,13 +236,10 @@ def _pooled_device(cands, gt, windows, seg_n, total, value_max, valid=None):
         raise ValueError(f"pooled_rows: {n_cand} candidates, {n_seg} segments, {total} pooled elements: not a size K12 takes "
                          "(fewer than 2^32 elements per call)")
     dev = gt.device
-    host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)        # one stream-ordered upload, never written again
-    host.numpy()[...] = tab
-    table = host.to(dev, non_blocking=True)
+    table = _upload(np.concatenate((_window_table(windows, True).reshape(-1), seg.reshape(-1))), dev)   # windows, then segments: one table
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty((n_cand, n_seg, len(ROW)), dtype=torch.float32, device=dev)
-    ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
-    numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+    ptrs, numel = _cand_arrays(cands)
     if masked:
         counts = torch.empty(n_seg, dtype=torch.int64, device=dev)
         _lib.check(lib.jspsr_summary_valid_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), valid.data_ptr(), valid.numel(),
@@ -252,14 +278,21 @@ def scores_pooled(cands, gt, segments=None, value_max: float = 1.0, valid=None):
             at = ((p * H + y0) * W + x0, W)
             windows.append((sg, h, w, at, [at] * len(cands)))
     flat = [t.detach().float().contiguous().reshape(-1) for t in cands]
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != gt.shape:
-            raise ValueError(f"scores_pooled: valid must be a bool or uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
-        if valid.device != gt.device:
-            raise ValueError(f"scores_pooled: valid on {valid.device}, the ground truth on {gt.device}")
-        valid = valid.detach().contiguous().reshape(-1)
-        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid     # a bool is one byte, 0 or 1
-    return pooled_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, len(segments), value_max, valid=valid)
+    return pooled_rows(flat, gt.detach().float().contiguous().reshape(-1), windows, len(segments), value_max,
+                       valid=_flat_valid("scores_pooled", valid, gt))
+
+
+def _flat_valid(what, valid, gt):
+    """A bool or uint8 validity tensor of gt's shape on gt's device -> the flat uint8 plane `pooled_rows` takes (None stays
+    None)."""
+    if valid is None:
+        return None
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != gt.shape:
+        raise ValueError(f"{what}: valid must be a bool or uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
+    if valid.device != gt.device:
+        raise ValueError(f"{what}: valid on {valid.device}, the ground truth on {gt.device}")
+    valid = valid.detach().contiguous().reshape(-1)
+    return valid.view(torch.uint8) if valid.dtype == torch.bool else valid     # a bool is one byte, 0 or 1
 
 
 class ScenePredictions:
@@ -579,21 +612,11 @@ def pooled_histogram(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: S
     if total >= 2 ** 32:
         raise ValueError(f"pooled_histogram: {total} pooled elements, the bin counters hold fewer than 2^32")
     if gt.is_cuda:
-        tab = np.zeros((len(windows), _WIN_WORDS), dtype=np.int64)
-        e_off = 0
-        for i, (_, h, w, (go, gp), cs) in enumerate(windows):
-            tab[i, :6] = (0, h, w, e_off, go, gp)
-            for c, (co, cp) in enumerate(cs):
-                tab[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
-            e_off += h * w
         dev = gt.device
-        host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)     # one stream-ordered upload, never written again
-        host.numpy()[...] = tab
-        table = host.to(dev, non_blocking=True)
+        table = _upload(_window_table(windows, False), dev)
         hist = torch.empty((n_cand, K), dtype=torch.int64, device=dev)
         counts = torch.empty((n_cand, 4), dtype=torch.int64, device=dev)
-        ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
-        numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+        ptrs, numel = _cand_arrays(cands)
         _lib.check(_lib.load().jspsr_errdist_hist_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(),
                                                           valid.data_ptr() if valid is not None else None,
                                                           valid.numel() if valid is not None else 0, table.data_ptr(), len(windows),
@@ -603,22 +626,11 @@ def pooled_histogram(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: S
         return hist, counts, key0
     g_np = gt.numpy()
     lo32, hi32 = np.float32(lo), np.float32(hi)
-    keep = None
-    if valid is not None:
-        v_np = valid.numpy()
-        keep = np.concatenate([v_np[go + np.arange(h)[:, None] * gp + np.arange(w)[None, :]].reshape(-1) != 0
-                               for _, h, w, (go, gp), _ in windows])
+    keep = None if valid is None else np.concatenate(_gather_plane(valid.numpy(), windows)) != 0
     hist = np.zeros((n_cand, K), dtype=np.int64)
     counts = np.zeros((n_cand, 4), dtype=np.int64)
     for c, cand in enumerate(cands):
-        c_np = cand.numpy()
-        parts = []
-        for _, h, w, (go, gp), cs in windows:
-            co, cp = cs[c]
-            rows, cols = np.arange(h)[:, None], np.arange(w)[None, :]
-            with np.errstate(invalid="ignore"):                 # inf - inf under a mask
-                parts.append((c_np[co + rows * cp + cols] - g_np[go + rows * gp + cols]).reshape(-1))
-        e = np.concatenate(parts).astype(np.float32, copy=False)
+        e = np.concatenate(_gather_errors(cand.numpy(), g_np, windows, c)).astype(np.float32, copy=False)
         if keep is not None:
             e = e[keep]
         inside = (e >= lo32) & (e <= hi32)
@@ -752,40 +764,25 @@ def stratified_rows(cands: Sequence[torch.Tensor], gt: torch.Tensor, windows: Se
         nbytes = lib.jspsr_strata_workspace_bytes(n_cand, n_classes, total)
         if nbytes == 0:
             raise ValueError(f"stratified_rows: {n_cand} candidates, {n_classes} classes, {total} pooled elements: not a size K22 takes")
-        tab = np.zeros((len(windows), _WIN_WORDS), dtype=np.int64)
-        e_off = 0
-        for i, (_, h, w, (go, gp), cs) in enumerate(windows):
-            tab[i, :6] = (0, h, w, e_off, go, gp)
-            for c, (co, cp) in enumerate(cs):
-                tab[i, 6 + 2 * c: 8 + 2 * c] = (co, cp)
-            e_off += h * w
         dev = gt.device
-        host = torch.empty(tab.shape, dtype=torch.int64, pin_memory=True)     # one stream-ordered upload, never written again
-        host.numpy()[...] = tab
-        table = host.to(dev, non_blocking=True)
+        table = _upload(_window_table(windows, False), dev)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty((n_cand, n_classes, len(ROW)), dtype=torch.float32, device=dev)
         counts = torch.empty(n_classes, dtype=torch.int64, device=dev)
-        ptrs = (ctypes.c_void_p * n_cand)(*[c.data_ptr() for c in cands])
-        numel = (ctypes.c_longlong * n_cand)(*[c.numel() for c in cands])
+        ptrs, numel = _cand_arrays(cands)
         _lib.check(lib.jspsr_strata_forward(ptrs, numel, n_cand, gt.data_ptr(), gt.numel(), labels.data_ptr(), labels.numel(), n_classes,
                                             valid.data_ptr() if valid is not None else None,
                                             valid.numel() if valid is not None else 0, table.data_ptr(), len(windows), total,
                                             float(value_max), out.data_ptr(), counts.data_ptr(), ws.data_ptr(),
                                             torch.cuda.current_stream(dev).cuda_stream), "jspsr_strata_forward")
         return out, counts
-    g_np, l_np = gt.numpy(), labels.numpy()
-    idx = [go + np.arange(h)[:, None] * gp + np.arange(w)[None, :] for _, h, w, (go, gp), _ in windows]
-    cls = np.concatenate([l_np[i].reshape(-1) for i in idx]).astype(np.int64)
+    g_np = gt.numpy()
+    cls = np.concatenate(_gather_plane(labels.numpy(), windows)).astype(np.int64)
     if valid is not None:
-        v_np = valid.numpy()
-        cls[np.concatenate([v_np[i].reshape(-1) for i in idx]) == 0] = NO_CLASS
+        cls[np.concatenate(_gather_plane(valid.numpy(), windows)) == 0] = NO_CLASS
     out = np.empty((n_cand, n_classes, len(ROW)), dtype=np.float32)
     for c, cand in enumerate(cands):
-        c_np = cand.numpy()
-        with np.errstate(invalid="ignore"):                     # inf - inf at a pixel of no class
-            e = np.concatenate([(c_np[co + np.arange(h)[:, None] * cp + np.arange(w)[None, :]] - g_np[i]).reshape(-1)
-                                for (_, h, w, _, cs), i in zip(windows, idx) for co, cp in [cs[c]]]).astype(np.float32, copy=False)
+        e = np.concatenate(_gather_errors(cand.numpy(), g_np, windows, c)).astype(np.float32, copy=False)
         for k in range(n_classes):
             ek = e[cls == k]
             out[c, k] = _row_host(ek, value_max) if ek.size else _nan_row()
@@ -803,13 +800,7 @@ def scores_by_class(cands, gt, labels, n_classes: int, value_max: float = 1.0, v
         raise ValueError(f"scores_by_class: labels must be a uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
     if labels.device != gt.device:
         raise ValueError(f"scores_by_class: labels on {labels.device}, the ground truth on {gt.device}")
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.shape != gt.shape:
-            raise ValueError(f"scores_by_class: valid must be a bool or uint8 tensor of the ground truth's shape {tuple(gt.shape)}")
-        if valid.device != gt.device:
-            raise ValueError(f"scores_by_class: valid on {valid.device}, the ground truth on {gt.device}")
-        valid = valid.detach().contiguous().reshape(-1)
-        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid     # a bool is one byte, 0 or 1
+    valid = _flat_valid("scores_by_class", valid, gt)
     H, W = gt.shape[-2:]
     planes = gt.numel() // (H * W) if H * W else 0
     windows = [(0, H, W, (p * H * W, W), [(p * H * W, W)] * len(cands)) for p in range(planes)]

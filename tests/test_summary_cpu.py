@@ -142,3 +142,19 @@ def test_bad_tables_are_refused():
         S.scores_pooled([gt] * 9, gt)
     with pytest.raises(ValueError):
         S.scores_pooled(gt, gt, segments=[[(0, 0, 0, 8, 8)], []])   # a segment without windows
+
+
+def test_window_table_rows():
+    """The rows K12, K21 and K22 read, written out: word 3 runs over h * w, the slots of candidates 2..7 stay 0, word 0 is
+    the segment or 0."""
+    windows = [(1, 3, 5, (7, 11), [(2, 5), (40, 9)]),
+               (0, 2, 4, (100, 6), [(0, 4), (8, 13)]),
+               (1, 1, 6, (50, 6), [(17, 6), (3, 7)])]
+    pad = [0] * 12
+    rows = [[1, 3, 5, 0, 7, 11, 2, 5, 40, 9] + pad,
+            [0, 2, 4, 15, 100, 6, 0, 4, 8, 13] + pad,
+            [1, 1, 6, 23, 50, 6, 17, 6, 3, 7] + pad]
+    kept = S._window_table(windows, True)
+    assert kept.dtype == np.int64 and kept.shape == (3, 22)
+    assert kept.tolist() == rows
+    assert S._window_table(windows, False).tolist() == [[0] + r[1:] for r in rows]
