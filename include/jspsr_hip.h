@@ -76,7 +76,10 @@ size_t jspsr_prop_backward_workspace_bytes(int B, int H, int W);
  * workspace: jspsr_prop_backward_workspace_bytes() bytes, 16-byte aligned.
  * Two launches: the streaming kernel (writes grad_weight / grad_offset and one row of 10 partial sums per
  * workgroup into the workspace) and a 10-workgroup fold of those rows into grad_wk / grad_b0.  With
- * grad_wk == grad_b0 == NULL only the first is launched; jspsr_prop_backward_fold_f32 is the second on its own.
+ * grad_wk == grad_b0 == NULL only the first is launched; jspsr_prop_backward_fold_f32 is the second on its own, on the
+ * same workspace (16-byte aligned there too: JSPSR_EALIGN before any launch).  Layout: a 16-byte header whose first
+ * word is the number of rows the streaming kernel wrote, then the rows of 10 floats; the query covers every kernel form
+ * of jspsr_prop_backward_f32 and jspsr_prop_logits_backward_f32 (0 for a non-positive size).
  */
 int jspsr_prop_backward_f32(const float* grad_out, const float* dem, const float* weight,
                             const float* offset, int offset_channels, const float* wk,
@@ -97,7 +100,8 @@ int jspsr_prop_backward_fold_f32(const void* workspace, int B, int H, int W, flo
  * Backward: grad_weight / grad_offset are overwritten, or ADDED to when accumulate != 0 (the affinities and offsets
  * of an N-step chain are shared by all steps: their gradients sum over the steps).  grad_dem (may be NULL): the
  * gradient with respect to dem is ADDED into it (bilinear scatter + scale * grad_out; the caller zero-fills it or
- * lets it carry another contribution); it uses float atomics, so its last bits depend on the execution order.
+ * lets it carry another contribution); a tap beyond tile + halo (possible from |offset| >= 7 px on) is added with a float
+ * atomic, so its last bits depend on the execution order only where such taps exist.
  * grad_wk / grad_b0: both NULL (partial rows stay in the workspace) or both valid (overwritten).
  * workspace: jspsr_prop_step_backward_workspace_bytes() bytes, 16-byte aligned. */
 int jspsr_prop_step_forward_f32(const float* dem, const float* weight, const float* offset, int offset_channels,
@@ -470,7 +474,9 @@ int jspsr_gate_backward_apply(int dtype, const void* dy, const float* s, const f
  * configs/<name>.yml:67-70): losses[4] = {L1, L2, Grad, Total = w1*L1 + w2*L2 + wg*Grad} on fp32
  * (B,1,H,W) tensors; Grad = L1 between normalised Sobel gradients with replicate padding
  * (losses/loss_functions.py:171-185).  The backward writes d(Total)/d(pred) * grad_total[0]
- * (grad_total may be NULL = 1).  workspace: jspsr_loss_workspace_bytes(), shared by both calls.
+ * (grad_total may be NULL = 1).  workspace: jspsr_loss_workspace_bytes() bytes (0 = a non-positive size), 16-byte aligned
+ * (JSPSR_EALIGN, decided before any launch), shared by both calls; the same holds for jspsr_loss_valid_*, whose
+ * workspace carries two 64-bit counts from the forward to the backward.
  */
 size_t jspsr_loss_workspace_bytes(int B, int H, int W);
 int jspsr_loss_forward(const float* pred, const float* gt, float w1, float w2, float wg, float* losses,
@@ -490,7 +496,9 @@ int jspsr_loss_backward(const float* pred, const float* gt, const float* grad_to
  * key_weight[k] * out[k] (host doubles; in double, rounded once).  workspace: jspsr_loss_menu_workspace_bytes(), shared
  * with the backward, which ADDS d(sum_s slot_weight[s] term_s)/d(pred) * grad_total[0] over the slots 3..6 of `terms`
  * (slot_weight: host doubles [7]; grad_total may be NULL = 1) to grad_pred.  JSPSR_EINVAL on bad arguments, SSIM with
- * H < 11 or W < 11 among them; the workspace query returns 0 there. */
+ * H < 11 or W < 11 among them; the workspace query returns 0 there.  The workspace of every entry of this family
+ * (jspsr_loss_menu_*, jspsr_loss_menu_valid_*, jspsr_loss_menu_valid_ssim_*, jspsr_ssim_forward,
+ * jspsr_ssim_tiles_forward) is 16-byte aligned: JSPSR_EALIGN, decided before any launch. */
 size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W);
 int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int planes, int H, int W, int n_keys,
                             const int* key_slot, const double* key_weight, const float* base_losses, float* out,
@@ -591,8 +599,9 @@ int jspsr_metrics_forward(const float* pred, const float* gt, int H, int W, floa
  * tile with both de-scaled rasters in LDS; larger tiles stream through 27 launches whatever B is.  Sums fold in double in
  * an order fixed by (h, w): row b does not depend on B or on the other tiles.  No host synchronisation.
  * JSPSR_EINVAL: B <= 0, border outside [0, 0.5), value_max - value_min <= 1, nothing or fewer than 3 rows / columns
- * left after the crop.  workspace: jspsr_scores_batch_workspace_bytes(B, H, W) bytes (0 = bad arguments), 16-byte
- * aligned (JSPSR_EALIGN). */
+ * left after the crop.  workspace: jspsr_scores_batch_workspace_bytes(B, H, W) bytes, 16-byte aligned (JSPSR_EALIGN).
+ * The query returns 0 for what the entry refuses whatever the border is: B <= 0, H < 3, W < 3, H * W above 2^30 - 1.
+ * A raster of at most 20 272 pixels before the crop gets 16 bytes, of which the one-launch path touches none. */
 size_t jspsr_scores_batch_workspace_bytes(int B, int H, int W);
 int jspsr_scores_batch_forward(const float* pred, const float* gt, int B, int H, int W, float border, float value_min,
                                float value_max, int elev_log, float* scores, void* workspace, jspsr_stream_t stream);
@@ -947,7 +956,8 @@ int jspsr_scores_batch_valid_forward(const float* pred, const float* gt, const u
  *   support, density  device fp64 [n_cand][gridsize];  stats  device fp64 [n_cand][3] = { mean, std, bw }.
  *   Two launches (census label errdist_kde), no host synchronisation.  JSPSR_EINVAL: a null pointer, n_cand outside 1..8, bins
  *   that are not finite float16 values, gridsize outside 2..65535, cut < 0, bw_adjust <= 0.  workspace:
- *   jspsr_errdist_workspace_bytes(n_cand, gridsize) bytes (0 = bad arguments), 16-byte aligned (JSPSR_EALIGN). */
+ *   jspsr_errdist_workspace_bytes(n_cand, gridsize) bytes (0 = n_cand or gridsize outside the bounds above), 16-byte aligned
+ *   (JSPSR_EALIGN). */
 int jspsr_errdist_bins(double lo, double hi, int* key0, int* K);
 int jspsr_errdist_key(float e, double lo, double hi);
 size_t jspsr_errdist_workspace_bytes(int n_cand, int gridsize);
@@ -1064,7 +1074,9 @@ int jspsr_tensor_ranges(int count, const void* const* tensors, const long long* 
  * average- and the max-pooled vector, ReLU between, Sigmoid of the sum): s[b,c] = sigmoid(W2 relu(W1 avg[b]) + W2 relu(W1
  * mx[b])).  w1 (Ch, C), w2 (C, Ch) fp32 row-major; hid (B, 2, Ch) receives the two hidden vectors for the backward pass.
  * Backward: from ds (B, C) the gradients of avg, mx (B, C) and of the two weights (summed over the batch in image order);
- * workspace of jspsr_gate_mlp_backward_workspace_bytes.  Needs (C + 2 Ch) * 4 bytes <= 64 KiB. */
+ * workspace of jspsr_gate_mlp_backward_workspace_bytes: dz (B, C) then dh (B, 2, Ch), fp32, 4-byte aligned (every access
+ * is one float).  Needs (C + 2 Ch) * 4 bytes <= 64 KiB: above it the entry is JSPSR_EINVAL and the query returns 0, as it
+ * does for a non-positive size. */
 int jspsr_gate_mlp_forward(const float* avg, const float* mx, const float* w1, const float* w2, int B, int C, int Ch,
                            float* s, float* hid, jspsr_stream_t stream);
 size_t jspsr_gate_mlp_backward_workspace_bytes(int B, int C, int Ch);

@@ -1520,7 +1520,7 @@ extern "C" int jspsr_gate_mlp_forward(const float* avg, const float* mx, const f
 }
 
 extern "C" size_t jspsr_gate_mlp_backward_workspace_bytes(int B, int C, int Ch) {
-  if (B <= 0 || C <= 0 || Ch <= 0) return 0;
+  if (B <= 0 || C <= 0 || Ch <= 0 || ((size_t)C + 2 * (size_t)Ch) * sizeof(float) > 64 * 1024) return 0;   // the entry's own limit
   return ((size_t)B * C + (size_t)B * 2 * Ch) * sizeof(float);
 }
 

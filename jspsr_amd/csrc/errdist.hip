@@ -312,7 +312,7 @@ extern "C" int jspsr_errdist_key(float e, double lo, double hi) {
 }
 
 extern "C" size_t jspsr_errdist_workspace_bytes(int n_cand, int gridsize) {
-  if (n_cand < 1 || n_cand > MAXC || gridsize < 2) return 0;
+  if (n_cand < 1 || n_cand > MAXC || gridsize < 2 || gridsize > 65535) return 0;     // the entry's own bounds
   return (size_t)n_cand * WS_WORDS * sizeof(double);
 }
 

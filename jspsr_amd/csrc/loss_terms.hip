@@ -662,6 +662,7 @@ extern "C" int jspsr_loss_menu_forward(const float* pred, const float* gt, int t
   if (!pred || !gt || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
       !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
     return fail(JSPSR_EINVAL, "loss_menu_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_forward: workspace not 16-byte aligned");
   if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_forward: SSIM needs H, W >= 11");
   KeyMap km{};
   km.n = n_keys;
@@ -704,6 +705,7 @@ extern "C" int jspsr_loss_menu_backward(const float* pred, const float* gt, int 
                                         const void* workspace, jspsr_stream_t stream) {
   if (!pred || !gt || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W))
     return fail(JSPSR_EINVAL, "loss_menu_backward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_backward: workspace not 16-byte aligned");
   if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_backward: SSIM needs H, W >= 11");
   const Layout L = layout(terms, planes, H, W);
   const char* ws = static_cast<const char*>(workspace);
@@ -738,6 +740,7 @@ extern "C" int jspsr_loss_menu_valid_forward(const float* pred, const float* gt,
   if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
       !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
     return fail(JSPSR_EINVAL, "loss_menu_valid_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_forward: workspace not 16-byte aligned");
   if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_forward: SSIM over a validity plane is not built");
   KeyMap km{};
   km.n = n_keys;
@@ -773,6 +776,7 @@ extern "C" int jspsr_loss_menu_valid_backward(const float* pred, const float* gt
   if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
       !dims_ok(planes, H, W))
     return fail(JSPSR_EINVAL, "loss_menu_valid_backward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_backward: workspace not 16-byte aligned");
   if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_backward: SSIM over a validity plane is not built");
   const ValidLayout L = valid_layout(planes, H, W);
   const char* ws = static_cast<const char*>(workspace);
@@ -792,6 +796,7 @@ extern "C" size_t jspsr_ssim_workspace_bytes(int planes, int H, int W, int same)
 extern "C" int jspsr_ssim_forward(const float* pred, const float* gt, int planes, int H, int W, int same,
                                   const float* window11, float* out, void* workspace, jspsr_stream_t stream) {
   if (!pred || !gt || !out || !workspace || !dims_ok(planes, H, W)) return fail(JSPSR_EINVAL, "ssim_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "ssim_forward: workspace not 16-byte aligned");
   if (!same && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "ssim_forward: valid mode needs H, W >= 11");
   Win11 k = gaussian_window();
   if (window11)
@@ -859,6 +864,7 @@ extern "C" int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float
   if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
       !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
     return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_ssim_forward: workspace not 16-byte aligned");
   if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
   if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: SSIM needs H, W >= 11");
   KeyMap km{};
@@ -909,6 +915,7 @@ extern "C" int jspsr_loss_menu_valid_ssim_backward(const float* pred, const floa
   if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
       !dims_ok(planes, H, W))
     return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_ssim_backward: workspace not 16-byte aligned");
   if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
   if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: SSIM needs H, W >= 11");
   const VsLayout L = vs_layout(terms, planes, H, W);
@@ -947,6 +954,7 @@ extern "C" int jspsr_ssim_tiles_forward(const float* pred, const float* gt, cons
                                         void* workspace, jspsr_stream_t stream) {
   if (!pred || !gt || !out || !counts || !workspace || !dims_ok(B, H, W))
     return fail(JSPSR_EINVAL, "ssim_tiles_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "ssim_tiles_forward: workspace not 16-byte aligned");
   if (!(border >= 0.0) || border >= 0.5) return fail(JSPSR_EINVAL, "ssim_tiles_forward: border must be in [0, 0.5)");
   const int bh = (int)((double)H * border), bw = (int)((double)W * border);       // int(h * border), metrics.prepare
   const int h = H - 2 * bh, w = W - 2 * bw;

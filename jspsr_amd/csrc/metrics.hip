@@ -150,6 +150,8 @@ int metric_blocks(long long n) {
 extern "C" size_t jspsr_metrics_workspace_bytes(int H, int W) {
   if (H <= 0 || W <= 0) return 0;
   const long long n = (long long)H * W;
+  // jspsr_metrics_forward rounds the dh and the partial region up to 16 bytes (at most 12 + 8 more) and uses three states:
+  // the fourth SelState (24 bytes) and the 64 cover that rounding
   return (size_t)n * sizeof(float) + (size_t)metric_blocks(n) * 2 * sizeof(float) + 256 * sizeof(unsigned) + 4 * sizeof(SelState) + 64;
 }
 

@@ -446,6 +446,7 @@ extern "C" int jspsr_prop_backward_f32(const float* grad_out, const float* dem, 
 extern "C" int jspsr_prop_backward_fold_f32(const void* workspace, int B, int H, int W, float* grad_wk, float* grad_b0,
                                             jspsr_stream_t stream) {
   if (!workspace || !grad_wk || !grad_b0) return jspsr::fail(JSPSR_EINVAL, "prop_backward_fold: null pointer");
+  if (!jspsr::aligned16(workspace)) return jspsr::fail(JSPSR_EALIGN, "prop_backward_fold: workspace not 16-byte aligned");
   Geom g;
   if (int e = make_geom(B, H, W, g)) return e;
   hipLaunchKernelGGL(prop_bwd_finalize, dim3(NRED), dim3(256), 0, static_cast<hipStream_t>(stream),

@@ -486,9 +486,11 @@ int stream_blocks(long long n) {
 }
 
 size_t workspace_bytes(bool masked, int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  if (B <= 0 || H < 3 || W < 3) return 0;                // what scores_run refuses whatever the border is: 0, as documented
   const long long n = (long long)H * W;
+  if (n > 0x7fffffffLL / 2) return 0;
   if (n <= LDS_MAX_N) return 16;                         // LDS path for every border: nothing is staged in memory
+  // every region below is a multiple of 16 bytes but the two planes; the + 64 is spare (it covers no rounding)
   return 2 * up16((size_t)B * n * sizeof(float)) + up16((size_t)B * stream_blocks(n) * NSUM * sizeof(double)) +
          (size_t)B * 256 * sizeof(unsigned) + up16((size_t)B * 3 * sizeof(SelState)) + 64 +
          (masked ? up16((size_t)B * stream_blocks(n) * NCNT * sizeof(unsigned)) : 0);

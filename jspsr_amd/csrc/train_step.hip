@@ -214,6 +214,7 @@ extern "C" size_t jspsr_loss_workspace_bytes(int B, int H, int W) {
 extern "C" int jspsr_loss_forward(const float* pred, const float* gt, float w1, float w2, float wg, float* losses,
                                   void* workspace, int B, int H, int W, jspsr_stream_t stream) {
   if (!pred || !gt || !losses || !workspace || B <= 0 || H <= 0 || W <= 0) return fail(JSPSR_EINVAL, "loss_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_forward: workspace not 16-byte aligned");
   const long long n = (long long)B * H * W;
   const int blocks = loss_blocks(n);
   float* partial = static_cast<float*>(workspace);
@@ -229,6 +230,7 @@ extern "C" int jspsr_loss_backward(const float* pred, const float* gt, const flo
                                    float wg, float* grad_pred, const void* workspace, int B, int H, int W,
                                    jspsr_stream_t stream) {
   if (!pred || !gt || !grad_pred || !workspace || B <= 0 || H <= 0 || W <= 0) return fail(JSPSR_EINVAL, "loss_backward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_backward: workspace not 16-byte aligned");
   const long long n = (long long)B * H * W;
   const int blocks = loss_blocks(n);
   const signed char* sg = static_cast<const signed char*>(workspace) + (((size_t)blocks * 3 * sizeof(float) + 15) & ~(size_t)15);
@@ -423,6 +425,7 @@ extern "C" int jspsr_loss_valid_forward(const float* pred, const float* gt, cons
                                         float wg, float* losses, void* workspace, int B, int H, int W, jspsr_stream_t stream) {
   if (!pred || !gt || !valid || !losses || !workspace || B <= 0 || H <= 0 || W <= 0)
     return fail(JSPSR_EINVAL, "loss_valid_forward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_valid_forward: workspace not 16-byte aligned");
   const long long n = (long long)B * H * W;
   const int blocks = loss_blocks(n);
   const ValidLayout L = valid_layout(n);
@@ -443,6 +446,7 @@ extern "C" int jspsr_loss_valid_backward(const float* pred, const float* gt, con
                                          const void* workspace, int B, int H, int W, jspsr_stream_t stream) {
   if (!pred || !gt || !valid || !grad_pred || !workspace || B <= 0 || H <= 0 || W <= 0)
     return fail(JSPSR_EINVAL, "loss_valid_backward: bad arguments");
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_valid_backward: workspace not 16-byte aligned");
   const long long n = (long long)B * H * W;
   const int blocks = loss_blocks(n);
   const ValidLayout L = valid_layout(n);
