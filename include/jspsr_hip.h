@@ -515,8 +515,10 @@ int jspsr_loss_menu_backward(const float* pred, const float* gt, int terms, int 
  * elements, divided by N.  N = 0 (N_g = 0) gives value 0 and gradient 0.  N and N_g are counted exactly, as integers, by
  * the forward and stay in the workspace, where the backward reads them: no host synchronisation, capturable in a graph.
  * The gradient is +0.0 at every invalid element: jspsr_loss_valid_backward writes it, jspsr_loss_menu_valid_backward leaves
- * the caller's value (which it ADDS to elsewhere) untouched there.  An all-ones plane gives the bits of the unmasked calls.
- * SSIM (term bit 8, slot 6) over a plane is not built: JSPSR_EINVAL, workspace query 0. */
+ * the caller's value (which it ADDS to elsewhere) untouched there.  An all-ones plane gives the bits of the unmasked calls:
+ * every pass is one kernel body, instantiated with and without the plane.
+ * jspsr_loss_menu_valid_* refuse SSIM (term bit 8, slot 6): JSPSR_EINVAL, workspace query 0.  They are
+ * jspsr_loss_menu_valid_ssim_* (below) with that bit refused: the same host path, launches and workspace. */
 size_t jspsr_loss_valid_workspace_bytes(int B, int H, int W);
 int jspsr_loss_valid_forward(const float* pred, const float* gt, const unsigned char* valid, float w1, float w2, float wg,
                              float* losses, void* workspace, int B, int H, int W, jspsr_stream_t stream);
@@ -538,8 +540,9 @@ int jspsr_loss_menu_valid_backward(const float* pred, const float* gt, const uns
  * is counted as an integer by the forward (one launch, census label ssim_valid_forward), folded by the combine kernel and
  * kept in the workspace, where the backward (one launch, ssim_valid_backward) forms (float)(w / (double)N_s): no host
  * synchronisation.  An all-ones plane gives the bits of jspsr_loss_menu_forward / _backward.  Every other argument and
- * every other term as in jspsr_loss_menu_valid_*, whose launches and bits these are without the SSIM bit.  SSIM needs
- * H, W >= 11 (JSPSR_EINVAL, workspace query 0).  The jspsr_loss_menu_valid_* entries themselves keep refusing the bit. */
+ * every other term as in jspsr_loss_menu_valid_*.  The three menu families are one host path and one kernel family
+ * (csrc/loss_terms.hip): without a plane, with a plane and SSIM refused, with a plane and SSIM under ssim_rule; without
+ * the SSIM bit ssim_rule is only range-checked.  SSIM needs H, W >= 11 (JSPSR_EINVAL, workspace query 0). */
 size_t jspsr_loss_menu_valid_ssim_workspace_bytes(int terms, int planes, int H, int W, int ssim_rule);
 int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
                                        int H, int W, int ssim_rule, int n_keys, const int* key_slot,

@@ -11,8 +11,10 @@
 // Every reduction writes per-workgroup partials folded in a fixed order in double: the same bits on every run.
 // Gradients accumulate (+=) into a buffer the caller has already written.
 #include "common.h"
+#include "loss_fold.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -61,27 +63,38 @@ Win11 gaussian_window() {
   return k;
 }
 
-struct Layout {             // one workspace for the whole menu forward + backward
+// One workspace for the whole menu forward + backward, th[4] = {thf, th^2 as float, 2 th as float, -} at 0.  Unmasked: the
+// pointwise partials only with a pointwise term.  Masked (K19, K23): always, then the per-workgroup counts and N (a long
+// long in 16 bytes); SSIM's partials are followed by its counts and N_s in the same way.
+struct Layout {
   int nb = 0, nbm = 0, nbs = 0, tiles_x = 0, tiles_y = 0, Hm = 0, Wm = 0;
-  size_t th = 0, pmax = 0, psum = 0, ssum = 0, coef = 0, bytes = 0;
+  size_t pmax = 0, psum = 0, pcnt = 0, nn = 0, ssum = 0, scnt = 0, ns = 0, coef = 0, bytes = 0;
   long long cplane = 0;     // elements of one coefficient map set: planes * Hm * Wm
 };
 
-Layout layout(int terms, int planes, int H, int W) {
+Layout layout(int terms, int planes, int H, int W, bool masked) {
   Layout L;
   const long long n = (long long)planes * H * W;
   L.nb = pw_blocks(n);
   L.nbm = max_blocks(n);
-  size_t off = 16;          // th[4] = {thf, th^2 as float, 2 th as float, -}
-  if (terms & (T_BERHU | T_BCE | T_NORM)) {
+  size_t off = 16;
+  if (masked || (terms & (T_BERHU | T_BCE | T_NORM))) {
     L.pmax = off; off += al16((size_t)L.nbm * 4);
     L.psum = off; off += al16((size_t)L.nb * 3 * 4);
+  }
+  if (masked) {
+    L.pcnt = off; off += al16((size_t)L.nb * 4);
+    L.nn = off; off += 16;
   }
   if (terms & T_SSIM) {
     L.Hm = H - 10; L.Wm = W - 10;
     L.tiles_x = (L.Wm + ST - 1) / ST; L.tiles_y = (L.Hm + ST - 1) / ST;
     L.nbs = L.tiles_x * L.tiles_y * planes;
     L.ssum = off; off += al16((size_t)L.nbs * 4);
+    if (masked) {
+      L.scnt = off; off += al16((size_t)L.nbs * 4);
+      L.ns = off; off += 16;
+    }
     L.cplane = (long long)planes * L.Hm * L.Wm;
     L.coef = off; off += al16((size_t)L.cplane * 3 * 4);
   }
@@ -118,62 +131,88 @@ __device__ __forceinline__ float bce_elem(float x, float y) { return fmaxf(x, 0.
 
 __device__ __forceinline__ float unit(float v) { return v / fmaxf(fabsf(v), 1e-12f); }   // F.normalize, C = 1
 
+// MASKED (K19): the terms over the elements a validity plane keeps.  valid: one byte per element, nonzero = valid.  pred / gt
+// are used behind a select on the plane (never multiplied by it: NaN * 0 is NaN), in the same grids, loop order and fold
+// order, one body per pass: an all-ones plane gives the unmasked bits.  N, the number of valid elements, is counted as an
+// integer by the sum pass, folded by the combine kernel and left in the workspace for the backward.  N = 0: every term and
+// every gradient element is 0.
+template <bool MASKED>
 __global__ __launch_bounds__(PT) void menu_max_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                     long long n, float* __restrict__ pmax) {
+                                                     const unsigned char* __restrict__ valid, long long n,
+                                                     float* __restrict__ pmax) {
   __shared__ float red[PT / 64];
   float m = 0.f;
-  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT)
-    m = fmaxf(m, fabsf(pred[i] - gt[i]));
+  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    const float ad = fabsf(pred[i] - gt[i]);          // MASKED: loaded beside the plane's byte, not after it
+    m = fmaxf(m, !MASKED || valid[i] ? ad : 0.f);
+  }
   m = block_reduce<true>(m, red);
   if (threadIdx.x == 0) pmax[blockIdx.x] = m;
 }
 
-// partial sums {BerHu, BCE, 1 - p^.g^} per workgroup; block 0 stores BerHu's threshold for the backward
+// partial sums {BerHu, BCE, 1 - p^.g^} per workgroup (MASKED: and the count of valid elements); block 0 stores BerHu's
+// threshold for the backward
+template <bool MASKED>
 __global__ __launch_bounds__(PT) void menu_sum_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                     long long n, int terms, const float* __restrict__ pmax, int nb,
-                                                     float* __restrict__ th, float* __restrict__ psum) {
-  __shared__ float red[3][PT / 64];
+                                                     const unsigned char* __restrict__ valid, long long n, int terms,
+                                                     const float* __restrict__ pmax, int nb, float* __restrict__ th,
+                                                     float* __restrict__ psum, unsigned int* __restrict__ pcnt) {
+  __shared__ float red[3 * (PT / 64)];
+  __shared__ unsigned int redc[PT / 64];
   float thf = 0.f, t2f = 0.f, tw = 0.f;
   if (terms & T_BERHU) {
     float m = 0.f;
     for (int r = threadIdx.x; r < nb; r += PT) m = fmaxf(m, pmax[r]);
-    m = block_reduce<true>(m, red[0]);
+    m = block_reduce<true>(m, red);
     __syncthreads();
     const double t = 0.6 * (double)m;       // delta * torch.max(diff).item()
     thf = (float)t; t2f = (float)(t * t); tw = (float)(2.0 * t);
     if (blockIdx.x == 0 && threadIdx.x == 0) { th[0] = thf; th[1] = t2f; th[2] = tw; th[3] = 0.f; }
   }
-  float sb = 0.f, sc = 0.f, sn = 0.f;
+  float s[3] = {0.f, 0.f, 0.f};
+  unsigned int nv[1] = {0};
   for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
-    const float x = pred[i], y = gt[i];
-    if (terms & T_BERHU) sb += berhu_elem(fabsf(x - y), thf, t2f, tw);
-    if (terms & T_BCE) sc += bce_elem(x, y);
-    if (terms & T_NORM) sn += 1.f - unit(x) * unit(y);
+    const float x = pred[i], y = gt[i];               // MASKED: loaded beside the plane's byte, not after it
+    if constexpr (MASKED) {
+      if (!valid[i]) continue;
+      ++nv[0];
+    }
+    if (terms & T_BERHU) s[0] += berhu_elem(fabsf(x - y), thf, t2f, tw);
+    if (terms & T_BCE) s[1] += bce_elem(x, y);
+    if (terms & T_NORM) s[2] += 1.f - unit(x) * unit(y);
   }
-  float v[3] = {sb, sc, sn};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float t = 0.f;
-    for (int w = 0; w < PT / 64; ++w) t += red[threadIdx.x][w];
-    psum[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-  }
+  block_fold3<PT, MASKED ? 1 : 0>(s, nv, red, redc, psum, pcnt);
 }
 
-// grad += up * (wb/n BerHu' + wc/n BCE' + wn/n Norm').  BerHu's threshold is a constant (the reference detaches it by
-// .item()); at th = 0 every element takes the |d| branch, whose gradient there is 0 (the reference: NaN, see header).
+// grad += up * (cb BerHu' + cc BCE' + cn Norm').  Unmasked: kb, kc, kn are the coefficients wb/n, wc/n, wn/(1e-12 n), formed
+// by the host.  MASKED: they are the weights, and the coefficients (float)(w / (double)N) are formed here from the stored
+// count (nothing valid: return, the caller's zeros stand); the gradient of an invalid element stays the +0.0 the caller wrote.
+// BerHu's threshold is a constant (the reference detaches it by .item()); at th = 0 every element takes the |d| branch,
+// whose gradient there is 0 (the reference: NaN, see header).
+template <bool MASKED>
 __global__ __launch_bounds__(PT) void menu_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                     long long n, int terms, const float* __restrict__ th,
-                                                     const float* __restrict__ gscale, float cb, float cc, float cn,
+                                                     const unsigned char* __restrict__ valid, long long n, int terms,
+                                                     const float* __restrict__ th, const long long* __restrict__ nn,
+                                                     const float* __restrict__ gscale,
+                                                     std::conditional_t<MASKED, double, float> kb,
+                                                     std::conditional_t<MASKED, double, float> kc,
+                                                     std::conditional_t<MASKED, double, float> kn,
                                                      float* __restrict__ grad) {
+  float cb, cc, cn;
+  if constexpr (MASKED) {
+    const long long nv = nn[0];
+    if (nv <= 0) return;
+    const double dn = (double)nv;
+    cb = (float)(kb / dn); cc = (float)(kc / dn); cn = (float)(kn / (1e-12 * dn));
+  } else {
+    cb = kb; cc = kc; cn = kn;
+  }
   const float up = gscale ? gscale[0] : 1.f;
   const float thf = (terms & T_BERHU) ? th[0] : 0.f, tw = (terms & T_BERHU) ? th[2] : 1.f;
   for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
+    if constexpr (MASKED) {
+      if (!valid[i]) continue;
+    }
     const float x = pred[i], y = gt[i];
     float g = 0.f;
     if (terms & T_BERHU) {
@@ -417,34 +456,40 @@ __global__ __launch_bounds__(SN) void ssim_bwd_kernel(const float* __restrict__ 
   }
 }
 
-// Fixed-order double fold of `rows` partials of column q (stride `cols`) by one wave; the sum lands in every lane.
-__device__ double wave_fold(const float* __restrict__ p, int rows, int cols, int q) {
-  const int lane = threadIdx.x & 63;
-  double s = 0.0;
-  if (p)
-    for (int r = lane; r < rows; r += 64) s += (double)p[(size_t)r * cols + q];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-  return s;
-}
-
 // out[k] = term of key k (config order), out[n] = Total = sum_k w_k out[k] (in double over the fp32 values, rounded
-// once).  Slots 0..2 come from jspsr_loss_forward's losses[0..2] when the caller passes them.
-__global__ void menu_combine_kernel(const float* __restrict__ psum, int nb, const float* __restrict__ ssum, int nbs,
+// once).  Slots 0..2 come from jspsr_loss_forward's losses[0..2] when the caller passes them.  Every fold is a
+// latency-bound walk by one wave, so they run side by side: psum's columns 0..2 by waves 0..2, then ssum (NULL: none
+// configured).  Unmasked: 4 waves, the divisors are the host's n and m.  MASKED: 6 waves, wave 3 folds pcnt and wave 5
+// scnt between and after them, the divisors are those counts (0: the term is 0), and nn[0] = N, ns[0] = N_s (ns NULL
+// without SSIM) are left for the backward.
+template <bool MASKED>
+__global__ void menu_combine_kernel(const float* __restrict__ psum, const unsigned int* __restrict__ pcnt, int nb,
+                                    const float* __restrict__ ssum, const unsigned int* __restrict__ scnt, int nbs,
                                     long long n, long long m, const float* __restrict__ base, KeyMap km,
-                                    float* __restrict__ out) {
+                                    float* __restrict__ out, long long* __restrict__ nn, long long* __restrict__ ns) {
   __shared__ double acc[4];
-  const int q = threadIdx.x >> 6;
-  const double s = q < 3 ? wave_fold(psum, nb, 3, q) : wave_fold(ssum, nbs, 1, 0);
-  if ((threadIdx.x & 63) == 0) acc[q] = s;
+  __shared__ long long cnt[2];
+  const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (q < 3) {
+    const double s = wave_fold(psum, nb, 3, q);
+    if (lane == 0) acc[q] = s;
+  } else if (q == (MASKED ? 4 : 3)) {
+    const double s = wave_fold(ssum, nbs, 1, 0);
+    if (lane == 0) acc[3] = s;
+  } else if constexpr (MASKED) {
+    const long long c = q == 3 ? wave_count(pcnt, nb, 1, 0) : wave_count(scnt, nbs, 1, 0);
+    if (lane == 0) cnt[q == 3 ? 0 : 1] = c;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
+    if constexpr (MASKED) { n = cnt[0]; m = cnt[1]; }
+    const bool any = !MASKED || n > 0;
     float f[NSLOT];
     for (int i = 0; i < 3; ++i) f[i] = base ? base[i] : 0.f;
-    f[S_BERHU] = (float)(acc[0] / (double)n);
-    f[S_BCE] = (float)(acc[1] / (double)n);
-    f[S_NORM] = (float)(acc[2] / (double)n);
+    f[S_BERHU] = any ? (float)(acc[0] / (double)n) : 0.f;
+    f[S_BCE] = any ? (float)(acc[1] / (double)n) : 0.f;
+    f[S_NORM] = any ? (float)(acc[2] / (double)n) : 0.f;
     f[S_SSIM] = m > 0 ? (float)(1.0 - acc[3] / (double)m) : 0.f;
     double tot = 0.0;
     for (int i = 0; i < km.n; ++i) {
@@ -453,6 +498,10 @@ __global__ void menu_combine_kernel(const float* __restrict__ psum, int nb, cons
       tot += km.w[i] * (double)v;
     }
     out[km.n] = (float)tot;
+    if constexpr (MASKED) {
+      nn[0] = n;
+      if (ns) ns[0] = m;
+    }
   }
 }
 
@@ -466,325 +515,205 @@ bool dims_ok(int planes, int H, int W) {
   return planes > 0 && H > 0 && W > 0 && planes <= 65535 && (long long)planes * H * W < (1ll << 40);
 }
 
-// ---- K19: the pointwise terms over the elements a validity plane keeps ---------------------------------------------------
-// valid: one byte per element, nonzero = valid.  The kernels above with pred / gt read behind a select on the plane (never
-// multiplied by it: NaN * 0 is NaN), the same grids, loop order and fold order, so an all-ones plane gives their bits.
-// N, the number of valid elements, is counted as an integer by the sum pass, folded by the combine kernel and left in the
-// workspace for the backward, which forms the host's coefficients (float)(w / (double)N) on the device.  N = 0: every term
-// and every gradient element is 0.
-struct ValidLayout {
-  int nb = 0, nbm = 0;
-  size_t pmax = 0, psum = 0, pcnt = 0, nn = 0, bytes = 0;
-};
-
-ValidLayout valid_layout(int planes, int H, int W) {
-  ValidLayout L;
-  const long long n = (long long)planes * H * W;
-  L.nb = pw_blocks(n);
-  L.nbm = max_blocks(n);
-  size_t off = 16;          // th[4], as in Layout
-  L.pmax = off; off += al16((size_t)L.nbm * 4);
-  L.psum = off; off += al16((size_t)L.nb * 3 * 4);
-  L.pcnt = off; off += al16((size_t)L.nb * 4);
-  L.nn = off; off += 16;    // long long N
-  L.bytes = off;
-  return L;
-}
-
-__global__ __launch_bounds__(PT) void menu_max_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                           const unsigned char* __restrict__ valid, long long n,
-                                                           float* __restrict__ pmax) {
-  __shared__ float red[PT / 64];
-  float m = 0.f;
-  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
-    const float ad = fabsf(pred[i] - gt[i]);          // loaded beside the plane's byte, not after it; used behind the select
-    m = fmaxf(m, valid[i] ? ad : 0.f);
-  }
-  m = block_reduce<true>(m, red);
-  if (threadIdx.x == 0) pmax[blockIdx.x] = m;
-}
-
-__global__ __launch_bounds__(PT) void menu_sum_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                           const unsigned char* __restrict__ valid, long long n, int terms,
-                                                           const float* __restrict__ pmax, int nb, float* __restrict__ th,
-                                                           float* __restrict__ psum, unsigned int* __restrict__ pcnt) {
-  __shared__ float red[3][PT / 64];
-  __shared__ unsigned int redc[PT / 64];
-  float thf = 0.f, t2f = 0.f, tw = 0.f;
-  if (terms & T_BERHU) {
-    float m = 0.f;
-    for (int r = threadIdx.x; r < nb; r += PT) m = fmaxf(m, pmax[r]);
-    m = block_reduce<true>(m, red[0]);
-    __syncthreads();
-    const double t = 0.6 * (double)m;
-    thf = (float)t; t2f = (float)(t * t); tw = (float)(2.0 * t);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { th[0] = thf; th[1] = t2f; th[2] = tw; th[3] = 0.f; }
-  }
-  float sb = 0.f, sc = 0.f, sn = 0.f;
-  unsigned int nv = 0;
-  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
-    const float x = pred[i], y = gt[i];               // loaded beside the plane's byte, not after it
-    if (!valid[i]) continue;
-    ++nv;
-    if (terms & T_BERHU) sb += berhu_elem(fabsf(x - y), thf, t2f, tw);
-    if (terms & T_BCE) sc += bce_elem(x, y);
-    if (terms & T_NORM) sn += 1.f - unit(x) * unit(y);
-  }
-  float v[3] = {sb, sc, sn};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v[q] += __shfl_xor(v[q], d, 64);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v[q];
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) nv += __shfl_xor(nv, d, 64);
-  if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = nv;
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float t = 0.f;
-    for (int w = 0; w < PT / 64; ++w) t += red[threadIdx.x][w];
-    psum[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-  } else if (threadIdx.x == 3) {
-    unsigned int t = 0;
-    for (int w = 0; w < PT / 64; ++w) t += redc[w];
-    pcnt[blockIdx.x] = t;
-  }
-}
-
-__global__ __launch_bounds__(PT) void menu_bwd_valid_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                           const unsigned char* __restrict__ valid, long long n, int terms,
-                                                           const float* __restrict__ th, const long long* __restrict__ nn,
-                                                           const float* __restrict__ gscale, double wb, double wc, double wn,
-                                                           float* __restrict__ grad) {
-  const long long nv = nn[0];
-  if (nv <= 0) return;                            // nothing valid: the caller's zeros stand
-  const double dn = (double)nv;
-  const float cb = (float)(wb / dn), cc = (float)(wc / dn), cn = (float)(wn / (1e-12 * dn));
-  const float up = gscale ? gscale[0] : 1.f;
-  const float thf = (terms & T_BERHU) ? th[0] : 0.f, tw = (terms & T_BERHU) ? th[2] : 1.f;
-  for (long long i = blockIdx.x * (long long)PT + threadIdx.x; i < n; i += (long long)gridDim.x * PT) {
-    if (!valid[i]) continue;                      // the gradient there stays the +0.0 the caller wrote
-    const float x = pred[i], y = gt[i];
-    float g = 0.f;
-    if (terms & T_BERHU) {
-      const float d = x - y, ad = fabsf(d);
-      g += cb * (ad <= thf ? sgnf(d) : 2.f * ad / tw * sgnf(d));
-    }
-    if (terms & T_BCE) g += cc * (1.f / (1.f + expf(-x)) - y);
-    if (terms & T_NORM) g += fabsf(x) <= 1e-12f ? -cn * unit(y) : 0.f;
-    grad[i] += up * g;
-  }
-}
-
-// Fixed-order integer fold of `rows` per-workgroup counts by one wave; the sum lands in every lane.
-__device__ long long wave_count(const unsigned int* __restrict__ p, int rows) {
-  const int lane = threadIdx.x & 63;
-  long long s = 0;
-  if (p)
-    for (int r = lane; r < rows; r += 64) s += (long long)p[r];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-  return s;
-}
-
-// menu_combine_kernel with a wave for the integer counts: nn[0] = N of the pointwise terms (psum / pcnt NULL: none
-// configured) and, with SSIM under the window rule (ssum / scnt, else NULL), a fifth wave folding SSIM's partials in
-// menu_combine_kernel's order and a sixth their counts, ns[0] = N_s, the counted map elements.  COMBINE_VALID_THREADS
-// threads: every fold is a latency-bound walk by one wave, so they run side by side, not one after another
-constexpr int COMBINE_VALID_THREADS = 6 * 64;
-__global__ void menu_combine_valid_kernel(const float* __restrict__ psum, const unsigned int* __restrict__ pcnt, int nb,
-                                          const float* __restrict__ base, KeyMap km, float* __restrict__ out,
-                                          long long* __restrict__ nn, const float* __restrict__ ssum,
-                                          const unsigned int* __restrict__ scnt, int nbs, long long* __restrict__ ns) {
-  __shared__ double acc[4];
-  __shared__ long long cnt, cnt_s;
-  const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (q < 3) {
-    const double s = wave_fold(psum, nb, 3, q);
-    if (lane == 0) acc[q] = s;
-  } else if (q == 3) {
-    const long long s = wave_count(pcnt, nb);
-    if (lane == 0) cnt = s;
-  } else if (q == 4) {
-    const double a = wave_fold(ssum, nbs, 1, 0);
-    if (lane == 0) acc[3] = a;
-  } else {
-    const long long m = wave_count(scnt, nbs);
-    if (lane == 0) cnt_s = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma clang fp contract(off)
-    const long long n = cnt, m = cnt_s;
-    float f[NSLOT];
-    for (int i = 0; i < 3; ++i) f[i] = base ? base[i] : 0.f;
-    f[S_BERHU] = n > 0 ? (float)(acc[0] / (double)n) : 0.f;
-    f[S_BCE] = n > 0 ? (float)(acc[1] / (double)n) : 0.f;
-    f[S_NORM] = n > 0 ? (float)(acc[2] / (double)n) : 0.f;
-    f[S_SSIM] = m > 0 ? (float)(1.0 - acc[3] / (double)m) : 0.f;
-    if (ns) ns[0] = m;
-    double tot = 0.0;
-    for (int i = 0; i < km.n; ++i) {
-      const float v = f[km.slot[i]];
-      out[i] = v;
-      tot += km.w[i] * (double)v;
-    }
-    out[km.n] = (float)tot;
-    nn[0] = n;
-  }
-}
-
 // Per-tile form: workgroup b (one wave) folds plane b's `tiles` partials in ssim_finalize_kernel's order for a
 // single-sample call and divides by the plane's own count; a plane with nothing counted is NaN with count 0.
 __global__ void ssim_tiles_finalize_kernel(const float* __restrict__ ssum, const unsigned int* __restrict__ scnt, int tiles,
                                            float* __restrict__ out, int* __restrict__ counts) {
   const int b = blockIdx.x;
   const double s = wave_fold(ssum + (size_t)b * tiles, tiles, 1, 0);
-  const long long m = wave_count(scnt + (size_t)b * tiles, tiles);
+  const long long m = wave_count(scnt + (size_t)b * tiles, tiles, 1, 0);
   if (threadIdx.x == 0) {
     out[b] = m > 0 ? (float)(s / (double)m) : __int_as_float(0x7fc00000);
     counts[b] = (int)m;
   }
 }
 
-}  // namespace
-
-extern "C" size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W) {
-  if (terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W)) return 0;
-  if ((terms & T_SSIM) && (H < 11 || W < 11)) return 0;
-  return layout(terms, planes, H, W).bytes;
+// the forward of one (SAME, MASKED) pair; the arguments are ssim_fwd_kernel's
+template <bool MASKED>
+void launch_ssim_fwd(bool same, dim3 grid, hipStream_t st, const float* pred, const float* gt, int H, int W, int Hm, int Wm,
+                     int tiles_x, const Win11& k, float* coef, long long cplane, float* part, const unsigned char* valid, int ld,
+                     long long ps, unsigned int* pcnt) {
+  if (same)
+    hipLaunchKernelGGL((ssim_fwd_kernel<true, MASKED>), grid, dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tiles_x, k, coef, cplane,
+                       part, valid, ld, ps, pcnt);
+  else
+    hipLaunchKernelGGL((ssim_fwd_kernel<false, MASKED>), grid, dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tiles_x, k, coef, cplane,
+                       part, valid, ld, ps, pcnt);
 }
 
-extern "C" int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int planes, int H, int W,
-                                       int n_keys, const int* key_slot, const double* key_weight,
-                                       const float* base_losses, float* out, void* workspace, jspsr_stream_t stream) {
-  if (!pred || !gt || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
-      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
-    return fail(JSPSR_EINVAL, "loss_menu_forward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_forward: workspace not 16-byte aligned");
-  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_forward: SSIM needs H, W >= 11");
+// ---- the menu's host path ----------------------------------------------------------------------------------------------
+// jspsr_loss_menu_* (no plane), jspsr_loss_menu_valid_* (K19: a plane, the SSIM bit refused) and
+// jspsr_loss_menu_valid_ssim_* (K23: a plane, SSIM under the "window" rule, ssim_rule 1 -- a map element counts iff every
+// pixel under its 11x11 window is valid) are one path.  name: the entry's, for its messages.
+struct Family {
+  const char* name;
+  bool masked, allow_ssim;
+  int ssim_rule;            // an entry without the argument passes 1
+};
+
+bool menu_query_ok(const Family& f, int terms, int planes, int H, int W) {
+  return terms > 0 && !(terms & ~T_ALL) && dims_ok(planes, H, W) && f.ssim_rule == 1 && (f.allow_ssim || !(terms & T_SSIM)) &&
+         !((terms & T_SSIM) && (H < 11 || W < 11));
+}
+
+// The refusals shared by forward and backward, in every entry's order; ptrs_ok: the caller's own pointer and count checks.
+int menu_args_ok(const Family& f, bool ptrs_ok, const unsigned char* valid, int terms, int planes, int H, int W,
+                 const void* workspace) {
+  if (!ptrs_ok || (f.masked && !valid) || !workspace || terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W))
+    return fail(JSPSR_EINVAL, "%s: bad arguments", f.name);
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", f.name);
+  if (f.ssim_rule != 1) return fail(JSPSR_EINVAL, "%s: ssim_rule %d (1 = window is the rule built)", f.name, f.ssim_rule);
+  if ((terms & T_SSIM) && !f.allow_ssim) return fail(JSPSR_EINVAL, "%s: SSIM over a validity plane is not built", f.name);
+  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "%s: SSIM needs H, W >= 11", f.name);
+  return JSPSR_OK;
+}
+
+int menu_forward(const Family& f, const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
+                 int H, int W, int n_keys, const int* key_slot, const double* key_weight, const float* base_losses, float* out,
+                 void* workspace, jspsr_stream_t stream) {
+  const bool ptrs_ok = pred && gt && out && key_slot && key_weight && n_keys > 0 && n_keys <= MAXKEY;
+  if (int e = menu_args_ok(f, ptrs_ok, valid, terms, planes, H, W, workspace)) return e;
   KeyMap km{};
   km.n = n_keys;
   for (int i = 0; i < n_keys; ++i) {
     const int s = key_slot[i];
     const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < NSLOT && (terms & (1 << (s - S_BERHU))));
-    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_forward: key %d has slot %d outside the configured terms", i, s);
+    if (!ok) return fail(JSPSR_EINVAL, "%s: key %d has slot %d outside the configured terms", f.name, i, s);
     km.slot[i] = s;
     km.w[i] = key_weight[i];
   }
-  const Layout L = layout(terms, planes, H, W);
+  const bool M = f.masked;
+  const Layout L = layout(terms, planes, H, W, M);
   char* ws = static_cast<char*>(workspace);
+  auto fl = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  auto un = [&](size_t off) { return reinterpret_cast<unsigned int*>(ws + off); };
+  auto ll = [&](size_t off) { return reinterpret_cast<long long*>(ws + off); };
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long n = (long long)planes * H * W;
-  const bool pw = terms & (T_BERHU | T_BCE | T_NORM);
+  const bool pw = terms & (T_BERHU | T_BCE | T_NORM), ss = terms & T_SSIM;
   if (terms & T_BERHU) {
-    hipLaunchKernelGGL(menu_max_kernel, dim3(L.nbm), dim3(PT), 0, st, pred, gt, n, reinterpret_cast<float*>(ws + L.pmax));
-    if (int e = check_launch("loss_menu_max")) return e;
+    if (M) hipLaunchKernelGGL(menu_max_kernel<true>, dim3(L.nbm), dim3(PT), 0, st, pred, gt, valid, n, fl(L.pmax));
+    else hipLaunchKernelGGL(menu_max_kernel<false>, dim3(L.nbm), dim3(PT), 0, st, pred, gt, nullptr, n, fl(L.pmax));
+    if (int e = check_launch(M ? "loss_menu_valid_max" : "loss_menu_max")) return e;
   }
   if (pw) {
-    hipLaunchKernelGGL(menu_sum_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, n, terms,
-                       reinterpret_cast<const float*>(ws + L.pmax), L.nbm, reinterpret_cast<float*>(ws),
-                       reinterpret_cast<float*>(ws + L.psum));
-    if (int e = check_launch("loss_menu_sum")) return e;
+    if (M) hipLaunchKernelGGL(menu_sum_kernel<true>, dim3(L.nb), dim3(PT), 0, st, pred, gt, valid, n, terms, fl(L.pmax), L.nbm,
+                              fl(0), fl(L.psum), un(L.pcnt));
+    else hipLaunchKernelGGL(menu_sum_kernel<false>, dim3(L.nb), dim3(PT), 0, st, pred, gt, nullptr, n, terms, fl(L.pmax), L.nbm,
+                            fl(0), fl(L.psum), nullptr);
+    if (int e = check_launch(M ? "loss_menu_valid_sum" : "loss_menu_sum")) return e;
+  }
+  if (ss) {
+    const dim3 grid(L.tiles_x * L.tiles_y, planes);
+    if (M) launch_ssim_fwd<true>(false, grid, st, pred, gt, H, W, L.Hm, L.Wm, L.tiles_x, gaussian_window(), fl(L.coef), L.cplane,
+                                 fl(L.ssum), valid, W, (long long)H * W, un(L.scnt));
+    else launch_ssim_fwd<false>(false, grid, st, pred, gt, H, W, L.Hm, L.Wm, L.tiles_x, gaussian_window(), fl(L.coef), L.cplane,
+                                fl(L.ssum), nullptr, 0, 0ll, nullptr);
+    if (int e = check_launch(M ? "ssim_valid_forward" : "ssim_forward")) return e;
+  }
+  const float* psum = pw ? fl(L.psum) : nullptr;
+  const float* ssum = ss ? fl(L.ssum) : nullptr;
+  if (M)
+    hipLaunchKernelGGL(menu_combine_kernel<true>, dim3(1), dim3(6 * 64), 0, st, psum, pw ? un(L.pcnt) : nullptr, L.nb, ssum,
+                       ss ? un(L.scnt) : nullptr, L.nbs, 0ll, 0ll, base_losses, km, out, ll(L.nn), ss ? ll(L.ns) : nullptr);
+  else
+    hipLaunchKernelGGL(menu_combine_kernel<false>, dim3(1), dim3(4 * 64), 0, st, psum, nullptr, L.nb, ssum, nullptr, L.nbs, n,
+                       L.cplane, base_losses, km, out, nullptr, nullptr);
+  return check_launch(M ? "loss_menu_valid_combine" : "loss_menu_combine");
+}
+
+int menu_backward(const Family& f, const float* pred, const float* gt, const unsigned char* valid, int terms, int planes,
+                  int H, int W, const double* slot_weight, const float* grad_total, float* grad_pred, const void* workspace,
+                  jspsr_stream_t stream) {
+  if (int e = menu_args_ok(f, pred && gt && grad_pred && slot_weight, valid, terms, planes, H, W, workspace)) return e;
+  const bool M = f.masked;
+  const Layout L = layout(terms, planes, H, W, M);
+  const char* ws = static_cast<const char*>(workspace);
+  const float* th = reinterpret_cast<const float*>(ws);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long n = (long long)planes * H * W;
+  const double wb = slot_weight[S_BERHU], wc = slot_weight[S_BCE], wn = slot_weight[S_NORM], wd = slot_weight[S_SSIM];
+  if (terms & (T_BERHU | T_BCE | T_NORM)) {
+    const double dn = (double)n;
+    if (M) hipLaunchKernelGGL(menu_bwd_kernel<true>, dim3(L.nb), dim3(PT), 0, st, pred, gt, valid, n, terms, th,
+                              reinterpret_cast<const long long*>(ws + L.nn), grad_total, wb, wc, wn, grad_pred);
+    else hipLaunchKernelGGL(menu_bwd_kernel<false>, dim3(L.nb), dim3(PT), 0, st, pred, gt, nullptr, n, terms, th, nullptr,
+                            grad_total, (float)(wb / dn), (float)(wc / dn), (float)(wn / (1e-12 * dn)), grad_pred);
+    if (int e = check_launch(M ? "loss_menu_valid_backward" : "loss_menu_backward")) return e;
   }
   if (terms & T_SSIM) {
-    hipLaunchKernelGGL((ssim_fwd_kernel<false, false>), dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
-                       L.Hm, L.Wm, L.tiles_x, gaussian_window(), reinterpret_cast<float*>(ws + L.coef), L.cplane,
-                       reinterpret_cast<float*>(ws + L.ssum), nullptr, 0, 0ll, nullptr);
-    if (int e = check_launch("ssim_forward")) return e;
+    const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
+    const float* coef = reinterpret_cast<const float*>(ws + L.coef);
+    if (M) hipLaunchKernelGGL(ssim_bwd_kernel<true>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, coef, L.cplane, H, W, L.Hm,
+                              L.Wm, tx, gaussian_window(), grad_total, 0.f, grad_pred, valid,
+                              reinterpret_cast<const long long*>(ws + L.ns), wd);
+    else hipLaunchKernelGGL(ssim_bwd_kernel<false>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, coef, L.cplane, H, W, L.Hm,
+                            L.Wm, tx, gaussian_window(), grad_total, (float)(wd / (double)L.cplane), grad_pred, nullptr, nullptr,
+                            0.0);
+    if (int e = check_launch(M ? "ssim_valid_backward" : "ssim_backward")) return e;
   }
-  hipLaunchKernelGGL(menu_combine_kernel, dim3(1), dim3(256), 0, st, pw ? reinterpret_cast<const float*>(ws + L.psum) : nullptr,
-                     L.nb, (terms & T_SSIM) ? reinterpret_cast<const float*>(ws + L.ssum) : nullptr, L.nbs, n, L.cplane,
-                     base_losses, km, out);
-  return check_launch("loss_menu_combine");
+  return JSPSR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t jspsr_loss_menu_workspace_bytes(int terms, int planes, int H, int W) {
+  return menu_query_ok({"", false, true, 1}, terms, planes, H, W) ? layout(terms, planes, H, W, false).bytes : 0;
+}
+
+extern "C" int jspsr_loss_menu_forward(const float* pred, const float* gt, int terms, int planes, int H, int W,
+                                       int n_keys, const int* key_slot, const double* key_weight,
+                                       const float* base_losses, float* out, void* workspace, jspsr_stream_t stream) {
+  return menu_forward({"loss_menu_forward", false, true, 1}, pred, gt, nullptr, terms, planes, H, W, n_keys, key_slot,
+                      key_weight, base_losses, out, workspace, stream);
 }
 
 extern "C" int jspsr_loss_menu_backward(const float* pred, const float* gt, int terms, int planes, int H, int W,
                                         const double* slot_weight, const float* grad_total, float* grad_pred,
                                         const void* workspace, jspsr_stream_t stream) {
-  if (!pred || !gt || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) || !dims_ok(planes, H, W))
-    return fail(JSPSR_EINVAL, "loss_menu_backward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_backward: workspace not 16-byte aligned");
-  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_backward: SSIM needs H, W >= 11");
-  const Layout L = layout(terms, planes, H, W);
-  const char* ws = static_cast<const char*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = (long long)planes * H * W;
-  if (terms & (T_BERHU | T_BCE | T_NORM)) {
-    const double dn = (double)n;
-    hipLaunchKernelGGL(menu_bwd_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, n, terms,
-                       reinterpret_cast<const float*>(ws), grad_total, (float)(slot_weight[S_BERHU] / dn),
-                       (float)(slot_weight[S_BCE] / dn), (float)(slot_weight[S_NORM] / (1e-12 * dn)), grad_pred);
-    if (int e = check_launch("loss_menu_backward")) return e;
-  }
-  if (terms & T_SSIM) {
-    const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
-    hipLaunchKernelGGL(ssim_bwd_kernel<false>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
-                       reinterpret_cast<const float*>(ws + L.coef), L.cplane, H, W, L.Hm, L.Wm, tx, gaussian_window(),
-                       grad_total, (float)(slot_weight[S_SSIM] / (double)L.cplane), grad_pred, nullptr, nullptr, 0.0);
-    if (int e = check_launch("ssim_backward")) return e;
-  }
-  return JSPSR_OK;
+  return menu_backward({"loss_menu_backward", false, true, 1}, pred, gt, nullptr, terms, planes, H, W, slot_weight, grad_total,
+                       grad_pred, workspace, stream);
 }
 
+// K19: jspsr_loss_menu_valid_ssim_* with the SSIM bit refused
 extern "C" size_t jspsr_loss_menu_valid_workspace_bytes(int terms, int planes, int H, int W) {
-  if (terms <= 0 || (terms & ~T_ALL) || (terms & T_SSIM) || !dims_ok(planes, H, W)) return 0;
-  return valid_layout(planes, H, W).bytes;
+  return menu_query_ok({"", true, false, 1}, terms, planes, H, W) ? layout(terms, planes, H, W, true).bytes : 0;
 }
 
 extern "C" int jspsr_loss_menu_valid_forward(const float* pred, const float* gt, const unsigned char* valid, int terms,
                                              int planes, int H, int W, int n_keys, const int* key_slot,
                                              const double* key_weight, const float* base_losses, float* out, void* workspace,
                                              jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
-      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
-    return fail(JSPSR_EINVAL, "loss_menu_valid_forward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_forward: workspace not 16-byte aligned");
-  if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_forward: SSIM over a validity plane is not built");
-  KeyMap km{};
-  km.n = n_keys;
-  for (int i = 0; i < n_keys; ++i) {
-    const int s = key_slot[i];
-    const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < S_SSIM && (terms & (1 << (s - S_BERHU))));
-    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_valid_forward: key %d has slot %d outside the configured terms", i, s);
-    km.slot[i] = s;
-    km.w[i] = key_weight[i];
-  }
-  const ValidLayout L = valid_layout(planes, H, W);
-  char* ws = static_cast<char*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = (long long)planes * H * W;
-  if (terms & T_BERHU) {
-    hipLaunchKernelGGL(menu_max_valid_kernel, dim3(L.nbm), dim3(PT), 0, st, pred, gt, valid, n,
-                       reinterpret_cast<float*>(ws + L.pmax));
-    if (int e = check_launch("loss_menu_valid_max")) return e;
-  }
-  hipLaunchKernelGGL(menu_sum_valid_kernel, dim3(L.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
-                     reinterpret_cast<const float*>(ws + L.pmax), L.nbm, reinterpret_cast<float*>(ws),
-                     reinterpret_cast<float*>(ws + L.psum), reinterpret_cast<unsigned int*>(ws + L.pcnt));
-  if (int e = check_launch("loss_menu_valid_sum")) return e;
-  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(COMBINE_VALID_THREADS), 0, st, reinterpret_cast<const float*>(ws + L.psum),
-                     reinterpret_cast<const unsigned int*>(ws + L.pcnt), L.nb, base_losses, km, out,
-                     reinterpret_cast<long long*>(ws + L.nn), nullptr, nullptr, 0, nullptr);
-  return check_launch("loss_menu_valid_combine");
+  return menu_forward({"loss_menu_valid_forward", true, false, 1}, pred, gt, valid, terms, planes, H, W, n_keys, key_slot,
+                      key_weight, base_losses, out, workspace, stream);
 }
 
 extern "C" int jspsr_loss_menu_valid_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
                                               int planes, int H, int W, const double* slot_weight, const float* grad_total,
                                               float* grad_pred, const void* workspace, jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
-      !dims_ok(planes, H, W))
-    return fail(JSPSR_EINVAL, "loss_menu_valid_backward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_backward: workspace not 16-byte aligned");
-  if (terms & T_SSIM) return fail(JSPSR_EINVAL, "loss_menu_valid_backward: SSIM over a validity plane is not built");
-  const ValidLayout L = valid_layout(planes, H, W);
-  const char* ws = static_cast<const char*>(workspace);
-  const long long n = (long long)planes * H * W;
-  hipLaunchKernelGGL(menu_bwd_valid_kernel, dim3(L.nb), dim3(PT), 0, static_cast<hipStream_t>(stream), pred, gt, valid, n,
-                     terms, reinterpret_cast<const float*>(ws), reinterpret_cast<const long long*>(ws + L.nn), grad_total,
-                     slot_weight[S_BERHU], slot_weight[S_BCE], slot_weight[S_NORM], grad_pred);
-  return check_launch("loss_menu_valid_backward");
+  return menu_backward({"loss_menu_valid_backward", true, false, 1}, pred, gt, valid, terms, planes, H, W, slot_weight,
+                       grad_total, grad_pred, workspace, stream);
+}
+
+// K23: the plane and SSIM under ssim_rule (1 = window)
+extern "C" size_t jspsr_loss_menu_valid_ssim_workspace_bytes(int terms, int planes, int H, int W, int ssim_rule) {
+  return menu_query_ok({"", true, true, ssim_rule}, terms, planes, H, W) ? layout(terms, planes, H, W, true).bytes : 0;
+}
+
+extern "C" int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                                  int planes, int H, int W, int ssim_rule, int n_keys, const int* key_slot,
+                                                  const double* key_weight, const float* base_losses, float* out,
+                                                  void* workspace, jspsr_stream_t stream) {
+  return menu_forward({"loss_menu_valid_ssim_forward", true, true, ssim_rule}, pred, gt, valid, terms, planes, H, W, n_keys,
+                      key_slot, key_weight, base_losses, out, workspace, stream);
+}
+
+extern "C" int jspsr_loss_menu_valid_ssim_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
+                                                   int planes, int H, int W, int ssim_rule, const double* slot_weight,
+                                                   const float* grad_total, float* grad_pred, const void* workspace,
+                                                   jspsr_stream_t stream) {
+  return menu_backward({"loss_menu_valid_ssim_backward", true, true, ssim_rule}, pred, gt, valid, terms, planes, H, W,
+                       slot_weight, grad_total, grad_pred, workspace, stream);
 }
 
 extern "C" size_t jspsr_ssim_workspace_bytes(int planes, int H, int W, int same) {
@@ -805,137 +734,10 @@ extern "C" int jspsr_ssim_forward(const float* pred, const float* gt, int planes
   const int tx = (Wm + ST - 1) / ST, ty = (Hm + ST - 1) / ST;
   float* part = static_cast<float*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (same)
-    hipLaunchKernelGGL((ssim_fwd_kernel<true, false>), dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
-                       nullptr, 0ll, part, nullptr, 0, 0ll, nullptr);
-  else
-    hipLaunchKernelGGL((ssim_fwd_kernel<false, false>), dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt, H, W, Hm, Wm, tx, k,
-                       nullptr, 0ll, part, nullptr, 0, 0ll, nullptr);
+  launch_ssim_fwd<false>(same, dim3(tx * ty, planes), st, pred, gt, H, W, Hm, Wm, tx, k, nullptr, 0ll, part, nullptr, 0, 0ll, nullptr);
   if (int e = check_launch("ssim_forward")) return e;
   hipLaunchKernelGGL(ssim_finalize_kernel, dim3(1), dim3(64), 0, st, part, tx * ty * planes, (long long)planes * Hm * Wm, out);
   return check_launch("ssim_finalize");
-}
-
-// ---- K23: SSIM over a validity plane, the "window" rule -----------------------------------------------------------------
-// The K19 menu entries plus SSIM: a map element counts iff every pixel under its 11x11 window is valid.  ssim_rule 1 =
-// window.  Without the SSIM bit these run exactly the launches of jspsr_loss_menu_valid_* on the same workspace layout.
-namespace {
-
-struct VsLayout {
-  ValidLayout V;
-  int nbs = 0, tiles_x = 0, tiles_y = 0, Hm = 0, Wm = 0;
-  size_t ssum = 0, scnt = 0, ns = 0, coef = 0, bytes = 0;
-  long long cplane = 0;
-};
-
-VsLayout vs_layout(int terms, int planes, int H, int W) {
-  VsLayout L;
-  L.V = valid_layout(planes, H, W);
-  size_t off = L.V.bytes;
-  if (terms & T_SSIM) {
-    L.Hm = H - 10; L.Wm = W - 10;
-    L.tiles_x = (L.Wm + ST - 1) / ST; L.tiles_y = (L.Hm + ST - 1) / ST;
-    L.nbs = L.tiles_x * L.tiles_y * planes;
-    L.ssum = off; off += al16((size_t)L.nbs * 4);
-    L.scnt = off; off += al16((size_t)L.nbs * 4);
-    L.ns = off; off += 16;    // long long N_s
-    L.cplane = (long long)planes * L.Hm * L.Wm;
-    L.coef = off; off += al16((size_t)L.cplane * 3 * 4);
-  }
-  L.bytes = off;
-  return L;
-}
-
-bool vs_args_ok(int terms, int planes, int H, int W, int ssim_rule) {
-  return terms > 0 && !(terms & ~T_ALL) && dims_ok(planes, H, W) && ssim_rule == 1 && !((terms & T_SSIM) && (H < 11 || W < 11));
-}
-
-}  // namespace
-
-extern "C" size_t jspsr_loss_menu_valid_ssim_workspace_bytes(int terms, int planes, int H, int W, int ssim_rule) {
-  if (!vs_args_ok(terms, planes, H, W, ssim_rule)) return 0;
-  return vs_layout(terms, planes, H, W).bytes;
-}
-
-extern "C" int jspsr_loss_menu_valid_ssim_forward(const float* pred, const float* gt, const unsigned char* valid, int terms,
-                                                  int planes, int H, int W, int ssim_rule, int n_keys, const int* key_slot,
-                                                  const double* key_weight, const float* base_losses, float* out,
-                                                  void* workspace, jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !out || !workspace || !key_slot || !key_weight || terms <= 0 || (terms & ~T_ALL) ||
-      !dims_ok(planes, H, W) || n_keys <= 0 || n_keys > MAXKEY)
-    return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_ssim_forward: workspace not 16-byte aligned");
-  if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
-  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: SSIM needs H, W >= 11");
-  KeyMap km{};
-  km.n = n_keys;
-  for (int i = 0; i < n_keys; ++i) {
-    const int s = key_slot[i];
-    const bool ok = (s >= S_L1 && s <= S_GRAD && base_losses) || (s >= S_BERHU && s < NSLOT && (terms & (1 << (s - S_BERHU))));
-    if (!ok) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_forward: key %d has slot %d outside the configured terms", i, s);
-    km.slot[i] = s;
-    km.w[i] = key_weight[i];
-  }
-  const VsLayout L = vs_layout(terms, planes, H, W);
-  char* ws = static_cast<char*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = (long long)planes * H * W;
-  const bool pw = terms & (T_BERHU | T_BCE | T_NORM), ss = terms & T_SSIM;
-  if (terms & T_BERHU) {
-    hipLaunchKernelGGL(menu_max_valid_kernel, dim3(L.V.nbm), dim3(PT), 0, st, pred, gt, valid, n,
-                       reinterpret_cast<float*>(ws + L.V.pmax));
-    if (int e = check_launch("loss_menu_valid_max")) return e;
-  }
-  if (pw) {
-    hipLaunchKernelGGL(menu_sum_valid_kernel, dim3(L.V.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
-                       reinterpret_cast<const float*>(ws + L.V.pmax), L.V.nbm, reinterpret_cast<float*>(ws),
-                       reinterpret_cast<float*>(ws + L.V.psum), reinterpret_cast<unsigned int*>(ws + L.V.pcnt));
-    if (int e = check_launch("loss_menu_valid_sum")) return e;
-  }
-  if (ss) {
-    hipLaunchKernelGGL((ssim_fwd_kernel<false, true>), dim3(L.tiles_x * L.tiles_y, planes), dim3(SN), 0, st, pred, gt, H, W,
-                       L.Hm, L.Wm, L.tiles_x, gaussian_window(), reinterpret_cast<float*>(ws + L.coef), L.cplane,
-                       reinterpret_cast<float*>(ws + L.ssum), valid, W, (long long)H * W,
-                       reinterpret_cast<unsigned int*>(ws + L.scnt));
-    if (int e = check_launch("ssim_valid_forward")) return e;
-  }
-  hipLaunchKernelGGL(menu_combine_valid_kernel, dim3(1), dim3(COMBINE_VALID_THREADS), 0, st,
-                     pw ? reinterpret_cast<const float*>(ws + L.V.psum) : nullptr,
-                     pw ? reinterpret_cast<const unsigned int*>(ws + L.V.pcnt) : nullptr, L.V.nb, base_losses, km, out,
-                     reinterpret_cast<long long*>(ws + L.V.nn), ss ? reinterpret_cast<const float*>(ws + L.ssum) : nullptr,
-                     ss ? reinterpret_cast<const unsigned int*>(ws + L.scnt) : nullptr, L.nbs,
-                     ss ? reinterpret_cast<long long*>(ws + L.ns) : nullptr);
-  return check_launch("loss_menu_valid_combine");
-}
-
-extern "C" int jspsr_loss_menu_valid_ssim_backward(const float* pred, const float* gt, const unsigned char* valid, int terms,
-                                                   int planes, int H, int W, int ssim_rule, const double* slot_weight,
-                                                   const float* grad_total, float* grad_pred, const void* workspace,
-                                                   jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !grad_pred || !workspace || !slot_weight || terms <= 0 || (terms & ~T_ALL) ||
-      !dims_ok(planes, H, W))
-    return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_menu_valid_ssim_backward: workspace not 16-byte aligned");
-  if (ssim_rule != 1) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: ssim_rule %d (1 = window is the rule built)", ssim_rule);
-  if ((terms & T_SSIM) && (H < 11 || W < 11)) return fail(JSPSR_EINVAL, "loss_menu_valid_ssim_backward: SSIM needs H, W >= 11");
-  const VsLayout L = vs_layout(terms, planes, H, W);
-  const char* ws = static_cast<const char*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = (long long)planes * H * W;
-  if (terms & (T_BERHU | T_BCE | T_NORM)) {
-    hipLaunchKernelGGL(menu_bwd_valid_kernel, dim3(L.V.nb), dim3(PT), 0, st, pred, gt, valid, n, terms,
-                       reinterpret_cast<const float*>(ws), reinterpret_cast<const long long*>(ws + L.V.nn), grad_total,
-                       slot_weight[S_BERHU], slot_weight[S_BCE], slot_weight[S_NORM], grad_pred);
-    if (int e = check_launch("loss_menu_valid_backward")) return e;
-  }
-  if (terms & T_SSIM) {
-    const int tx = (W + ST - 1) / ST, ty = (H + ST - 1) / ST;
-    hipLaunchKernelGGL(ssim_bwd_kernel<true>, dim3(tx * ty, planes), dim3(SN), 0, st, pred, gt,
-                       reinterpret_cast<const float*>(ws + L.coef), L.cplane, H, W, L.Hm, L.Wm, tx, gaussian_window(),
-                       grad_total, 0.f, grad_pred, valid, reinterpret_cast<const long long*>(ws + L.ns), slot_weight[S_SSIM]);
-    if (int e = check_launch("ssim_valid_backward")) return e;
-  }
-  return JSPSR_OK;
 }
 
 // Per-tile SSIM of a batch of uncropped (B,1,H,W) tiles: the crop of `border` on every side (int(H * border) rows,
@@ -970,12 +772,8 @@ extern "C" int jspsr_ssim_tiles_forward(const float* pred, const float* gt, cons
   unsigned int* pcnt = reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + half);
   const long long o = (long long)bh * W + bw;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (same)
-    hipLaunchKernelGGL((ssim_fwd_kernel<true, true>), dim3(tx * ty, B), dim3(SN), 0, st, pred + o, gt + o, h, w, Hm, Wm, tx, k,
-                       nullptr, 0ll, part, valid ? valid + o : nullptr, W, (long long)H * W, pcnt);
-  else
-    hipLaunchKernelGGL((ssim_fwd_kernel<false, true>), dim3(tx * ty, B), dim3(SN), 0, st, pred + o, gt + o, h, w, Hm, Wm, tx, k,
-                       nullptr, 0ll, part, valid ? valid + o : nullptr, W, (long long)H * W, pcnt);
+  launch_ssim_fwd<true>(same, dim3(tx * ty, B), st, pred + o, gt + o, h, w, Hm, Wm, tx, k, nullptr, 0ll, part,
+                        valid ? valid + o : nullptr, W, (long long)H * W, pcnt);
   if (int e = check_launch("ssim_tiles_forward")) return e;
   hipLaunchKernelGGL(ssim_tiles_finalize_kernel, dim3(B), dim3(64), 0, st, part, pcnt, tx * ty, out, counts);
   return check_launch("ssim_tiles_finalize");

@@ -7,6 +7,7 @@
 //     utils/common_config.py:241-291, configs/*.yml:71-76): HBM-bound, 16 B read + 12 B written per
 //     parameter.
 #include "common.h"
+#include "loss_fold.h"
 
 namespace {
 
@@ -16,76 +17,122 @@ constexpr int LT = 256;
 
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
-// pass 1: per-pixel d, Sobel of d, partial sums {sum|d|, sum d^2, sum(|gx|+|gy|)}, signs of gx, gy
+// The three loss kernels take MASKED (K19): the same loss over the elements a validity plane keeps.  valid: one byte per
+// element of pred, nonzero = valid.  One body per pass, so an all-ones plane gives the unmasked bits.  pred / gt at an
+// invalid element are read only behind a select (never multiplied by the mask: NaN * 0 is NaN).  A Sobel output is
+// counted iff its nine replicate-clamped taps are valid; an uncounted output stores sign bytes 0, which is all the adjoint
+// loop needs.  N (valid elements) and N_g (counted outputs) are counted as integers per workgroup, folded by the finalize
+// kernel and left in the workspace for the backward: no host round trip.
+
+// pass 1: per-pixel d, Sobel of d, partial sums {sum|d|, sum d^2, sum(|gx|+|gy|)}, signs of gx, gy; MASKED: pcnt {N, N_g}
+template <bool MASKED>
 __global__ __launch_bounds__(LT) void loss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     const unsigned char* __restrict__ valid,
                                                      signed char* __restrict__ sg, float* __restrict__ partial,
-                                                     int B, int H, int W) {
-  __shared__ float red[3][LT / 64];
+                                                     unsigned int* __restrict__ pcnt, int B, int H, int W) {
+  __shared__ float red[3 * (LT / 64)];
+  __shared__ unsigned int redc[MASKED ? 2 * (LT / 64) : 1];
   const long long n = (long long)B * H * W;
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  float s[3] = {0.f, 0.f, 0.f};
+  unsigned int cnt[2] = {0, 0};
   for (long long i = blockIdx.x * (long long)LT + threadIdx.x; i < n; i += (long long)gridDim.x * LT) {
     const int x = (int)(i % W);
     const int y = (int)((i / W) % H);
     const long long base = i - (long long)y * W - x;
     const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
     const int xm = x > 0 ? x - 1 : 0, xp = x < W - 1 ? x + 1 : W - 1;
-    auto D = [&](int yy, int xx) { const long long j = base + (long long)yy * W + xx; return pred[j] - gt[j]; };
-    const float d = D(y, x);
+    bool all = true;
+    auto D = [&](int yy, int xx) {
+      const long long j = base + (long long)yy * W + xx;
+      const float dj = pred[j] - gt[j];               // MASKED: loaded beside the plane's byte, not after it
+      if constexpr (MASKED) {
+        const bool vj = valid[j] != 0;
+        all = all && vj;
+        return vj ? dj : 0.f;
+      } else {
+        return dj;
+      }
+    };
+    const float d = D(y, x);                          // 0 at an invalid element: the sums keep their bits
+    const bool v = all;
     const float a = D(ym, xm), b = D(ym, x), c = D(ym, xp), e = D(y, xm), f = D(y, xp), g = D(yp, xm), h = D(yp, x), k = D(yp, xp);
     const float gx = ((c - a) + 2.f * (f - e) + (k - g)) * 0.125f;
     const float gy = ((g - a) + 2.f * (h - b) + (k - c)) * 0.125f;
-    s1 += fabsf(d);
-    s2 += d * d;
-    s3 += fabsf(gx) + fabsf(gy);
-    sg[2 * i] = (signed char)sgn(gx);
-    sg[2 * i + 1] = (signed char)sgn(gy);
+    s[0] += fabsf(d);
+    {
+#pragma clang fp contract(off)                        // a product and a sum
+      s[1] += d * d;
+    }
+    if constexpr (MASKED) {
+      cnt[0] += v ? 1u : 0u;
+      if (all) {
+        s[2] += fabsf(gx) + fabsf(gy);
+        ++cnt[1];
+      }
+      sg[2 * i] = all ? (signed char)sgn(gx) : (signed char)0;
+      sg[2 * i + 1] = all ? (signed char)sgn(gy) : (signed char)0;
+    } else {
+      s[2] += fabsf(gx) + fabsf(gy);
+      sg[2 * i] = (signed char)sgn(gx);
+      sg[2 * i + 1] = (signed char)sgn(gy);
+    }
   }
-  float v[3] = {s1, s2, s3};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int d2 = 32; d2 > 0; d2 >>= 1) v[q] += __shfl_xor(v[q], d2, 64);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float t = 0.f;
-    for (int w = 0; w < LT / 64; ++w) t += red[threadIdx.x][w];
-    partial[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-  }
+  block_fold3<LT, MASKED ? 2 : 0>(s, cnt, red, redc, partial, pcnt);
 }
 
-// losses[0..3] = {L1, L2, Grad, Total}
-__global__ void loss_finalize_kernel(const float* __restrict__ partial, int rows, long long n, float w1, float w2,
-                                     float wg, float* __restrict__ losses) {
+// losses[0..3] = {L1, L2, Grad, Total}.  MASKED: two more waves fold the counts, nn[0..1] = {N, N_g}, and an empty mask
+// gives 0, not 0 / 0; else both divisors are the host's n.
+template <bool MASKED>
+__global__ void loss_finalize_kernel(const float* __restrict__ partial, const unsigned int* __restrict__ pcnt, int rows,
+                                     long long n, float w1, float w2, float wg, float* __restrict__ losses,
+                                     long long* __restrict__ nn) {
   __shared__ double acc[3];
+  __shared__ long long cnt[2];
   const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (q < 3) {
-    double s = 0.0;
-    for (int r = lane; r < rows; r += 64) s += (double)partial[(size_t)r * 3 + q];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+    const double s = wave_fold(partial, rows, 3, q);
     if (lane == 0) acc[q] = s;
+  } else if constexpr (MASKED) {
+    const long long s = wave_count(pcnt, rows, 2, q - 3);
+    if (lane == 0) cnt[q - 3] = s;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double l1 = acc[0] / (double)n, l2 = acc[1] / (double)n, lg = acc[2] / (2.0 * (double)n);
+    long long m = n;
+    if constexpr (MASKED) { n = cnt[0]; m = cnt[1]; }
+    const bool any = !MASKED || n > 0, any_g = !MASKED || m > 0;
+    const double l1 = any ? acc[0] / (double)n : 0.0, l2 = any ? acc[1] / (double)n : 0.0;
+    const double lg = any_g ? acc[2] / (2.0 * (double)m) : 0.0;
     losses[0] = (float)l1; losses[1] = (float)l2; losses[2] = (float)lg;
     losses[3] = (float)(w1 * l1 + w2 * l2 + wg * lg);
+    if constexpr (MASKED) { nn[0] = n; nn[1] = m; }
   }
 }
 
 // pass 2: d(Total)/d(pred) * upstream scalar gradient.  Adjoint of the replicate-padded Sobel: pixel p
-// collects k[delta] * sign(g[q]) from every (q, delta) with clamp(q + delta) == p.
+// collects k[delta] * sign(g[q]) from every (q, delta) with clamp(q + delta) == p.  MASKED: N and N_g are loaded from
+// nn, and every invalid element gets +0.0.
+template <bool MASKED>
 __global__ __launch_bounds__(LT) void loss_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                     const signed char* __restrict__ sg, const float* __restrict__ gscale,
-                                                     float w1, float w2, float wg, float* __restrict__ gpred, int B,
-                                                     int H, int W) {
+                                                     const unsigned char* __restrict__ valid,
+                                                     const signed char* __restrict__ sg, const long long* __restrict__ nn,
+                                                     const float* __restrict__ gscale, float w1, float w2, float wg,
+                                                     float* __restrict__ gpred, int B, int H, int W) {
   const long long n = (long long)B * H * W;
+  long long nv = n, ngv = n;
+  if constexpr (MASKED) { nv = nn[0]; ngv = nn[1]; }
   const float up = gscale ? gscale[0] : 1.f;
-  const float c1 = up * w1 / (float)n, c2 = up * 2.f * w2 / (float)n, cg = up * wg / (2.f * (float)n) * 0.125f;
+  const bool any = !MASKED || nv > 0, any_g = !MASKED || ngv > 0;       // a count of 0: coefficient 0, not a division
+  const float c1 = any ? up * w1 / (float)nv : 0.f, c2 = any ? up * 2.f * w2 / (float)nv : 0.f;
+  const float cg = any_g ? up * wg / (2.f * (float)ngv) * 0.125f : 0.f;
   // kernels: gx weight kx[dy][dx] = {-1,0,1; -2,0,2; -1,0,1}, gy weight = its transpose
   for (long long i = blockIdx.x * (long long)LT + threadIdx.x; i < n; i += (long long)gridDim.x * LT) {
+    if constexpr (MASKED) {
+      if (!valid[i]) {
+        gpred[i] = 0.f;
+        continue;
+      }
+    }
     const int x = (int)(i % W);
     const int y = (int)((i / W) % H);
     const long long base = i - (long long)y * W - x;
@@ -113,7 +160,15 @@ __global__ __launch_bounds__(LT) void loss_bwd_kernel(const float* __restrict__ 
         }
       }
     }
-    gpred[i] = c1 * sgn(d) + c2 * d + cg * acc;
+    // c1 sgn(d) + c2 d + cg acc in stated roundings: both products rounded, their sum rounded, then one fused
+    // multiply-add of the Sobel part
+    float gv;
+    {
+#pragma clang fp contract(off)
+      const float t = c1 * sgn(d), u = c2 * d;
+      gv = __builtin_fmaf(cg, acc, t + u);
+    }
+    gpred[i] = gv;
   }
 }
 
@@ -203,258 +258,105 @@ int loss_blocks(long long n) {
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
+size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+struct LossLayout {         // partials at 0; masked: the count pairs and {N, N_g} between them and the sign bytes
+  int blocks = 0;
+  size_t cnt = 0, nn = 0, sg = 0, bytes = 0;
+};
+
+LossLayout layout(long long n, bool masked) {
+  LossLayout L;
+  L.blocks = loss_blocks(n);
+  size_t off = al16((size_t)L.blocks * 3 * sizeof(float));
+  if (masked) {
+    L.cnt = off; off += al16((size_t)L.blocks * 2 * sizeof(unsigned int));
+    L.nn = off; off += 16;
+  }
+  L.sg = off;
+  L.bytes = off + (size_t)n * 2;
+  return L;
+}
+
+// valid NULL is an error of a masked entry; an unmasked one passes NULL and masked = false
+int loss_forward(bool masked, const float* pred, const float* gt, const unsigned char* valid, float w1, float w2, float wg,
+                 float* losses, void* workspace, int B, int H, int W, jspsr_stream_t stream) {
+  const char* name = masked ? "loss_valid_forward" : "loss_forward";
+  if (!pred || !gt || (masked && !valid) || !losses || !workspace || B <= 0 || H <= 0 || W <= 0)
+    return fail(JSPSR_EINVAL, "%s: bad arguments", name);
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", name);
+  const long long n = (long long)B * H * W;
+  const LossLayout L = layout(n, masked);
+  char* ws = static_cast<char*>(workspace);
+  float* partial = reinterpret_cast<float*>(ws);
+  unsigned int* pcnt = reinterpret_cast<unsigned int*>(ws + L.cnt);
+  signed char* sg = reinterpret_cast<signed char*>(ws + L.sg);
+  long long* nn = reinterpret_cast<long long*>(ws + L.nn);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (masked) {
+    hipLaunchKernelGGL(loss_fwd_kernel<true>, dim3(L.blocks), dim3(LT), 0, s, pred, gt, valid, sg, partial, pcnt, B, H, W);
+    if (int e = check_launch("loss_valid_forward")) return e;
+    hipLaunchKernelGGL(loss_finalize_kernel<true>, dim3(1), dim3(320), 0, s, partial, pcnt, L.blocks, n, w1, w2, wg, losses, nn);
+    return check_launch("loss_valid_finalize");
+  }
+  hipLaunchKernelGGL(loss_fwd_kernel<false>, dim3(L.blocks), dim3(LT), 0, s, pred, gt, nullptr, sg, partial, nullptr, B, H, W);
+  if (int e = check_launch("loss_forward")) return e;
+  hipLaunchKernelGGL(loss_finalize_kernel<false>, dim3(1), dim3(192), 0, s, partial, nullptr, L.blocks, n, w1, w2, wg, losses,
+                     nullptr);
+  return check_launch("loss_finalize");
+}
+
+int loss_backward(bool masked, const float* pred, const float* gt, const unsigned char* valid, const float* grad_total,
+                  float w1, float w2, float wg, float* grad_pred, const void* workspace, int B, int H, int W,
+                  jspsr_stream_t stream) {
+  const char* name = masked ? "loss_valid_backward" : "loss_backward";
+  if (!pred || !gt || (masked && !valid) || !grad_pred || !workspace || B <= 0 || H <= 0 || W <= 0)
+    return fail(JSPSR_EINVAL, "%s: bad arguments", name);
+  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "%s: workspace not 16-byte aligned", name);
+  const LossLayout L = layout((long long)B * H * W, masked);
+  const char* ws = static_cast<const char*>(workspace);
+  const signed char* sg = reinterpret_cast<const signed char*>(ws + L.sg);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (masked) {
+    hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(L.blocks), dim3(LT), 0, s, pred, gt, valid, sg,
+                       reinterpret_cast<const long long*>(ws + L.nn), grad_total, w1, w2, wg, grad_pred, B, H, W);
+    return check_launch("loss_valid_backward");
+  }
+  hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(L.blocks), dim3(LT), 0, s, pred, gt, nullptr, sg, nullptr, grad_total, w1, w2,
+                     wg, grad_pred, B, H, W);
+  return check_launch("loss_backward");
+}
+
 }  // namespace
 
 extern "C" size_t jspsr_loss_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  const long long n = (long long)B * H * W;
-  return (((size_t)loss_blocks(n) * 3 * sizeof(float) + 15) & ~(size_t)15) + (size_t)n * 2;
+  return B <= 0 || H <= 0 || W <= 0 ? 0 : layout((long long)B * H * W, false).bytes;
+}
+
+extern "C" size_t jspsr_loss_valid_workspace_bytes(int B, int H, int W) {
+  return B <= 0 || H <= 0 || W <= 0 ? 0 : layout((long long)B * H * W, true).bytes;
 }
 
 extern "C" int jspsr_loss_forward(const float* pred, const float* gt, float w1, float w2, float wg, float* losses,
                                   void* workspace, int B, int H, int W, jspsr_stream_t stream) {
-  if (!pred || !gt || !losses || !workspace || B <= 0 || H <= 0 || W <= 0) return fail(JSPSR_EINVAL, "loss_forward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_forward: workspace not 16-byte aligned");
-  const long long n = (long long)B * H * W;
-  const int blocks = loss_blocks(n);
-  float* partial = static_cast<float*>(workspace);
-  signed char* sg = static_cast<signed char*>(workspace) + (((size_t)blocks * 3 * sizeof(float) + 15) & ~(size_t)15);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(loss_fwd_kernel, dim3(blocks), dim3(LT), 0, s, pred, gt, sg, partial, B, H, W);
-  if (int e = check_launch("loss_forward")) return e;
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(192), 0, s, partial, blocks, n, w1, w2, wg, losses);
-  return check_launch("loss_finalize");
+  return loss_forward(false, pred, gt, nullptr, w1, w2, wg, losses, workspace, B, H, W, stream);
 }
 
 extern "C" int jspsr_loss_backward(const float* pred, const float* gt, const float* grad_total, float w1, float w2,
                                    float wg, float* grad_pred, const void* workspace, int B, int H, int W,
                                    jspsr_stream_t stream) {
-  if (!pred || !gt || !grad_pred || !workspace || B <= 0 || H <= 0 || W <= 0) return fail(JSPSR_EINVAL, "loss_backward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_backward: workspace not 16-byte aligned");
-  const long long n = (long long)B * H * W;
-  const int blocks = loss_blocks(n);
-  const signed char* sg = static_cast<const signed char*>(workspace) + (((size_t)blocks * 3 * sizeof(float) + 15) & ~(size_t)15);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(blocks), dim3(LT), 0, static_cast<hipStream_t>(stream), pred, gt, sg, grad_total,
-                     w1, w2, wg, grad_pred, B, H, W);
-  return check_launch("loss_backward");
-}
-
-// ---- K19: the same loss over the elements a validity plane keeps ---------------------------------------------------------
-// valid: one byte per element of pred, nonzero = valid.  Same grid, loop order and fold order as the kernels above, so an
-// all-ones plane gives their bits.  pred / gt at an invalid element are read only behind a select (never multiplied by the
-// mask: NaN * 0 is NaN).  A Sobel output is counted iff its nine replicate-clamped taps are valid; an uncounted output
-// stores sign bytes 0, which is all the adjoint loop needs.  N (valid elements) and N_g (counted outputs) are counted as
-// integers per workgroup, folded by the finalize kernel and left in the workspace for the backward: no host round trip.
-namespace {
-
-struct ValidLayout {
-  size_t cnt, nn, sg, bytes;
-};
-
-ValidLayout valid_layout(long long n) {
-  const size_t blocks = (size_t)loss_blocks(n);
-  ValidLayout L;
-  L.cnt = (blocks * 3 * sizeof(float) + 15) & ~(size_t)15;
-  L.nn = L.cnt + ((blocks * 2 * sizeof(unsigned int) + 15) & ~(size_t)15);
-  L.sg = L.nn + 16;
-  L.bytes = L.sg + (size_t)n * 2;
-  return L;
-}
-
-__global__ __launch_bounds__(LT) void loss_valid_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                           const unsigned char* __restrict__ valid,
-                                                           signed char* __restrict__ sg, float* __restrict__ partial,
-                                                           unsigned int* __restrict__ pcnt, int B, int H, int W) {
-  __shared__ float red[3][LT / 64];
-  __shared__ unsigned int redc[2][LT / 64];
-  const long long n = (long long)B * H * W;
-  float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  unsigned int n1 = 0, ng = 0;
-  for (long long i = blockIdx.x * (long long)LT + threadIdx.x; i < n; i += (long long)gridDim.x * LT) {
-    const int x = (int)(i % W);
-    const int y = (int)((i / W) % H);
-    const long long base = i - (long long)y * W - x;
-    const int ym = y > 0 ? y - 1 : 0, yp = y < H - 1 ? y + 1 : H - 1;
-    const int xm = x > 0 ? x - 1 : 0, xp = x < W - 1 ? x + 1 : W - 1;
-    bool all = true;
-    auto D = [&](int yy, int xx) {
-      const long long j = base + (long long)yy * W + xx;
-      const float dj = pred[j] - gt[j];               // loaded beside the plane's byte, not after it; used behind the select
-      const bool vj = valid[j] != 0;
-      all = all && vj;
-      return vj ? dj : 0.f;
-    };
-    const float d = D(y, x);
-    const bool v = all;
-    const float a = D(ym, xm), b = D(ym, x), c = D(ym, xp), e = D(y, xm), f = D(y, xp), g = D(yp, xm), h = D(yp, x), k = D(yp, xp);
-    const float gx = ((c - a) + 2.f * (f - e) + (k - g)) * 0.125f;
-    const float gy = ((g - a) + 2.f * (h - b) + (k - c)) * 0.125f;
-    s1 += fabsf(d);                                   // d is 0 at an invalid element: the sums keep their bits
-    {
-#pragma clang fp contract(off)                        // loss_fwd_kernel compiles to a product and a sum; keep its bits
-      s2 += d * d;
-    }
-    n1 += v ? 1u : 0u;
-    if (all) {
-      s3 += fabsf(gx) + fabsf(gy);
-      ++ng;
-    }
-    sg[2 * i] = all ? (signed char)sgn(gx) : (signed char)0;
-    sg[2 * i + 1] = all ? (signed char)sgn(gy) : (signed char)0;
-  }
-  float vs[3] = {s1, s2, s3};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int d2 = 32; d2 > 0; d2 >>= 1) vs[q] += __shfl_xor(vs[q], d2, 64);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = vs[q];
-  }
-  unsigned int vc[2] = {n1, ng};
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-#pragma unroll
-    for (int d2 = 32; d2 > 0; d2 >>= 1) vc[q] += __shfl_xor(vc[q], d2, 64);
-    if ((threadIdx.x & 63) == 0) redc[q][threadIdx.x >> 6] = vc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    float t = 0.f;
-    for (int w = 0; w < LT / 64; ++w) t += red[threadIdx.x][w];
-    partial[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-  } else if (threadIdx.x < 5) {
-    unsigned int t = 0;
-    for (int w = 0; w < LT / 64; ++w) t += redc[threadIdx.x - 3][w];
-    pcnt[(size_t)blockIdx.x * 2 + threadIdx.x - 3] = t;
-  }
-}
-
-// losses[0..3] = {L1, L2, Grad, Total}; nn[0..1] = {N, N_g}.  An empty mask gives 0, not 0 / 0.
-__global__ void loss_valid_finalize_kernel(const float* __restrict__ partial, const unsigned int* __restrict__ pcnt, int rows,
-                                           float w1, float w2, float wg, float* __restrict__ losses,
-                                           long long* __restrict__ nn) {
-  __shared__ double acc[3];
-  __shared__ long long cnt[2];
-  const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (q < 3) {
-    double s = 0.0;
-    for (int r = lane; r < rows; r += 64) s += (double)partial[(size_t)r * 3 + q];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    if (lane == 0) acc[q] = s;
-  } else {
-    long long s = 0;
-    for (int r = lane; r < rows; r += 64) s += (long long)pcnt[(size_t)r * 2 + q - 3];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
-    if (lane == 0) cnt[q - 3] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const long long n = cnt[0], m = cnt[1];
-    const double l1 = n > 0 ? acc[0] / (double)n : 0.0, l2 = n > 0 ? acc[1] / (double)n : 0.0;
-    const double lg = m > 0 ? acc[2] / (2.0 * (double)m) : 0.0;
-    losses[0] = (float)l1; losses[1] = (float)l2; losses[2] = (float)lg;
-    losses[3] = (float)(w1 * l1 + w2 * l2 + wg * lg);
-    nn[0] = n; nn[1] = m;
-  }
-}
-
-// the adjoint loop of loss_bwd_kernel with n and n_g loaded; +0.0 at every invalid element
-__global__ __launch_bounds__(LT) void loss_valid_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                           const unsigned char* __restrict__ valid,
-                                                           const signed char* __restrict__ sg, const long long* __restrict__ nn,
-                                                           const float* __restrict__ gscale, float w1, float w2, float wg,
-                                                           float* __restrict__ gpred, int B, int H, int W) {
-  const long long n = (long long)B * H * W;
-  const long long nv = nn[0], ngv = nn[1];
-  const float up = gscale ? gscale[0] : 1.f;
-  const float c1 = nv > 0 ? up * w1 / (float)nv : 0.f, c2 = nv > 0 ? up * 2.f * w2 / (float)nv : 0.f;
-  const float cg = ngv > 0 ? up * wg / (2.f * (float)ngv) * 0.125f : 0.f;
-  for (long long i = blockIdx.x * (long long)LT + threadIdx.x; i < n; i += (long long)gridDim.x * LT) {
-    if (!valid[i]) {
-      gpred[i] = 0.f;
-      continue;
-    }
-    const int x = (int)(i % W);
-    const int y = (int)((i / W) % H);
-    const long long base = i - (long long)y * W - x;
-    const float d = pred[i] - gt[i];
-    float acc = 0.f;
-    for (int qy = y - 1; qy <= y + 1; ++qy) {
-      if (qy < 0 || qy >= H) continue;
-      for (int qx = x - 1; qx <= x + 1; ++qx) {
-        if (qx < 0 || qx >= W) continue;
-        const long long j = base + (long long)qy * W + qx;
-        const float sx = (float)sg[2 * j], sy = (float)sg[2 * j + 1];
-        if (sx == 0.f && sy == 0.f) continue;
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy) {
-          int ty = qy + dy; ty = ty < 0 ? 0 : (ty > H - 1 ? H - 1 : ty);
-          if (ty != y) continue;
-#pragma unroll
-          for (int dx = -1; dx <= 1; ++dx) {
-            int tx = qx + dx; tx = tx < 0 ? 0 : (tx > W - 1 ? W - 1 : tx);
-            if (tx != x) continue;
-            const float kx = (float)dx * (dy == 0 ? 2.f : 1.f);
-            const float ky = (float)dy * (dx == 0 ? 2.f : 1.f);
-            acc += kx * sx + ky * sy;
-          }
-        }
-      }
-    }
-    // the rounding steps loss_bwd_kernel's expression compiles to, spelled out so that an all-ones plane keeps its bits:
-    // both products rounded, their sum rounded, then one fused multiply-add of the Sobel part
-    float gv;
-    {
-#pragma clang fp contract(off)
-      const float t = c1 * sgn(d), u = c2 * d;
-      gv = __builtin_fmaf(cg, acc, t + u);
-    }
-    gpred[i] = gv;
-  }
-}
-
-}  // namespace
-
-extern "C" size_t jspsr_loss_valid_workspace_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return valid_layout((long long)B * H * W).bytes;
+  return loss_backward(false, pred, gt, nullptr, grad_total, w1, w2, wg, grad_pred, workspace, B, H, W, stream);
 }
 
 extern "C" int jspsr_loss_valid_forward(const float* pred, const float* gt, const unsigned char* valid, float w1, float w2,
                                         float wg, float* losses, void* workspace, int B, int H, int W, jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !losses || !workspace || B <= 0 || H <= 0 || W <= 0)
-    return fail(JSPSR_EINVAL, "loss_valid_forward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_valid_forward: workspace not 16-byte aligned");
-  const long long n = (long long)B * H * W;
-  const int blocks = loss_blocks(n);
-  const ValidLayout L = valid_layout(n);
-  char* ws = static_cast<char*>(workspace);
-  float* partial = reinterpret_cast<float*>(ws);
-  unsigned int* pcnt = reinterpret_cast<unsigned int*>(ws + L.cnt);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(loss_valid_fwd_kernel, dim3(blocks), dim3(LT), 0, s, pred, gt, valid,
-                     reinterpret_cast<signed char*>(ws + L.sg), partial, pcnt, B, H, W);
-  if (int e = check_launch("loss_valid_forward")) return e;
-  hipLaunchKernelGGL(loss_valid_finalize_kernel, dim3(1), dim3(320), 0, s, partial, pcnt, blocks, w1, w2, wg, losses,
-                     reinterpret_cast<long long*>(ws + L.nn));
-  return check_launch("loss_valid_finalize");
+  return loss_forward(true, pred, gt, valid, w1, w2, wg, losses, workspace, B, H, W, stream);
 }
 
 extern "C" int jspsr_loss_valid_backward(const float* pred, const float* gt, const unsigned char* valid,
                                          const float* grad_total, float w1, float w2, float wg, float* grad_pred,
                                          const void* workspace, int B, int H, int W, jspsr_stream_t stream) {
-  if (!pred || !gt || !valid || !grad_pred || !workspace || B <= 0 || H <= 0 || W <= 0)
-    return fail(JSPSR_EINVAL, "loss_valid_backward: bad arguments");
-  if (!aligned16(workspace)) return fail(JSPSR_EALIGN, "loss_valid_backward: workspace not 16-byte aligned");
-  const long long n = (long long)B * H * W;
-  const int blocks = loss_blocks(n);
-  const ValidLayout L = valid_layout(n);
-  const char* ws = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(loss_valid_bwd_kernel, dim3(blocks), dim3(LT), 0, static_cast<hipStream_t>(stream), pred, gt, valid,
-                     reinterpret_cast<const signed char*>(ws + L.sg), reinterpret_cast<const long long*>(ws + L.nn), grad_total,
-                     w1, w2, wg, grad_pred, B, H, W);
-  return check_launch("loss_valid_backward");
+  return loss_backward(true, pred, gt, valid, grad_total, w1, w2, wg, grad_pred, workspace, B, H, W, stream);
 }
 
 extern "C" int jspsr_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,

@@ -19,37 +19,64 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+# The C entries without and with a validity plane: (the fused L1 + L2 + Grad pair, the menu).  A masked call passes the
+# plane after gt, and the menu its SSIM rule after W; everything else is one argument list.  jspsr_loss_menu_valid_* is the
+# _valid_ssim_ family with the SSIM bit refused, so the menu never calls it.
+_ENTRY = {False: ("jspsr_loss", "jspsr_loss_menu"), True: ("jspsr_loss_valid", "jspsr_loss_menu_valid_ssim")}
+
+
+def _call(stem, what, *args):
+    name = f"{stem}_{what}"
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
+def _check_pair(pred, gt):
+    if not pred.is_cuda:
+        raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
+    if pred.shape != gt.shape or pred.dim() != 4:
+        raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
+
+
+def _fused_forward(pred, gt, valid, weights):
+    """jspsr_loss[_valid]_forward on contiguous fp32 (B,C,H,W) -> (losses[4], workspace)."""
+    B, C, H, W = pred.shape
+    stem = _ENTRY[valid is not None][0]
+    plane = () if valid is None else (valid.data_ptr(),)
+    ws = torch.empty(getattr(_lib.load(), stem + "_workspace_bytes")(B * C, H, W), dtype=torch.uint8, device=pred.device)
+    losses = torch.empty(4, dtype=torch.float32, device=pred.device)
+    _call(stem, "forward", pred.data_ptr(), gt.data_ptr(), *plane, *weights, losses.data_ptr(), ws.data_ptr(), B * C, H, W,
+          _stream())
+    return losses, ws
+
+
+def _fused_backward(pred, gt, valid, weights, g, ws):
+    """jspsr_loss[_valid]_backward: writes every element of the gradient (+0.0 at the invalid ones); g: d/d(Total), (1,)."""
+    B, C, H, W = pred.shape
+    plane = () if valid is None else (valid.data_ptr(),)
+    gp = torch.empty_like(pred)
+    _call(_ENTRY[valid is not None][0], "backward", pred.data_ptr(), gt.data_ptr(), *plane, g.data_ptr(), *weights,
+          gp.data_ptr(), ws.data_ptr(), B * C, H, W, _stream())
+    return gp
+
+
 class _FusedLoss(torch.autograd.Function):
+    """losses = (L1, L2, Grad, Total), over the elements `valid` keeps (K19) or, valid None, over all."""
+
     @staticmethod
-    def forward(ctx, pred, gt, w1, w2, wg):
-        if not pred.is_cuda:
-            raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
-        if pred.shape != gt.shape or pred.dim() != 4:
-            raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
+    def forward(ctx, pred, gt, valid, w1, w2, wg):
         pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
-        B, C, H, W = pred_c.shape
-        lib = _lib.load()
-        ws = torch.empty(lib.jspsr_loss_workspace_bytes(B * C, H, W), dtype=torch.uint8, device=pred.device)
-        losses = torch.empty(4, dtype=torch.float32, device=pred.device)
-        _lib.check(lib.jspsr_loss_forward(pred_c.data_ptr(), gt_c.data_ptr(), w1, w2, wg, losses.data_ptr(),
-                                          ws.data_ptr(), B * C, H, W, _stream()), "jspsr_loss_forward")
-        ctx.save_for_backward(pred_c, gt_c, ws)
+        losses, ws = _fused_forward(pred_c, gt_c, valid, (w1, w2, wg))
+        ctx.save_for_backward(pred_c, gt_c, valid, ws)
         ctx.w = (w1, w2, wg)
         ctx.mark_non_differentiable(gt)
         return losses
 
     @staticmethod
     def backward(ctx, glosses):
-        pred, gt, ws = ctx.saved_tensors
-        w1, w2, wg = ctx.w
-        B, C, H, W = pred.shape
-        g = glosses.float().contiguous()
-        gp = torch.empty_like(pred)
-        lib = _lib.load()
+        pred, gt, valid, ws = ctx.saved_tensors
         # only "Total" carries gradient (MultiLoss detaches the three components)
-        _lib.check(lib.jspsr_loss_backward(pred.data_ptr(), gt.data_ptr(), g[3:4].contiguous().data_ptr(), w1, w2, wg,
-                                           gp.data_ptr(), ws.data_ptr(), B * C, H, W, _stream()), "jspsr_loss_backward")
-        return gp, None, None, None, None
+        g = glosses.float().contiguous()[3:4].contiguous()
+        return _fused_backward(pred, gt, valid, ctx.w, g, ws), None, None, None, None, None
 
 
 def _plane(pred, valid):
@@ -67,47 +94,10 @@ def _plane(pred, valid):
     return valid.expand(B, C, H, W).contiguous()
 
 
-class _FusedLossValid(torch.autograd.Function):
-    """_FusedLoss over the elements `valid` keeps (jspsr_loss_valid_forward / _backward, K19)."""
-
-    @staticmethod
-    def forward(ctx, pred, gt, valid, w1, w2, wg):
-        pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
-        B, C, H, W = pred_c.shape
-        lib = _lib.load()
-        ws = torch.empty(lib.jspsr_loss_valid_workspace_bytes(B * C, H, W), dtype=torch.uint8, device=pred.device)
-        losses = torch.empty(4, dtype=torch.float32, device=pred.device)
-        _lib.check(lib.jspsr_loss_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), w1, w2, wg,
-                                                losses.data_ptr(), ws.data_ptr(), B * C, H, W, _stream()),
-                   "jspsr_loss_valid_forward")
-        ctx.save_for_backward(pred_c, gt_c, valid, ws)
-        ctx.w = (w1, w2, wg)
-        ctx.mark_non_differentiable(gt)
-        return losses
-
-    @staticmethod
-    def backward(ctx, glosses):
-        pred, gt, valid, ws = ctx.saved_tensors
-        w1, w2, wg = ctx.w
-        B, C, H, W = pred.shape
-        g = glosses.float().contiguous()
-        gp = torch.empty_like(pred)
-        lib = _lib.load()
-        _lib.check(lib.jspsr_loss_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), g[3:4].contiguous().data_ptr(),
-                                                 w1, w2, wg, gp.data_ptr(), ws.data_ptr(), B * C, H, W, _stream()),
-                   "jspsr_loss_valid_backward")
-        return gp, None, None, None, None, None
-
-
 def _fused(pred, gt, valid, weights):
-    """The fused L1 + L2 + Grad pair, unmasked (valid None: today's calls) or over a validity plane."""
-    if valid is None:
-        return _FusedLoss.apply(pred, gt, *weights)
-    if not pred.is_cuda:
-        raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
-    if pred.shape != gt.shape or pred.dim() != 4:
-        raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
-    return _FusedLossValid.apply(pred, gt, _plane(pred, valid), *weights)
+    """The fused L1 + L2 + Grad pair, unmasked (valid None) or over a validity plane."""
+    _check_pair(pred, gt)
+    return _FusedLoss.apply(pred, gt, None if valid is None else _plane(pred, valid), *weights)
 
 
 class MultiLoss(torch.nn.Module):
@@ -176,10 +166,7 @@ class _Spec:
 
     def check(self, pred, gt):
         """Shape rules, raised before any launch."""
-        if not pred.is_cuda:
-            raise RuntimeError("jspsr_amd losses run on the GPU only (no CPU fallback)")
-        if pred.shape != gt.shape or pred.dim() != 4:
-            raise ValueError(f"loss: expected equal (B,C,H,W) shapes, got {tuple(pred.shape)} {tuple(gt.shape)}")
+        _check_pair(pred, gt)
         if 5 in self.slots and pred.shape[1] != 1:
             raise ValueError(f"loss Norm: supported for one channel (the DEM head) only, got C = {pred.shape[1]}")
         if 6 in self.slots and (pred.shape[2] < 11 or pred.shape[3] < 11):
@@ -187,83 +174,24 @@ class _Spec:
 
 
 class _MenuLoss(torch.autograd.Function):
-    """out = (term of every key in config order..., Total).  Only Total carries gradient."""
-
-    @staticmethod
-    def forward(ctx, pred, gt, spec):
-        pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
-        B, C, H, W = pred_c.shape
-        P = B * C
-        lib = _lib.load()
-        base, bws = None, None
-        if spec.base:
-            bws = torch.empty(lib.jspsr_loss_workspace_bytes(P, H, W), dtype=torch.uint8, device=pred.device)
-            base = torch.empty(4, dtype=torch.float32, device=pred.device)
-            _lib.check(lib.jspsr_loss_forward(pred_c.data_ptr(), gt_c.data_ptr(), *spec.base_w, base.data_ptr(),
-                                              bws.data_ptr(), P, H, W, _stream()), "jspsr_loss_forward")
-        ws = torch.empty(lib.jspsr_loss_menu_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
-        out = torch.empty(len(spec.keys) + 1, dtype=torch.float32, device=pred.device)
-        _lib.check(lib.jspsr_loss_menu_forward(pred_c.data_ptr(), gt_c.data_ptr(), spec.terms, P, H, W, len(spec.keys),
-                                               spec.c_slots, spec.c_weights, base.data_ptr() if base is not None else None,
-                                               out.data_ptr(), ws.data_ptr(), _stream()), "jspsr_loss_menu_forward")
-        ctx.save_for_backward(pred_c, gt_c, ws, bws)
-        ctx.spec = spec
-        ctx.mark_non_differentiable(gt)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        pred, gt, ws, bws = ctx.saved_tensors
-        spec = ctx.spec
-        B, C, H, W = pred.shape
-        P = B * C
-        n = len(spec.keys)
-        g = gout[n:n + 1].float().contiguous()
-        lib = _lib.load()
-        if spec.base:   # writes the gradient of the L1 / L2 / Grad part; the menu adds its own terms
-            gp = torch.empty_like(pred)
-            _lib.check(lib.jspsr_loss_backward(pred.data_ptr(), gt.data_ptr(), g.data_ptr(), *spec.base_w, gp.data_ptr(),
-                                               bws.data_ptr(), P, H, W, _stream()), "jspsr_loss_backward")
-        else:
-            gp = torch.zeros_like(pred)
-        _lib.check(lib.jspsr_loss_menu_backward(pred.data_ptr(), gt.data_ptr(), spec.terms, P, H, W, spec.c_slot_w,
-                                                g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
-                   "jspsr_loss_menu_backward")
-        return gp, None, None
-
-
-class _MenuLossValid(torch.autograd.Function):
-    """_MenuLoss over the elements `valid` keeps (jspsr_loss_valid_* for the L1 / L2 / Grad part, jspsr_loss_menu_valid_*
-    for the rest, K19; jspsr_loss_menu_valid_ssim_* when SSIM is among the terms, K23)."""
+    """out = (term of every key in config order..., Total), over the elements `valid` keeps (K19; SSIM under spec's rule,
+    K23) or, valid None, over all.  Only Total carries gradient."""
 
     @staticmethod
     def forward(ctx, pred, gt, valid, spec):
         pred_c, gt_c = pred.float().contiguous(), gt.float().contiguous()
         B, C, H, W = pred_c.shape
         P = B * C
-        lib = _lib.load()
-        base, bws = None, None
-        if spec.base:
-            bws = torch.empty(lib.jspsr_loss_valid_workspace_bytes(P, H, W), dtype=torch.uint8, device=pred.device)
-            base = torch.empty(4, dtype=torch.float32, device=pred.device)
-            _lib.check(lib.jspsr_loss_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), *spec.base_w,
-                                                    base.data_ptr(), bws.data_ptr(), P, H, W, _stream()),
-                       "jspsr_loss_valid_forward")
+        stem = _ENTRY[valid is not None][1]
+        # the C side ignores the rule without the SSIM bit, except for its range check: 1 then
+        plane, rule = ((), ()) if valid is None else ((valid.data_ptr(),), (SSIM_RULES.get(spec.ssim_valid, 1),))
+        base, bws = _fused_forward(pred_c, gt_c, valid, spec.base_w) if spec.base else (None, None)
+        ws = torch.empty(getattr(_lib.load(), stem + "_workspace_bytes")(spec.terms, P, H, W, *rule), dtype=torch.uint8,
+                         device=pred.device)
         out = torch.empty(len(spec.keys) + 1, dtype=torch.float32, device=pred.device)
-        if 6 in spec.slots:
-            rule = SSIM_RULES[spec.ssim_valid]
-            ws = torch.empty(lib.jspsr_loss_menu_valid_ssim_workspace_bytes(spec.terms, P, H, W, rule), dtype=torch.uint8,
-                             device=pred.device)
-            _lib.check(lib.jspsr_loss_menu_valid_ssim_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P,
-                                                              H, W, rule, len(spec.keys), spec.c_slots, spec.c_weights,
-                                                              base.data_ptr() if base is not None else None, out.data_ptr(),
-                                                              ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_ssim_forward")
-        else:
-            ws = torch.empty(lib.jspsr_loss_menu_valid_workspace_bytes(spec.terms, P, H, W), dtype=torch.uint8, device=pred.device)
-            _lib.check(lib.jspsr_loss_menu_valid_forward(pred_c.data_ptr(), gt_c.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
-                                                         len(spec.keys), spec.c_slots, spec.c_weights,
-                                                         base.data_ptr() if base is not None else None, out.data_ptr(),
-                                                         ws.data_ptr(), _stream()), "jspsr_loss_menu_valid_forward")
+        _call(stem, "forward", pred_c.data_ptr(), gt_c.data_ptr(), *plane, spec.terms, P, H, W, *rule, len(spec.keys),
+              spec.c_slots, spec.c_weights, base.data_ptr() if base is not None else None, out.data_ptr(), ws.data_ptr(),
+              _stream())
         ctx.save_for_backward(pred_c, gt_c, valid, ws, bws)
         ctx.spec = spec
         ctx.mark_non_differentiable(gt)
@@ -274,32 +202,20 @@ class _MenuLossValid(torch.autograd.Function):
         pred, gt, valid, ws, bws = ctx.saved_tensors
         spec = ctx.spec
         B, C, H, W = pred.shape
-        P = B * C
         n = len(spec.keys)
         g = gout[n:n + 1].float().contiguous()
-        lib = _lib.load()
-        if spec.base:   # writes the L1 / L2 / Grad part, +0.0 at the invalid elements; the menu adds at the valid ones
-            gp = torch.empty_like(pred)
-            _lib.check(lib.jspsr_loss_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), g.data_ptr(),
-                                                     *spec.base_w, gp.data_ptr(), bws.data_ptr(), P, H, W, _stream()),
-                       "jspsr_loss_valid_backward")
-        else:
-            gp = torch.zeros_like(pred)
-        if 6 in spec.slots:
-            _lib.check(lib.jspsr_loss_menu_valid_ssim_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H,
-                                                               W, SSIM_RULES[spec.ssim_valid], spec.c_slot_w, g.data_ptr(),
-                                                               gp.data_ptr(), ws.data_ptr(), _stream()),
-                       "jspsr_loss_menu_valid_ssim_backward")
-        else:
-            _lib.check(lib.jspsr_loss_menu_valid_backward(pred.data_ptr(), gt.data_ptr(), valid.data_ptr(), spec.terms, P, H, W,
-                                                          spec.c_slot_w, g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream()),
-                       "jspsr_loss_menu_valid_backward")
+        plane, rule = ((), ()) if valid is None else ((valid.data_ptr(),), (SSIM_RULES.get(spec.ssim_valid, 1),))
+        # the fused pair writes the gradient of the L1 / L2 / Grad part (+0.0 at the invalid elements); the menu adds its
+        # own terms at the valid ones
+        gp = _fused_backward(pred, gt, valid, spec.base_w, g, bws) if spec.base else torch.zeros_like(pred)
+        _call(_ENTRY[valid is not None][1], "backward", pred.data_ptr(), gt.data_ptr(), *plane, spec.terms, B * C, H, W, *rule,
+              spec.c_slot_w, g.data_ptr(), gp.data_ptr(), ws.data_ptr(), _stream())
         return gp, None, None, None
 
 
 def _evaluate(spec, pred, gt, valid=None):
     """-> (components in config order, Total): one fused forward, one fused backward.  valid: the plane of the elements
-    that count, or None (today's calls)."""
+    that count, or None."""
     spec.check(pred, gt)
     n = len(spec.keys)
     if valid is not None:
@@ -308,10 +224,11 @@ def _evaluate(spec, pred, gt, valid=None):
                                       "of its own); drop SSIM from the criterion or pass valid=None")
         valid = _plane(pred, valid)
     if spec.terms == 0:      # L1 / L2 / Grad (any aliases) only: exactly the fused pair MultiLoss runs
-        v = _FusedLoss.apply(pred, gt, *spec.base_w) if valid is None else _FusedLossValid.apply(pred, gt, valid, *spec.base_w)
+        v = _FusedLoss.apply(pred, gt, valid, *spec.base_w)
         return [v[s].detach() for s in spec.slots], v[3]
-    v = _MenuLoss.apply(pred, gt, spec) if valid is None else _MenuLossValid.apply(pred, gt, valid, spec)
+    v = _MenuLoss.apply(pred, gt, valid, spec)
     return [v[i].detach() for i in range(n)], v[n]
+
 
 
 class LossTerm(torch.nn.Module):
