@@ -1026,6 +1026,41 @@ int jspsr_slope_classes(const float* z, long long pixels, const long long* scene
                         int n_thr, const unsigned char* valid, long long valid_numel, unsigned char* out,
                         jspsr_stream_t stream);
 
+/* ---- K25 (ABI v25, additive): single-channel fp32 rasters resampled to a finer grid -- F.interpolate with size=, mode
+ * "bicubic" or "bilinear" and align_corners=False, for a list of rasters of different shapes in one launch
+ * (csrc/resample.hip).  Upsampling only.  No workspace.
+ * jspsr_resample_axis: plain host code, no GPU.  The taps of one axis, output length H over a source of h: first HOST int32
+ *   [H], weights HOST fp32 [H][4].  In integers n = (2Y + 1) h - H, d = 2H, i = floor(n / d), r = n - i d; t = r / d in double.
+ *   JSPSR_RESAMPLE_BICUBIC (A = -0.75): first = i - 1, weights = { c2 at t + 1, c1 at t, c1 at 1 - t, c2 at 2 - t } with
+ *     c1 x = ((A + 2) x - (A + 3)) x^2 + 1 and c2 x = ((A x - 5A) x + 8A) x - 4A, evaluated in double, each rounded to fp32 once.
+ *   JSPSR_RESAMPLE_BILINEAR: n < 0 counts as 0 (i = 0, t = 0); first = i, weights = { 1 - t, t, 0, 0 } from double.
+ *   Tap k of output Y is the source index first[Y] + k clamped to [0, h - 1]; H == h gives weights { 0, 1, 0, 0 } and
+ *     { 1, 0, 0, 0 }.
+ *   JSPSR_EINVAL: a null pointer, another mode, h < 1, H < h (downsampling needs a prefilter and is not built).
+ * jspsr_resample_forward: ONE launch, no host synchronisation.
+ *   src     device fp32 [src_numel];  dst  device fp32 [dst_numel];  n rasters, 1..65535
+ *   table   device int64 [n][8] = { src_off, h, w, dst_off, H, W, ytaps_off, xtaps_off } and host_table, the same rows on
+ *     the HOST: every row is checked there against src_numel, dst_numel and n_taps before the launch (H >= h, W >= w).
+ *   first / weights  device int32 [n_taps] / fp32 [n_taps][4]: the axis tables of the call back to back, a raster's rows at
+ *     ytaps_off, its columns at xtaps_off, made by jspsr_resample_axis for `mode`.  Source indices are clamped in the
+ *     kernel, so a table that does not belong to the shapes gives wrong values and no access outside the buffers.
+ *   clamp   device fp32 [n][2] = { lo, hi } per raster, or NULL
+ *   src_void / dst_void  device uint8 [src_numel] / [dst_numel], both or neither: dst_void of an output pixel = src_void of
+ *     the source pixel (iy, ix) clamped to the raster, i the index above.
+ *   In fp32, every operation rounded once, no fused multiply-add, in exactly this order (bicubic; bilinear: two taps per
+ *     axis, the first one the centre): c = v[iy][ix], indices clamped; r_k = ((wx0 (v_k0 - c) + wx1 (v_k1 - c)) + wx2 (v_k2 -
+ *     c)) + wx3 (v_k3 - c); s = ((wy0 r_0 + wy1 r_1) + wy2 r_2) + wy3 r_3; out = s + c; with a clamp out < lo ? lo : (out > hi
+ *     ? hi : out), which keeps a NaN.  A numpy float32 restatement reproduces every bit, whatever rasters share the call.
+ *   JSPSR_EINVAL: a null pointer, another mode, n outside 1..65535, one void plane without the other, a row that
+ *     downsamples or leaves a buffer; JSPSR_EALIGN: a tensor not 4-byte, the table not 8-byte, weights not 16-byte aligned. */
+#define JSPSR_RESAMPLE_BICUBIC 0
+#define JSPSR_RESAMPLE_BILINEAR 1
+int jspsr_resample_axis(int h, int H, int mode, int* first, float* weights);
+int jspsr_resample_forward(const float* src, long long src_numel, float* dst, long long dst_numel, const long long* table,
+                           const long long* host_table, int n, const int* first, const float* weights, long long n_taps,
+                           int mode, const float* clamp, const unsigned char* src_void, unsigned char* dst_void,
+                           jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

@@ -80,13 +80,23 @@ class DeviceScenes:
     lr_dem must still be finite: voids in lr_dem AND hr_dem of one store are not built, so `nodata` (the lr_dem voids of
     `infer.InferenceScenes`, filled on the device at construction, K17) still raises NotImplementedError together with
     hr_dem.  Scores over the valid pixels only are `summary.summarise(valid=...)` with `summary.valid_plane` (K18).
+
+    lr_dem at its own resolution (K25, csrc/resample.hip, `resample.resample_rasters`): with `lr_resample="bicubic"` (or
+    "bilinear") lr_dem[i] may be smaller than the other rasters of scene i -- a 30 m DEM under 8 m imagery, any ratio >= 1 per
+    axis, the extents taken as equal as `F.interpolate(size=)` takes them.  The other rasters fix the scene's shape; a store
+    without any needs `lr_shape=(H, W)` (or one pair per scene).  The coarse raster is what is uploaded; base, range checks
+    (and void detection) read it; ONE launch at construction then resamples every scene to its shape, clamped to the
+    [min, max] of its valid coarse pixels (`lr_clamp`), so that bicubic overshoot cannot leave the range the host checked,
+    go below the `relative` base or reach the log of a non-positive number.  `shapes` holds the scenes' (fine) shapes,
+    `lr_shapes` the coarse ones; after construction the store is what host-resampled scenes would have given, and batches,
+    prepare and every pass downstream are unchanged.  lr_resample=None (the default) keeps requiring equal shapes.
     """
 
     def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
                  relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
                  normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda", nodata=None,
-                 hr_nodata=None, valid=None):
+                 hr_nodata=None, valid=None, lr_resample: str | None = None, lr_shape=None):
         if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
             raise KeyError("hr_dem")
         if nodata is not None:
@@ -96,16 +106,20 @@ class DeviceScenes:
         self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device,
-                    hr_nodata=hr_nodata, valid=valid)
+                    hr_nodata=hr_nodata, valid=valid, lr_resample=lr_resample, lr_shape=lr_shape)
 
     def _setup(self, raw: dict, coord, *, relative, elev_min, elev_max, elev_log, scale_mask, mask_channel, image_range,
                label_range, normalize, ids, device, base=None, nodata=None, void_margin=0, fill_limit=None, hr_nodata=None,
-               valid=None):
+               valid=None, lr_resample=None, lr_shape=None):
         """Checks, layout and upload of a store holding the kinds of `raw` that are not None (`infer.InferenceScenes` is
         the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`.  nodata, void_margin,
         fill_limit: the voids of lr_dem (K17, `infer.InferenceScenes`); nodata=None changes nothing.  hr_nodata, valid: the
-        voids of hr_dem (K19, see the class docstring); both None changes nothing."""
+        voids of hr_dem (K19, see the class docstring); both None changes nothing.  lr_resample, lr_shape: lr_dem on a
+        coarser grid of its own (K25, see the class docstring); lr_resample=None changes nothing."""
         lr_dem = raw["lr_dem"]
+        if lr_resample is not None:
+            from . import resample                                   # resample imports infer, which imports this module
+            resample._mode(lr_resample)
         void_margin = _whole("void_margin", void_margin)
         fill_limit = None if fill_limit is None else _whole("fill_limit", fill_limit)
         if nodata is not None and raw.get("hr_dem") is not None:
@@ -142,14 +156,18 @@ class DeviceScenes:
         for kind in ("lr_dem", "hr_dem", "canopy"):
             if kind in host and self.channels[kind] != 1:
                 raise ValueError(f"{kind} has {self.channels[kind]} channels, not 1")
+        self.lr_shapes = [a.shape[:2] for a in host["lr_dem"]]
+        self.shapes = self.lr_shapes if lr_resample is None else self._fine_shapes(host, lr_shape)
+        if lr_resample is None and lr_shape is not None:
+            raise ValueError("lr_shape: only together with lr_resample")
         for kind, arrs in host.items():
             for i, a in enumerate(arrs):
-                if a.shape[2] != self.channels[kind] or a.shape[:2] != host["lr_dem"][i].shape[:2]:
+                if a.shape[2] != self.channels[kind] or a.shape[:2] != (self.lr_shapes if kind == "lr_dem" else self.shapes)[i]:
                     raise ValueError(f"{kind}[{i}] {a.shape} does not match lr_dem {host['lr_dem'][i].shape} / "
-                                     f"{self.channels[kind]} channels")
+                                     f"{self.channels[kind]} channels" if lr_resample is None else
+                                     f"{kind}[{i}] {a.shape} does not match the scene's {self.shapes[i]} / {self.channels[kind]} channels")
             if self.channels[kind] > 16:
                 raise ValueError(f"{kind}: {self.channels[kind]} channels, the kernel takes at most 16")
-        self.shapes = [a.shape[:2] for a in host["lr_dem"]]
         if coord and any(h < 2 or w < 2 for h, w in self.shapes):
             raise ValueError("local coordinates need scenes of at least 2 x 2 pixels")
         self.ids = [str(i) for i in range(n)] if ids is None else [str(i) for i in ids]
@@ -181,10 +199,13 @@ class DeviceScenes:
         self.scene_table = torch.tensor([[int(offs[i]), h, w] for i, (h, w) in enumerate(self.shapes)], dtype=torch.int64,
                                         device=self.device)
         # one flat buffer per kind; the store is never modified
-        self.store = {k: torch.from_numpy(np.concatenate([a.reshape(-1) for a in v])).to(self.device) for k, v in host.items()}
+        self.store = {k: torch.from_numpy(np.concatenate([a.reshape(-1) for a in v])).to(self.device) for k, v in host.items()
+                      if lr_resample is None or k != "lr_dem"}
         self.flags = ((LOG if elev_log else 0) | (SCALE_MASK if scale_mask else 0) | (IMAGE_11 if image_range == "[-1, 1]" else 0)
                       | (LABEL_11 if label_range == "[-1, 1]" else 0) | (IMAGE_255 if image_range == "[0, 255]" else 0))
-        if voids is not None:
+        if lr_resample is not None:
+            self._resample_lr(host["lr_dem"], voids, nodata, void_margin, fill_limit, lr_resample)
+        elif voids is not None:
             self._fill_voids(voids, nodata, void_margin, fill_limit)
         if planes is not None:                   # K19: one byte per pixel at the scenes' pixel offsets, padded to 4 bytes
             flat = np.concatenate([p.reshape(-1) for p in planes]).astype(np.uint8)
@@ -233,17 +254,76 @@ class DeviceScenes:
         self.void_out = self.void
         if sum(self.void_counts) == 0:
             return
-        host_table = np.array([[0, h, w] for h, w in self.shapes], dtype=np.int64)
-        host_table[1:, 0] = np.cumsum([h * w for h, w in self.shapes])[:-1]
+        host_table = infer._host_table(self.shapes)
+        self._fill(self.store["lr_dem"], self.void, self.scene_table, host_table, fill_limit)
+        if void_margin > 0:
+            self.void_out = self._margin(self.void, self.scene_table, host_table, void_margin)
+
+    def _fill(self, dem, void, table, host_table, fill_limit):
+        """Every void of the flat buffer `dem` <- its nearest valid pixel of the same scene, or the scene's base."""
+        from . import infer
         src = None
         if fill_limit is None or fill_limit > 0:
-            src, _ = infer._nearest_seed(self.void ^ 1, self.scene_table, host_table, fill_limit or 0)
+            src, _ = infer._nearest_seed(void ^ 1, table, host_table, fill_limit or 0)
         base = torch.tensor([float(np.float32(b)) for b in self.base], dtype=torch.float32, device=self.device)
-        infer.fill_voids(self.store["lr_dem"], self.void, src, self.scene_table, base)
-        del src
-        if void_margin > 0:
-            _, d2 = infer._nearest_seed(self.void, self.scene_table, host_table, void_margin)
-            self.void_out = (d2 >= 0).to(torch.uint8)
+        infer.fill_voids(dem, void, src, table, base)
+
+    @staticmethod
+    def _margin(void, table, host_table, void_margin):
+        """The output mask: void, or within the Euclidean distance `void_margin` of one."""
+        from . import infer
+        _, d2 = infer._nearest_seed(void, table, host_table, void_margin)
+        return (d2 >= 0).to(torch.uint8)
+
+    lr_clamp = None                              # K25: per-scene (lo, hi) the resampled lr_dem was clamped to, if any
+
+    def _fine_shapes(self, host: dict, lr_shape) -> list:
+        """The scenes' shapes under `lr_resample`: those of the rasters other than lr_dem, else `lr_shape` -- one (H, W) for
+        all scenes or one per scene.  No side of a scene may be shorter than its lr_dem's."""
+        n = len(host["lr_dem"])
+        others = [k for k in host if k != "lr_dem"]
+        if lr_shape is not None:
+            given = np.asarray(lr_shape, dtype=np.int64)
+            if given.shape not in ((2,), (n, 2)):
+                raise ValueError(f"lr_shape: one (H, W) or one per scene, got shape {given.shape}")
+            given = [tuple(int(v) for v in (given if given.ndim == 1 else given[i])) for i in range(n)]
+        if others:
+            fine = [tuple(host[others[0]][i].shape[:2]) for i in range(n)]
+            if lr_shape is not None and fine != given:
+                raise ValueError(f"lr_shape {given} does not match the shapes of {others[0]}: {fine}")
+        elif lr_shape is None:
+            raise ValueError("lr_resample: the store has no other raster to take the scenes' shapes from: give lr_shape=(H, W)")
+        else:
+            fine = given
+        for i, ((h, w), (H, W)) in enumerate(zip(self.lr_shapes, fine)):
+            if H < h or W < w:
+                raise ValueError(f"lr_dem[{i}] is {h} x {w}, its scene {H} x {W}: downsampling needs a prefilter and is not built")
+        return fine
+
+    def _resample_lr(self, coarse: list, voids, nodata, void_margin: int, fill_limit, mode: str):
+        """The device side of `lr_resample` (K25, csrc/resample.hip), once, at construction: upload lr_dem on its own grid,
+        with `nodata` fill its voids there (K17, `fill_limit` in coarse pixels), then ONE launch resamples every scene to its
+        shape, clamped to the [min, max] of its valid coarse pixels, and writes the void plane of the fine grid beside it (a
+        fine pixel is a void where its centre tap, the coarse pixel at the floor of its coordinate, is); `void_margin` is applied on the fine grid."""
+        from . import infer, resample
+        host_table = infer._host_table(self.lr_shapes)
+        table = torch.from_numpy(host_table).to(self.device)
+        lr = torch.from_numpy(np.concatenate([a.reshape(-1) for a in coarse])).to(self.device)
+        void = None
+        if voids is not None:
+            self.nodata, self.void_margin, self.fill_limit = nodata, void_margin, fill_limit
+            self.void_counts = [int(v.sum()) for v in voids]                   # counted on lr_dem's own grid
+            void = torch.from_numpy(np.concatenate([v.reshape(-1) for v in voids]).astype(np.uint8)).to(self.device)
+            if sum(self.void_counts) > 0:
+                self._fill(lr, void, table, host_table, fill_limit)
+        good = [a if voids is None else a[~voids[i]] for i, a in enumerate(coarse)]
+        self.lr_clamp = [(np.float32(g.min()), np.float32(g.max())) for g in good]
+        out = resample.resample_rasters(lr, host_table, self.shapes, mode, clamp=self.lr_clamp, void=void)
+        self.store["lr_dem"] = out[0]
+        if void is not None:
+            self.void = self.void_out = out[2]
+            if void_margin > 0 and sum(self.void_counts) > 0:
+                self.void_out = self._margin(self.void, self.scene_table, infer._host_table(self.shapes), void_margin)
 
     def void_mask(self, i: int, out: bool = False) -> torch.Tensor:
         """(H, W) bool view on the device of scene i's voids; out=True: of its output mask (void or within `void_margin`

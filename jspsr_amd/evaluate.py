@@ -7,7 +7,7 @@ runs the model and one meter object per score on ONE tile per step (valid_batch_
 `.item()`; here a batch of any size is scored by one launch (`metrics.batch_scores`, K10), the rows stay in a device
 table, and a pass ends in one device-to-host copy.
 
-Left out: plotting, GeoTIFF output, the skimage and richdem packages and the bicubic resize of a smaller input.
+Left out: plotting, GeoTIFF output and the skimage and richdem packages.
 (EarlyStopper is in jspsr_amd/train.py; the scene mosaics and summarise_evaluation's table in jspsr_amd/summary.py, fed
 through `evaluate(..., collector=)`.)
 """
@@ -371,14 +371,16 @@ def _sample_additive(criterion):
 
 
 @torch.no_grad()
-def evaluate(model, batches, criterion, meter, model_name, input_data, compare_input=False, collector=None):
+def evaluate(model, batches, criterion, meter, model_name, input_data, compare_input=False, collector=None, resize_input=None):
     """eval_model (evaluate_utils.py:274-357) without plotting and disk output: `model.eval()`, no gradients, and for each
     batch of `batches` (e.g. `data.TileCropBatches`, any batch size): `criterion.reset()`, `data.batch_pair`, the
     forward, the criterion, `meter.update`.  `meter` is reset first (the reference builds a new one per call).
 
     -> (scores, mean Total loss, {term: mean}); with compare_input=True a fourth item, the scores of the input DEM
-    `inputs[0][:, 0:1]` against the target from a second meter (evaluate_utils.py:325-342).  An input of another size (the
-    reference resizes it bicubically) raises NotImplementedError.
+    `inputs[0][:, 0:1]` against the target from a second meter (evaluate_utils.py:325-342).  An input of another size
+    raises NotImplementedError unless resize_input="bicubic" is given: it is then resized to the target's size on the
+    device (`resample.resize`, K25: the reference's `F.interpolate(..., mode="bicubic")`, evaluate_utils.py:331-332), without
+    a clamp -- the meter clamps, as in the reference.
 
     The loss means are weighted per sample, as `AverageMeter.update(v.item(), gt.size(0))` weights them.  With the
     reference's batch of one, every logged value is a single sample's value; to report the same means at any batch size,
@@ -402,6 +404,8 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
     averaged over the tiles that have a valid pixel for it, and `meter.counts()` holds every tile's counts.  A meter that
     was not built with masked=True together with such a batch raises NotImplementedError before the forward."""
     model.eval()
+    if resize_input not in (None, "bicubic"):
+        raise ValueError(f"evaluate: resize_input is None or 'bicubic', got {resize_input!r}")
     if meter is None and compare_input:
         raise ValueError("evaluate: compare_input needs a meter")
     if meter is not None:
@@ -440,8 +444,11 @@ def evaluate(model, batches, criterion, meter, model_name, input_data, compare_i
         if compare_input:
             data_input = inputs[0][:, 0:1]
             if data_input.shape[-2:] != gt.shape[-2:]:
-                raise NotImplementedError(f"evaluate: the input DEM is {tuple(data_input.shape[-2:])}, the target "
-                                          f"{tuple(gt.shape[-2:])}; the reference's bicubic resize is not built")
+                if resize_input is None:
+                    raise NotImplementedError(f"evaluate: the input DEM is {tuple(data_input.shape[-2:])}, the target "
+                                              f"{tuple(gt.shape[-2:])}; the reference's bicubic resize is not built")
+                from .resample import resize
+                data_input = resize(data_input.float(), gt.shape[-2:], resize_input)
             if valid is not None:
                 meter_in.update(data_input, gt, meta=meta, valid=valid)
             else:

@@ -151,16 +151,26 @@ class InferenceScenes(DeviceScenes):
     the tiled passes read it unchanged.  `void_out` (`void_mask(i, out=True)`): void, or within the Euclidean distance
     `void_margin` of one (0: `void` itself, the same tensor); `predict_scenes(mask_voids=True)` writes np.float32(nodata)
     there.  Such results are scored over the valid pixels only by `summary.summarise(valid=...)` (K18).  Voids in image, mask
-    or canopy and voids together with hr_dem are not built."""
+    or canopy and voids together with hr_dem are not built.
+
+    lr_dem at its own resolution (K25, csrc/resample.hip; `data.DeviceScenes` has the whole account).
+    lr_resample="bicubic" | "bilinear": lr_dem[i] may be coarser than the other rasters of scene i, which fix the scene's
+    shape (no other raster: lr_shape=(H, W), or one pair per scene); it is uploaded as it is and resampled on the device at
+    construction, clamped to the [min, max] of its valid pixels.  `shapes` are the scenes' shapes, `lr_shapes` those of
+    lr_dem.  With `nodata` the voids are found and filled on lr_dem's own grid (`fill_limit` and `void_counts` in its
+    pixels), `void` is written on the scene's grid -- a pixel is a void where its centre tap (the lr_dem pixel at the floor of its
+    coordinate) is -- and
+    `void_margin` is applied there.  After construction the store is what host-resampled scenes would have given."""
 
     def __init__(self, lr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *, relative: bool = False,
                  elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, ids: Sequence[str] | None = None,
-                 device="cuda", base: Sequence | None = None, nodata=None, void_margin: int = 0, fill_limit: int | None = None):
+                 device="cuda", base: Sequence | None = None, nodata=None, void_margin: int = 0, fill_limit: int | None = None,
+                 lr_resample: str | None = None, lr_shape=None):
         self._setup({"lr_dem": lr_dem, "hr_dem": None, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=None, normalize=None, ids=ids, device=device, base=base,
-                    nodata=nodata, void_margin=void_margin, fill_limit=fill_limit)
+                    nodata=nodata, void_margin=void_margin, fill_limit=fill_limit, lr_resample=lr_resample, lr_shape=lr_shape)
 
 
 def _input_kinds(scenes):
