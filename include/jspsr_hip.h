@@ -1061,6 +1061,34 @@ int jspsr_resample_forward(const float* src, long long src_numel, float* dst, lo
                            int mode, const float* clamp, const unsigned char* src_void, unsigned char* dst_void,
                            jspsr_stream_t stream);
 
+/* ---- K26 (ABI v25, additive): HWC uint8 rasters brought to a coarser grid by their exact area mean -- image, mask and
+ * canopy held finer than their scene -- for a list of rasters of different shapes and one channel count in one launch
+ * (csrc/area.hip).  Downsampling (and the identity) only, any ratio >= 1 per axis.  No workspace.
+ * The rule of one axis, output length H over a source of h, 1 <= H <= h <= 65535: the weight of source pixel i under output Y
+ *   is the overlap a(Y, i) = min((Y + 1) h, (i + 1) H) - max(Y h, i H) where positive; taps i0 = floor(Y h / H) ..
+ *   floor(((Y + 1) h - 1) / H), at most ceil(h / H) + 1; sum_i a = h, sum_Y a = H.
+ * jspsr_area_axis: plain host code, no GPU.  first / count HOST int32 [H]: the first source index and the number of taps
+ *   of every output; weights HOST uint32 [H][ceil(h / H) + 1] or NULL: a(Y, first[Y] + k), zero past count[Y] -- from the
+ *   inline the kernel evaluates.  JSPSR_EINVAL: a null first or count, h or H < 1, H > h (upsampling), h > 65535.
+ * jspsr_area_forward: ONE launch, no host synchronisation, integer accumulators.
+ *   src     device uint8 [src_numel][channels];  dst  device uint8 [dst_numel][channels] (numel in PIXELS);  channels 1..16
+ *   table   device int64 [n][6] = { src_off, h, w, dst_off, H, W }, offsets in pixels, and host_table, the same rows on the
+ *     HOST: every row is checked there before the launch.  n rasters, 1..65535.
+ *   With S = sum_y sum_x a_y a_x v per channel and D = h w:
+ *   JSPSR_AREA_MEAN      out = floor((S + floor(D / 2)) / D), exactly (round half up); H == h and W == w copies the raster.
+ *   JSPSR_AREA_MAJORITY  a non-zero byte counts as 1; none = D - sum_c S_c (signed); c* = the lowest index among the
+ *     channels of largest S_c; the output pixel is one-hot (a byte 1) at c* iff S_c* > 0 and S_c* >= none, else all zeros.
+ *   Every raster's bytes are those of the raster alone, on every run.
+ *   JSPSR_EINVAL: a null pointer, another mode, channels outside 1..16, n outside 1..65535, a row with an empty side, one
+ *     that upsamples (H > h or W > w), a source side above 65535 (the weight products are 32-bit, S + D / 2 < 2^40) or one
+ *     that leaves src or dst; JSPSR_EALIGN: the table not 8-byte aligned.  src and dst need no alignment. */
+#define JSPSR_AREA_MEAN 0
+#define JSPSR_AREA_MAJORITY 1
+int jspsr_area_axis(int h, int H, int* first, int* count, unsigned* weights);
+int jspsr_area_forward(const unsigned char* src, long long src_numel, unsigned char* dst, long long dst_numel,
+                       const long long* table, const long long* host_table, int n, int channels, int mode,
+                       jspsr_stream_t stream);
+
 /* One AdamW step (torch.optim.AdamW semantics: decoupled weight decay, bias correction) over a flat
  * fp32 parameter / gradient / moment buffer of n elements (utils/common_config.py:241-291).  The four pointers are
  * 4-byte aligned and share one offset from a 16-byte boundary (sub-ranges of four identically laid out buffers). */

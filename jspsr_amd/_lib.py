@@ -120,6 +120,8 @@ SIGNATURES = {
     "jspsr_slope_classes": (c_i, [c_p, c_ll, c_p, c_i, c_p, c_i, c_p, c_ll, c_p, c_p]),
     "jspsr_resample_axis": (c_i, [c_i, c_i, c_i, c_p, c_p]),
     "jspsr_resample_forward": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_p, c_p, c_ll, c_i, c_p, c_p, c_p, c_p]),
+    "jspsr_area_axis": (c_i, [c_i, c_i, c_p, c_p, c_p]),
+    "jspsr_area_forward": (c_i, [c_p, c_ll, c_p, c_ll, c_p, c_p, c_i, c_i, c_i, c_p]),
     "jspsr_adamw_step": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_i, c_p]),
     "jspsr_adamw_step_dev": (c_i, [c_p, c_p, c_p, c_p, c_ll, c_p, c_p]),
     "jspsr_optim_workspace_bytes": (ctypes.c_size_t, []),

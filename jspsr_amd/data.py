@@ -27,6 +27,7 @@ from .tiles import get_tile
 
 KINDS = ("lr_dem", "hr_dem", "image", "mask", "canopy", "coord")   # the C ABI's kind indices 0..5
 CONCAT_ORDER = ("lr_dem", "image", "mask", "canopy", "coord")      # EDSR's input, utils/utils.py:248-315
+GUIDES = ("image", "mask", "canopy")                                # the kinds `guide_resample` takes on finer grids (K26)
 _DTYPE = {"lr_dem": np.float32, "hr_dem": np.float32, "image": np.uint8, "mask": np.uint8, "canopy": np.uint8}
 LOG, SCALE_MASK, IMAGE_11, LABEL_11, IMAGE_255 = 1, 2, 4, 8, 16   # JSPSR_BATCH_* (include/jspsr_hip.h)
 ROW = 8                                                            # int32 words per sample-table row
@@ -90,13 +91,26 @@ class DeviceScenes:
     go below the `relative` base or reach the log of a non-positive number.  `shapes` holds the scenes' (fine) shapes,
     `lr_shapes` the coarse ones; after construction the store is what host-resampled scenes would have given, and batches,
     prepare and every pass downstream are unchanged.  lr_resample=None (the default) keeps requiring equal shapes.
+
+    Imagery at its own resolution (K26, csrc/area.hip, `resample.area_rasters`): with `guide_resample="area"` image[i],
+    mask[i] and canopy[i] may each lie on a FINER grid of their own -- 0.5-2 m orthophotos and land cover under an 8 m scene,
+    any ratio >= 1 per axis, independent per kind and per scene, the extents taken as equal.  The scene's shape is hr_dem's
+    where the store has one, else lr_dem's when `lr_resample` is None, else `lr_shape=` (required then: the guidance rasters
+    fix nothing).  The fine rasters are what is uploaded and what the mask and canopy range checks read (a maximum of <= 1 or
+    <= 68 survives a mean); ONE launch per kind at construction then brings every scene to its shape: image and canopy by
+    the exact area mean rounded half up, the one-hot mask by the majority rule (the class of largest coverage, the lowest
+    index among equals, if it covers at least as much as no class does).  `store[kind]` is the result, the fine buffer is
+    dropped, `guide_shapes[kind]` keeps the shapes the rasters came in.  A guidance raster smaller than its scene on either
+    axis is a ValueError.  Afterwards the store is what host-resampled rasters would have given, bit for bit, and
+    `lr_resample`, `nodata`, batches, prepare and every pass downstream work on it unchanged.  guide_resample=None (the
+    default) keeps requiring equal shapes.
     """
 
     def __init__(self, lr_dem: Sequence, hr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *,
                  relative: bool = False, elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, label_range: str | None = None,
                  normalize: Sequence[str] | None = None, ids: Sequence[str] | None = None, device="cuda", nodata=None,
-                 hr_nodata=None, valid=None, lr_resample: str | None = None, lr_shape=None):
+                 hr_nodata=None, valid=None, lr_resample: str | None = None, lr_shape=None, guide_resample: str | None = None):
         if hr_dem is None:                      # only `infer.InferenceScenes` builds a store without a ground truth
             raise KeyError("hr_dem")
         if nodata is not None:
@@ -106,17 +120,21 @@ class DeviceScenes:
         self._setup({"lr_dem": lr_dem, "hr_dem": hr_dem, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=label_range, normalize=normalize, ids=ids, device=device,
-                    hr_nodata=hr_nodata, valid=valid, lr_resample=lr_resample, lr_shape=lr_shape)
+                    hr_nodata=hr_nodata, valid=valid, lr_resample=lr_resample, lr_shape=lr_shape, guide_resample=guide_resample)
 
     def _setup(self, raw: dict, coord, *, relative, elev_min, elev_max, elev_log, scale_mask, mask_channel, image_range,
                label_range, normalize, ids, device, base=None, nodata=None, void_margin=0, fill_limit=None, hr_nodata=None,
-               valid=None, lr_resample=None, lr_shape=None):
+               valid=None, lr_resample=None, lr_shape=None, guide_resample=None):
         """Checks, layout and upload of a store holding the kinds of `raw` that are not None (`infer.InferenceScenes` is
         the same store without hr_dem).  base: per-scene base elevations instead of `np.min(lr_dem)`.  nodata, void_margin,
         fill_limit: the voids of lr_dem (K17, `infer.InferenceScenes`); nodata=None changes nothing.  hr_nodata, valid: the
         voids of hr_dem (K19, see the class docstring); both None changes nothing.  lr_resample, lr_shape: lr_dem on a
-        coarser grid of its own (K25, see the class docstring); lr_resample=None changes nothing."""
+        coarser grid of its own (K25, see the class docstring); lr_resample=None changes nothing.  guide_resample: image,
+        mask and canopy on finer grids of their own (K26, see the class docstring); None changes nothing."""
         lr_dem = raw["lr_dem"]
+        if guide_resample not in (None, "area"):
+            raise ValueError(f"guide_resample must be None or 'area', got {guide_resample!r}")
+        guided = guide_resample is not None
         if lr_resample is not None:
             from . import resample                                   # resample imports infer, which imports this module
             resample._mode(lr_resample)
@@ -157,11 +175,20 @@ class DeviceScenes:
             if kind in host and self.channels[kind] != 1:
                 raise ValueError(f"{kind} has {self.channels[kind]} channels, not 1")
         self.lr_shapes = [a.shape[:2] for a in host["lr_dem"]]
-        self.shapes = self.lr_shapes if lr_resample is None else self._fine_shapes(host, lr_shape)
+        self.shapes = self.lr_shapes if lr_resample is None else self._fine_shapes(host, lr_shape, guided)
         if lr_resample is None and lr_shape is not None:
             raise ValueError("lr_shape: only together with lr_resample")
+        if guided:
+            self.guide_shapes = {k: [tuple(a.shape[:2]) for a in host[k]] for k in GUIDES if k in host}
         for kind, arrs in host.items():
             for i, a in enumerate(arrs):
+                if guided and kind in GUIDES and a.shape[2] == self.channels[kind]:
+                    if a.shape[0] < self.shapes[i][0] or a.shape[1] < self.shapes[i][1]:
+                        raise ValueError(f"{kind}[{i}] is {a.shape[0]} x {a.shape[1]}, its scene {self.shapes[i][0]} x "
+                                         f"{self.shapes[i][1]}: upsampling of image / mask / canopy is not built")
+                    if max(a.shape[:2]) > 65535:
+                        raise ValueError(f"{kind}[{i}] is {a.shape[0]} x {a.shape[1]}: guide_resample takes sides up to 65535")
+                    continue
                 if a.shape[2] != self.channels[kind] or a.shape[:2] != (self.lr_shapes if kind == "lr_dem" else self.shapes)[i]:
                     raise ValueError(f"{kind}[{i}] {a.shape} does not match lr_dem {host['lr_dem'][i].shape} / "
                                      f"{self.channels[kind]} channels" if lr_resample is None else
@@ -201,6 +228,8 @@ class DeviceScenes:
         # one flat buffer per kind; the store is never modified
         self.store = {k: torch.from_numpy(np.concatenate([a.reshape(-1) for a in v])).to(self.device) for k, v in host.items()
                       if lr_resample is None or k != "lr_dem"}
+        if guided:
+            self._resample_guides()
         self.flags = ((LOG if elev_log else 0) | (SCALE_MASK if scale_mask else 0) | (IMAGE_11 if image_range == "[-1, 1]" else 0)
                       | (LABEL_11 if label_range == "[-1, 1]" else 0) | (IMAGE_255 if image_range == "[0, 255]" else 0))
         if lr_resample is not None:
@@ -276,12 +305,23 @@ class DeviceScenes:
         return (d2 >= 0).to(torch.uint8)
 
     lr_clamp = None                              # K25: per-scene (lo, hi) the resampled lr_dem was clamped to, if any
+    guide_shapes = None                          # K26: kind -> per-scene (h, w) the guidance rasters came in, if guide_resample
 
-    def _fine_shapes(self, host: dict, lr_shape) -> list:
+    def _resample_guides(self):
+        """The device side of `guide_resample` (K26, csrc/area.hip), once, at construction: the fine rasters of image, mask
+        and canopy are what was uploaded; ONE launch per kind brings every scene's raster to the scene's shape -- the exact
+        area mean for image and canopy, the majority rule for the one-hot mask -- and the fine buffer is dropped."""
+        from . import infer, resample
+        for kind, shapes in self.guide_shapes.items():
+            self.store[kind], _ = resample.area_rasters(self.store[kind], infer._host_table(shapes), self.channels[kind], self.shapes,
+                                                        "majority" if kind == "mask" else "area")
+
+    def _fine_shapes(self, host: dict, lr_shape, guided: bool = False) -> list:
         """The scenes' shapes under `lr_resample`: those of the rasters other than lr_dem, else `lr_shape` -- one (H, W) for
-        all scenes or one per scene.  No side of a scene may be shorter than its lr_dem's."""
+        all scenes or one per scene.  No side of a scene may be shorter than its lr_dem's.  Under `guide_resample` image,
+        mask and canopy have grids of their own and fix nothing: hr_dem does, else `lr_shape`."""
         n = len(host["lr_dem"])
-        others = [k for k in host if k != "lr_dem"]
+        others = [k for k in host if k != "lr_dem" and not (guided and k in GUIDES)]
         if lr_shape is not None:
             given = np.asarray(lr_shape, dtype=np.int64)
             if given.shape not in ((2,), (n, 2)):

@@ -160,17 +160,24 @@ class InferenceScenes(DeviceScenes):
     lr_dem.  With `nodata` the voids are found and filled on lr_dem's own grid (`fill_limit` and `void_counts` in its
     pixels), `void` is written on the scene's grid -- a pixel is a void where its centre tap (the lr_dem pixel at the floor of its
     coordinate) is -- and
-    `void_margin` is applied there.  After construction the store is what host-resampled scenes would have given."""
+    `void_margin` is applied there.  After construction the store is what host-resampled scenes would have given.
+
+    Imagery at its own resolution (K26, csrc/area.hip; `data.DeviceScenes` has the whole account).  guide_resample="area":
+    image[i], mask[i] and canopy[i] may each be finer than scene i, any ratio >= 1 per axis; the scene's shape is lr_dem's,
+    or `lr_shape=` together with `lr_resample`.  They are uploaded as they are and brought to the scene's grid on the device
+    at construction, one launch per kind: the exact area mean for image and canopy, the majority rule for the mask.
+    `guide_shapes[kind]` keeps the shapes they came in."""
 
     def __init__(self, lr_dem: Sequence, image=None, mask=None, canopy=None, coord=None, *, relative: bool = False,
                  elev_min: float, elev_max: float, elev_log: bool = False, scale_mask: bool = False,
                  mask_channel: Sequence[int] | None = None, image_range: str | None = None, ids: Sequence[str] | None = None,
                  device="cuda", base: Sequence | None = None, nodata=None, void_margin: int = 0, fill_limit: int | None = None,
-                 lr_resample: str | None = None, lr_shape=None):
+                 lr_resample: str | None = None, lr_shape=None, guide_resample: str | None = None):
         self._setup({"lr_dem": lr_dem, "hr_dem": None, "image": image, "mask": mask, "canopy": canopy}, coord, relative=relative,
                     elev_min=elev_min, elev_max=elev_max, elev_log=elev_log, scale_mask=scale_mask, mask_channel=mask_channel,
                     image_range=image_range, label_range=None, normalize=None, ids=ids, device=device, base=base,
-                    nodata=nodata, void_margin=void_margin, fill_limit=fill_limit, lr_resample=lr_resample, lr_shape=lr_shape)
+                    nodata=nodata, void_margin=void_margin, fill_limit=fill_limit, lr_resample=lr_resample, lr_shape=lr_shape,
+                    guide_resample=guide_resample)
 
 
 def _input_kinds(scenes):
