@@ -18,6 +18,12 @@ int conv_dynq_override();      // jspsr_conv_dynamic_queue(): -1 = the environme
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
+// Workgroups of 256 for n items of a grid-stride loop
+inline int blocks_for(long long n) {
+  long long b = (n + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+
 // Workgroups b and b+8 share an XCD (private 4 MiB L2) under the observed round-robin dispatch.
 // Bijective remap that hands every XCD one contiguous run of logical tile ids, so that
 // neighbouring tiles (which share halo rows / operand panels) hit the same L2.  Speed only.

@@ -4,9 +4,7 @@
 //                         (evaluation/evaluate_utils.py:242-271), ONE launch
 // HBM streaming, 4 B in, 4 B out.  No LDS: a thread makes four consecutive pixels of a row of the scene's window, so a wave
 // writes 1 KiB runs (16-byte stores when W % 4 == 0 and the output is 16-byte aligned).
-#include "scene_prepare.h"
-
-#include <cmath>
+#include "scene_finish.h"
 
 namespace {
 
@@ -15,8 +13,8 @@ using namespace jspsr;
 // out[b][y][x] = pred[b][top + y][left + x], in metres (to_metres) or as it is
 __global__ __launch_bounds__(256) void scene_finish_kernel(const void* __restrict__ pred, float* __restrict__ out,
                                                           const int* __restrict__ samples, int bf16, int B, int Hp, int Wp,
-                                                          int top, int left, int H, int W, int metres, int elev_log, float lo,
-                                                          float span, float log_span, int vec) {
+                                                          int top, int left, int H, int W, int metres, int elev_log, ElevRange e,
+                                                          int vec) {
   const int Wq = (W + 3) >> 2;
   const long long total = (long long)B * H * Wq;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -29,14 +27,9 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const void* __restric
     float v[4];
     for (int q = 0; q < 4; ++q) {
       const float t = load_pred(pred, s + min(q, n - 1), bf16);
-      v[q] = metres ? to_metres(t, elev_log, lo, span, log_span, base) : t;
+      v[q] = metres ? to_metres(t, elev_log, e.lo, e.span, e.log_span, base) : t;
     }
-    float* o = out + ((size_t)b * H + y) * W + x;
-    if (vec) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      for (int q = 0; q < n; ++q) o[q] = v[q];
-    }
+    store_quad(out + ((size_t)b * H + y) * W + x, v, n, vec);
   }
 }
 
@@ -53,12 +46,9 @@ extern "C" int jspsr_scene_finish(int dtype, const void* pred, float* out, const
   const int bf16 = dtype == JSPSR_BF16;
   if (!jspsr::aligned4(out) || (reinterpret_cast<uintptr_t>(pred) & (bf16 ? 1u : 3u)))
     return jspsr::fail(JSPSR_EALIGN, "scene_finish: pointers not aligned to their element size");
-  // the constants as the reference's Python forms them (doubles), rounded once to the tensors' fp32 (jspsr_elev_scale_f32)
-  const float span = (float)(elev_max - elev_min);
-  const float log_span = (float)log(elev_max - elev_min);
   const long long items = (long long)B * H * ((W + 3) / 4);
   hipLaunchKernelGGL(scene_finish_kernel, dim3(blocks_for(items)), dim3(256), 0, static_cast<hipStream_t>(stream), pred, out, samples,
-                     bf16, B, Hp, Wp, top, left, H, W, metres ? 1 : 0, elev_log ? 1 : 0, (float)elev_min, span, log_span,
+                     bf16, B, Hp, Wp, top, left, H, W, metres ? 1 : 0, elev_log ? 1 : 0, elev_range(elev_min, elev_max),
                      (W & 3) == 0 && jspsr::aligned16(out));
   return jspsr::check_launch("scene_finish");
 }

@@ -1,14 +1,15 @@
-// The parts that the whole-scene entries share (K13-K16: scene_prepare.hip, scene.hip, scene_tta.hip, scene_tiles.hip).
+// The parts that the whole-scene prepare entries share (K13-K16: scene_prepare.hip; the steps after the model are in
+// scene_finish.h).
 //
 // prepare: out[b][c][Y][X] = ToTensor_kind(store pixel (sy, sx) of sample b's scene), (sy, sx) = geometry(b, Y, X).  The
 // geometry is a compile-time policy of the two kernel templates in scene_prepare.hip; everything here is the same for
 // every geometry: the argument block, the scene lookup, the staging of a block of the HWC store in LDS and its read-out,
 // and the epilogue that writes four consecutive pixels of a row in every channel of a kind.
-// finish / finish_mean / merge: the prediction load and the metre conversion, one rounding per operation.
 // Every translation unit that includes this is built with -ffp-contract=off (csrc/Makefile).
 #pragma once
 #include "common.h"
 #include "d4.h"
+#include "scene_finish.h"   // store_quad
 #include "totensor.h"
 
 #include <climits>
@@ -40,11 +41,6 @@ struct PrepareArgs {
   double log_span;            // log(elev_max - elev_min)
 };
 
-inline int blocks_for(long long n) {
-  long long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 // The scene `scene` of the table: false unless it lies inside the store of kind d.  With a D4 code the sides must fit an
 // int and the code must have the launch's rot90 parity.
 template <bool D4>
@@ -74,11 +70,7 @@ __device__ __forceinline__ void write_quad(const PrepareArgs& a, const KindDesc&
 #pragma unroll kUnroll
     for (int q = 0; q < 4; ++q)
       v[q] = okp[q] ? transform(d.kind, c, bytes(q, c), base, (int)sy[q], (int)sx[q], H, W, a) : __int_as_float(0x7fc00000);
-    if (d.vec) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      for (int q = 0; q < n; ++q) o[q] = v[q];
-    }
+    store_quad(o, v, n, d.vec);
   }
 }
 
@@ -119,19 +111,6 @@ __device__ __forceinline__ void stage_block(const KindDesc& d, const Block& k, l
 // One channel value's bytes, es = 4 or 1 of them
 __device__ __forceinline__ unsigned int channel_bytes(const unsigned char* p, int es) {
   return es == 4 ? *reinterpret_cast<const unsigned int*>(p) : (unsigned int)*p;
-}
-
-__device__ __forceinline__ float load_pred(const void* p, size_t i, int bf16) {
-  if (bf16) return __uint_as_float((unsigned int)static_cast<const unsigned short*>(p)[i] << 16);
-  return static_cast<const float*>(p)[i];
-}
-
-// A prediction in metres: clamp (a NaN stays a NaN, as torch.clamp leaves it), descale_data's two roundings, + base --
-// elev_scale_kernel's expressions (csrc/tiles.hip), the bits of summary.compose_scene
-__device__ __forceinline__ float to_metres(float t, int elev_log, float lo, float span, float log_span, float base) {
-  t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-  t = elev_log ? __fadd_rn(expf(__fmul_rn(t, log_span)), lo) : __fadd_rn(__fmul_rn(t, span), lo);
-  return __fadd_rn(t, base);
 }
 
 }  // namespace jspsr

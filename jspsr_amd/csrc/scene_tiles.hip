@@ -10,9 +10,7 @@
 // every run.
 //
 // All offsets into the tile buffer and the output are 64-bit: the cover of a 37 000 x 37 000 scene passes 2^31 bytes.
-#include "scene_prepare.h"
-
-#include <cmath>
+#include "scene_finish.h"
 
 namespace {
 
@@ -29,12 +27,12 @@ struct MergeArgs {
   const int* samples;         // [S][2] {scene, base (fp32 bits)}
   float* out;                 // [S][H][W]
   int bf16, S, n_y, n_x, kh, kw, H, W, metres, elev_log, vec;
-  float lo, span, log_span;
+  ElevRange e;
 };
 
 // out[s][y][x] = sum over the (at most 2 x 2) tiles with non-zero weights there, row-major, of (m * wx) * wy; m the tile
 // value in metres (to_metres) or as it is.  The sum is scenes_assemble_kernel's
-// (csrc/summary.hip): acc starts at 0, every product and sum rounded on its own.
+// (csrc/summary.hip): acc starts at 0 and takes feather_add.
 __global__ __launch_bounds__(256) void scene_merge_windows_kernel(MergeArgs a) {
   const int Wq = (a.W + 3) >> 2;
   const long long total = (long long)a.S * a.H * Wq;
@@ -79,18 +77,13 @@ __global__ __launch_bounds__(256) void scene_merge_windows_kernel(MergeArgs a) {
           if (jx[w] < 0 || wx[w] == 0.f) continue;                     // a tile of weight zero is not read
           const size_t t = ((size_t)s * a.n_y + (ty0 + u)) * a.n_x + (tx0 + w);
           float m = load_pred(a.tiles, t * tile + (size_t)jy[u] * a.kw + jx[w], a.bf16);
-          if (a.metres) m = to_metres(m, a.elev_log, a.lo, a.span, a.log_span, base);
-          acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(m, wx[w]), wy[u]));
+          if (a.metres) m = to_metres(m, a.elev_log, a.e.lo, a.e.span, a.e.log_span, base);
+          acc = feather_add(acc, m, wx[w], wy[u]);
         }
       }
       v[q] = acc;
     }
-    float* o = a.out + ((size_t)s * a.H + y) * a.W + x0;
-    if (a.vec) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      for (int q = 0; q < n; ++q) o[q] = v[q];
-    }
+    store_quad(a.out + ((size_t)s * a.H + y) * a.W + x0, v, n, a.vec);
   }
 }
 
@@ -130,10 +123,7 @@ extern "C" int jspsr_scene_merge_windows(int dtype, const void* tiles, const flo
   a.metres = metres ? 1 : 0;
   a.elev_log = elev_log ? 1 : 0;
   a.vec = (W & 3) == 0 && jspsr::aligned16(out);
-  // the constants as the reference's Python forms them (doubles), rounded once to the tensors' fp32 (jspsr_scene_finish)
-  a.lo = (float)elev_min;
-  a.span = (float)(elev_max - elev_min);
-  a.log_span = (float)log(elev_max - elev_min);
+  a.e = elev_range(elev_min, elev_max);
   const long long items = (long long)S * H * ((W + 3) / 4);
   hipLaunchKernelGGL(scene_merge_windows_kernel, dim3(blocks_for(items)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return jspsr::check_launch("scene_merge_windows");

@@ -9,10 +9,10 @@
 // (16.9 KiB: of eight distinct elements four are quarter turns, and the entry point refuses duplicates) and read transposed --
 // pitch 33: lane (oy, ox) reads bank (ox + p + oy) mod 32 up to reflection, and within 32 lanes ox is a multiple of 4 and oy
 // spans 4 values: conflict-free.
-#include "scene_prepare.h"
+#include "scene_finish.h"
+#include "scene_prepare.h"   // kTile, d4_image
 
 #include <climits>
-#include <cmath>
 
 namespace {
 
@@ -32,7 +32,8 @@ struct MeanArgs {
   float* out;                 // [B][H][W]
   const int* samples;         // [B][2] {scene, base (fp32 bits)}
   int K, B, H, W, metres, elev_log, vec;
-  float lo, span, log_span, count;
+  ElevRange e;
+  float count;
 };
 
 // out[b][y][x] = post((((y'_0 + y'_1) + y'_2) + ...) / K), y'_k[y][x] = pred_k[b][top_k + i][left_k + j] with (i, j) the
@@ -86,14 +87,9 @@ __global__ __launch_bounds__(256) void scene_finish_mean_kernel(MeanArgs a, int 
   float r[4];
   for (int q = 0; q < 4; ++q) {
     const float t = __fdiv_rn(acc[q], a.count);                       // K = 1: x / 1.0f is x
-    r[q] = a.metres ? to_metres(t, a.elev_log, a.lo, a.span, a.log_span, base) : t;
+    r[q] = a.metres ? to_metres(t, a.elev_log, a.e.lo, a.e.span, a.e.log_span, base) : t;
   }
-  float* o = a.out + ((size_t)b * a.H + y) * a.W + x0 + ox;
-  if (a.vec) {
-    *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-  } else {
-    for (int q = 0; q < n; ++q) o[q] = r[q];
-  }
+  store_quad(a.out + ((size_t)b * a.H + y) * a.W + x0 + ox, r, n, a.vec);
 }
 
 // The element a code denotes, as the code with flip_ud clear: flipud = fliplr after a half turn
@@ -137,10 +133,7 @@ extern "C" int jspsr_scene_finish_mean(const jspsr_tta_variant* variants, int K,
   a.metres = metres ? 1 : 0;
   a.elev_log = elev_log ? 1 : 0;
   a.vec = (W & 3) == 0 && jspsr::aligned16(out);
-  // the constants as the reference's Python forms them (doubles), rounded once to the tensors' fp32 (jspsr_scene_finish)
-  a.lo = (float)elev_min;
-  a.span = (float)(elev_max - elev_min);
-  a.log_span = (float)log(elev_max - elev_min);
+  a.e = elev_range(elev_min, elev_max);
   a.count = (float)K;
   const long long tiles_x = (W + kTile - 1) / kTile, tiles = tiles_x * ((H + kTile - 1) / kTile);
   if (tiles > INT_MAX) return jspsr::fail(JSPSR_EINVAL, "scene_finish_mean: a %d x %d scene has too many tiles", H, W);

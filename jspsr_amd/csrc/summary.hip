@@ -5,9 +5,9 @@
 //   * summarise_evaluation       utils/utils.py:1238-1356   RMSE, median, NMAD, LE95, PSNR of the errors of ALL scenes
 //                                pooled, for the prediction and every baseline DEM against the ground truth
 // (a) jspsr_scenes_assemble_f32: clamp, de-scale, + base and the feather merge of every scene of a batch in ONE launch,
-//     each mosaic written at its own offset of one pooled buffer.  The expressions of elev_scale_kernel and
-//     tiles_merge_kernel (csrc/tiles.hip), rounded one by one (this file is built with -ffp-contract=off): the bits of
-//     clamp -> descale_data -> + base -> merge_tiles run scene by scene.
+//     each mosaic written at its own offset of one pooled buffer.  tiles_merge_kernel's loop (csrc/tiles.hip) over
+//     to_metres, ramp_weight and feather_add, the statements K8 uses (scene_finish.h), rounded one by one (this file is
+//     built with -ffp-contract=off): the bits of clamp -> descale_data -> + base -> merge_tiles run scene by scene.
 // (b) jspsr_summary_forward: pooled scores of n_cand candidates against one ground truth over a table of pitched
 //     windows grouped into segments.  A streaming selection:
 //       prepare   reads the candidate and the ground truth through the window table (pooled_read.h: the reader K21 and
@@ -39,6 +39,7 @@
 // without the 1e-8 the reference's online form adds for the baselines.
 #include "common.h"
 #include "pooled_read.h"
+#include "scene_finish.h"
 #include "summary_select.h"
 
 #include <cmath>
@@ -54,25 +55,10 @@ constexpr int SEG_WORDS = 8;                  // e start, n, first chunk, 4 rank
 static_assert(CHUNK % (MT * UNROLL) == 0, "a chunk is a whole number of unrolled steps");
 
 // ---- (a) scene assembly --------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ramp_weight(const float* __restrict__ ramp, int p, int w_l_c, int n_x, int pos, int j) {
-  float w = 1.f;
-  if (pos > 0 && j < p) w = ramp[p - 1 - j];
-  if (pos < n_x - 1 && j >= w_l_c - p) w = ramp[j - (w_l_c - p)];
-  return w;
-}
-
-// network range -> metres: clamp (a NaN stays a NaN, as torch.clamp leaves it), descale_data's two roundings, + base
-__device__ __forceinline__ float to_metres(float t, int elev_log, float lo, float span, float log_span, float base) {
-  const float v = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-  const float d = elev_log ? __fadd_rn(expf(__fmul_rn(v, log_span)), lo) : __fadd_rn(__fmul_rn(v, span), lo);
-  return __fadd_rn(d, base);
-}
-
 __global__ __launch_bounds__(256) void scenes_assemble_kernel(const float* __restrict__ tiles, const float* __restrict__ base,
                                                              const float* __restrict__ ramp, float* __restrict__ out,
                                                              const long long* __restrict__ out_off, long long out_numel, int n_x,
-                                                             int k, int b, int s, int w_l_c, int w_h_c, int elev_log, float lo,
-                                                             float span, float log_span) {
+                                                             int k, int b, int s, int w_l_c, int w_h_c, int elev_log, ElevRange e) {
   const int scene = blockIdx.y;
   const long long total = (long long)w_h_c * w_h_c;
   const long long off = out_off[scene];
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(256) void scenes_assemble_kernel(const float* __res
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int X = (int)(i % w_h_c), Y = (int)(i / w_h_c);
     if (n_x == 1) {                                             // the 8 m case: the de-scaled tile, uncropped
-      o[i] = to_metres(t0[i], elev_log, lo, span, log_span, bs);
+      o[i] = to_metres(t0[i], elev_log, e.lo, e.span, e.log_span, bs);
       continue;
     }
     float acc = 0.f;
@@ -96,8 +82,8 @@ __global__ __launch_bounds__(256) void scenes_assemble_kernel(const float* __res
         const int jx = X - s * c;
         if (jx < 0 || jx >= w_l_c) continue;
         const float wx = ramp_weight(ramp, p, w_l_c, n_x, c, jx);
-        const float t = to_metres(t0[((size_t)(r * n_x + c) * k + b + jy) * k + b + jx], elev_log, lo, span, log_span, bs);
-        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(t, wx), wy));      // (t * wx) * wy, then the add, as tiles_merge_kernel
+        const float t = to_metres(t0[((size_t)(r * n_x + c) * k + b + jy) * k + b + jx], elev_log, e.lo, e.span, e.log_span, bs);
+        acc = feather_add(acc, t, wx, wy);
       }
     }
     o[i] = acc;
@@ -367,10 +353,8 @@ extern "C" int jspsr_scenes_assemble_f32(const float* tiles, const float* base, 
   const long long total = (long long)w_h_c * w_h_c;
   long long blocks = (total + 255) / 256;
   blocks = blocks > 4096 ? 4096 : blocks;
-  // the constants as jspsr_elev_scale_f32 forms them: the reference's Python doubles, rounded once to fp32
   hipLaunchKernelGGL(scenes_assemble_kernel, dim3((unsigned)blocks, S), dim3(256), 0, static_cast<hipStream_t>(stream), tiles, base, ramp,
-                     out, out_off, out_numel, n_x, k, b, stride, w_l_c, w_h_c, elev_log ? 1 : 0, (float)elev_min,
-                     (float)(elev_max - elev_min), (float)log(elev_max - elev_min));
+                     out, out_off, out_numel, n_x, k, b, stride, w_l_c, w_h_c, elev_log ? 1 : 0, elev_range(elev_min, elev_max));
   return check_launch("scenes_assemble");
 }
 

@@ -3,13 +3,13 @@
 // merge_dem(method = copyto_add), utils/utils.py:802-967), the mirror padding of whole-scene inference (add_padding,
 // utils/utils.py:1501-1520) and the elevation scaling / de-scaling (ToTensor.scale_data / ToDEM.descale_data,
 // data/data_utils.py:289-312, 441-457).  HBM-bound one-pass kernels; the merge is a GATHER (every mosaic pixel sums the
-// <= 4 tiles that cover it, in tile order -- the reference's own order of additions -- instead of n read-modify-write
+// tiles that cover it, in tile order -- the reference's own order of additions -- instead of n read-modify-write
 // passes over the mosaic).
-#include "common.h"
-
-#include <cmath>
+#include "scene_finish.h"
 
 namespace {
+
+using namespace jspsr;
 
 // out[i][c][y][x] = x[c][stride r + y][stride col + x], i = r n_x + col
 __global__ __launch_bounds__(256) void tiles_crop_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W,
@@ -26,21 +26,10 @@ __global__ __launch_bounds__(256) void tiles_crop_kernel(const float* __restrict
   }
 }
 
-// weight of position j (0 .. w_l_c-1) of a tile at cover position pos (0 .. n_x-1): 1 inside, the linear ramp over the
-// p = w_l_c - s pixels it shares with a neighbour (utils.py:802-895: linspace(1, 0, p + 2) without its ends)
-__device__ __forceinline__ float ramp_weight(const float* __restrict__ ramp, int p, int w_l_c, int n_x, int pos, int j) {
-  float w = 1.f;
-  if (pos > 0 && j < p) w = ramp[p - 1 - j];
-  if (pos < n_x - 1 && j >= w_l_c - p) w = ramp[j - (w_l_c - p)];
-  return w;
-}
-
 // mosaic[Y][X] = sum over the tiles (r, c) covering it, in tile order, of tile[r n_x + c][b + Y - s r][b + X - s c] * wx * wy
 __global__ __launch_bounds__(256) void tiles_merge_kernel(const float* __restrict__ tiles, const float* __restrict__ ramp,
                                                          float* __restrict__ out, int n_x, int k, int b, int s, int w_l_c,
                                                          int w_h_c) {
-  // (hipcc contracts a * b + c into a fused multiply-add by default, __fmul_rn / __fadd_rn included: this file is built with
-  // -ffp-contract=off, csrc/Makefile)
   const int p = w_l_c - s;
   const long long total = (long long)w_h_c * w_h_c;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -54,8 +43,7 @@ __global__ __launch_bounds__(256) void tiles_merge_kernel(const float* __restric
         const int jx = X - s * c;
         if (jx < 0 || jx >= w_l_c) continue;
         const float wx = ramp_weight(ramp, p, w_l_c, n_x, c, jx);
-        const float t = tiles[((size_t)(r * n_x + c) * k + b + jy) * k + b + jx];
-        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(t, wx), wy));      // (t * wx) * wy, then the add: no contraction -- the bits of the tile-by-tile composition
+        acc = feather_add(acc, tiles[((size_t)(r * n_x + c) * k + b + jy) * k + b + jx], wx, wy);      // the bits of the tile-by-tile composition
       }
     }
     out[i] = acc;
@@ -89,19 +77,12 @@ __global__ __launch_bounds__(256) void elev_scale_kernel(const float* __restrict
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float v = in[i];
     float o;
-    // every operation rounded on its own, as the reference's element-wise tensor expressions are (no fused multiply-add: the
-    // scores are differences of de-scaled elevations of ~500 m, where a contraction moves the last bit and the median with it)
+    // every operation rounded on its own, as the reference's element-wise tensor expressions are (descale, scene_finish.h)
     if (mode == 0) o = __fdiv_rn(__fsub_rn(__fsub_rn(v, base), lo), span);
     else if (mode == 1) o = __fadd_rn(__fdiv_rn(logf(__fsub_rn(__fsub_rn(v, base), lo)), log_span), 1e-8f);
-    else if (mode == 2) o = __fadd_rn(__fmul_rn(v, span), lo);
-    else o = __fadd_rn(expf(__fmul_rn(v, log_span)), lo);
+    else o = descale(v, mode == 3, lo, span, log_span);
     out[i] = o;
   }
-}
-
-int blocks_for(long long n) {
-  long long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
 }  // namespace
@@ -135,10 +116,8 @@ extern "C" int jspsr_mirror_pad_f32(const float* x, float* out, int C, int H, in
 extern "C" int jspsr_elev_scale_f32(const float* in, float* out, long long n, int descale, int elev_log, double elev_min, double elev_max,
                                     double base_elev, jspsr_stream_t stream) {
   if (!in || !out || n <= 0 || !(elev_max > elev_min)) return jspsr::fail(JSPSR_EINVAL, "elev_scale: bad arguments");
-  // the constants as the reference's Python forms them (doubles), rounded once to the tensors' fp32
-  const float span = (float)(elev_max - elev_min);
-  const float log_span = (float)log(elev_max - elev_min);
+  const ElevRange e = elev_range(elev_min, elev_max);
   hipLaunchKernelGGL(elev_scale_kernel, dim3(blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), in, out, n,
-                     (descale ? 2 : 0) + (elev_log ? 1 : 0), (float)elev_min, span, log_span, descale ? 0.f : (float)base_elev);
+                     (descale ? 2 : 0) + (elev_log ? 1 : 0), e.lo, e.span, e.log_span, descale ? 0.f : (float)base_elev);
   return jspsr::check_launch("elev_scale");
 }
