@@ -114,20 +114,26 @@ class _FlatOptimizer:
     def enable_device_hyper(self):
         """From now on the kernels read lr / betas / eps / weight decay / bias corrections from a small device tensor per
         parameter group (jspsr_adamw_step_dev) that `upload_hyper()` refreshes -- the launches can then be captured in a
-        hipGraph and replayed while the learning rate and the step count move on.  Same arithmetic, same bits."""
+        hipGraph and replayed while the learning rate and the step count move on.  Same arithmetic, same bits -- also when
+        the host runs ahead of the GPU: every step reads the row that was uploaded for it, however many steps are queued
+        (see `upload_hyper`)."""
         if getattr(self, "_hyper_dev", None) is None:
-            n = len(self.param_groups)
-            self._hyper_host = torch.zeros((n, 8), dtype=torch.float32).pin_memory()
-            self._hyper_dev = torch.zeros((n, 8), dtype=torch.float32, device=self.flat_p.device)
+            self._hyper_dev = torch.zeros((len(self.param_groups), 8), dtype=torch.float32, device=self.flat_p.device)
         return self
 
     def upload_hyper(self, step=None):
         """Write the seven scalars of every group for step count `step` (default: the current one) into the device tensor;
-        an ordinary stream-ordered copy from pinned memory -- call it OUTSIDE a captured region."""
+        an ordinary stream-ordered copy from pinned memory -- call it OUTSIDE a captured region.
+
+        The copy may still be queued behind GPU work when the next call comes (a loop that synchronises once per epoch,
+        `GraphedStep` replays), so the host rows it reads are never written again: every call fills a NEW pinned tensor.
+        The caching host allocator records the copy's stream on that block and hands it out again only once the copy has
+        run; a call neither waits for the GPU nor, in the steady state, allocates."""
         step = self.steps if step is None else step
-        for i, g in enumerate(self.param_groups):
-            self._hyper_host[i, :7] = torch.tensor(self._row(g, step), dtype=torch.float64).float()
-        self._hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        rows = [list(self._row(g, step)) + [0.0] for g in self.param_groups]
+        host = torch.empty((len(rows), 8), dtype=torch.float32, pin_memory=True)
+        host.copy_(torch.tensor(rows, dtype=torch.float64))      # rounds to fp32, as the argument form's C floats do
+        self._hyper_dev.copy_(host, non_blocking=True)
 
     # -- the fused gradient range ------------------------------------------------------------------------------------
     def fused_grad_range(self):
